@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's metric on its configs[1]: Mpoints/s for GausPcgc
 encode + decode of a 1M-anchor synthetic cloud on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one scene: gpcc_encode (points resident in
@@ -29,10 +29,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-
-# The HIP runtime multiplexes a process's streams onto 4 hardware queues by default; a context uses three streams, so two
-# scenes in flight (the `scenes_in_flight` pass) would share queues and serialise.  No effect on the timed one-scene region.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 MFMA_F32_PEAK_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, dense fp32 matrix peak
 HBM_PEAK_GBPS = 8000.0        # same guide: HBM3E 8.0 TB/s spec (6.3 TB/s measured with a float4 copy)
@@ -71,6 +67,28 @@ def launcher_selftest(args, rank, world):
     dist.destroy_process_group()
 
 
+def dump_outputs(out_dir, outputs, limit=64_000_000):
+    """--dump-outputs: outputs = (scene, container bytes, decoded (N, 3) int32 points) of every scene of the last timed step ->
+    out_dir/scene<i>_container_bytes.npy (float32) and out_dir/scene<i>_decoded_points.npy (float64), both exact.  Above `limit` bytes
+    in all, every array keeps the same share of its rows, at positions drawn from a fixed seed."""
+    arrays = {}
+    for scene, blob, points in sorted(outputs, key=lambda o: o[0]):
+        arrays[f"scene{scene}_container_bytes"] = np.frombuffer(bytes(blob), dtype=np.uint8).astype(np.float32)
+        arrays[f"scene{scene}_decoded_points"] = np.asarray(points.cpu() if hasattr(points, "cpu") else points).astype(np.float64)
+    room = limit - 128 * len(arrays)   # an .npy header of these shapes is 128 bytes
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = total > room
+    if sampled:
+        rng = np.random.default_rng(0)
+        for name, a in arrays.items():
+            keep = int(len(a) * room / total)
+            arrays[name] = a[np.sort(rng.choice(len(a), keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench: {len(arrays)} arrays of the last timed step in {out_dir}" + (" (seeded sample of rows)" if sampled else ""), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -95,10 +113,14 @@ def main():
     ap.add_argument("--skip-stages", action="store_true", help="do not run the extra pass that times the HBM-bound stages")
     ap.add_argument("--skip-sizes", action="store_true", help="do not run the untimed passes behind `sizes` (one scene of 10 k / 100 k / 1 M points) and `batched` "
                     "(K scenes through one chain of launches: gpcc_encode_batch / gpcc_decode_batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned to its caller -- every scene's "
+                    "container bytes and decoded points -- as DIR/scene<i>_<name>.npy (float32 / float64, at most 64 MB in all: a seeded sample of rows beyond that)")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)   # tests/test_dist_cpu.py: the N > 1 launch path on gloo, no GPU
     ap.add_argument("--selftest-scenes", type=int, default=0, help=argparse.SUPPRESS)     # (selftest) scenes of the batch in all; 0 = scenes_per_gpu x ranks
     ap.add_argument("--selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)  # (selftest) this rank exits before the rendezvous
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -155,7 +177,8 @@ def main():
 
     batch_mode = K > 1 and not args.solo_scenes and args.chunk_log2 != 0
 
-    def step():
+    def step(keep=None):
+        # keep (--dump-outputs, last timed step): a list that receives (scene, container, decoded points) of every scene of the step
         te = td = 0.0
         if batch_mode:
             # the rank's K scenes through ONE chain of launches; `data` / `dec` of the step are scene 0's (checked after the timed region)
@@ -168,10 +191,12 @@ def main():
             t2 = time.perf_counter()
             st0 = sts[0]
             st0.coded_nodes = sum(s_.coded_nodes for s_ in sts)
+            if keep is not None:
+                keep.extend(zip(my_scenes, views, decs))
             return views[0], st0, decs[0], t1 - t0, t2 - t1
-        for xi in reversed(xs_batch):   # scene 0 last: `data` / `dec` of the step are its (checked after the timed region)
+        for j in reversed(range(len(xs_batch))):   # scene 0 last: `data` / `dec` of the step are its (checked after the timed region)
             t0 = time.perf_counter()
-            data, st = _encode_view(xi, model, args.chunk_log2, 1)   # the bitstream stays in the library's pinned host buffer
+            data, st = _encode_view(xs_batch[j], model, args.chunk_log2, 1)   # the bitstream stays in the library's pinned host buffer
             torch.cuda.synchronize(device)
             t1 = time.perf_counter()
             dec, _, _ = _decode_bytes(data, model, device)
@@ -179,6 +204,11 @@ def main():
             t2 = time.perf_counter()
             te += t1 - t0
             td += t2 - t1
+            if keep is not None:
+                # the next scene's encode overwrites the buffer behind `data`: scenes other than the last keep a copy.  With --dump-outputs
+                # and K > 1 scenes coded one after the other, these host copies (one container each) fall inside the last timed step and
+                # so inside `elapsed` / ms_per_step; one scene, or K scenes through one chain of launches, copy nothing here
+                keep.append((my_scenes[j], data if j == 0 else bytes(data), dec))
         return data, st, dec, te, td
 
     for _ in range(args.warmup):
@@ -188,10 +218,11 @@ def main():
     barrier()
     t_start = time.perf_counter()
     enc_s = dec_s = 0.0
+    last_outputs = [] if args.dump_outputs else None
     for i in range(args.steps):
         if i == ev_steps and ev_steps > 0:
             _lib.check(L.gpcc_profile_enable(ctx, 3))   # keep what was collected, stop recording
-        data, st, dec, te, td = step()
+        data, st, dec, te, td = step(last_outputs if i == args.steps - 1 else None)
         enc_s += te
         dec_s += td
     barrier()
@@ -199,6 +230,8 @@ def main():
     prof = _lib.Profile()
     _lib.check(L.gpcc_profile_get(ctx, C.byref(prof)))
     _lib.check(L.gpcc_profile_enable(ctx, 0))
+    if args.dump_outputs:   # before the passes below: they encode again into the buffer the containers of the step are views of
+        dump_outputs(args.dump_outputs, last_outputs, limit=64_000_000 // world)   # every rank writes its own scenes
 
     # size of the same cloud in the reference's container layout (one coder stream per level and stage, chunk_log2 = 0):
     # what the chunked default costs in bytes, outside the timed region

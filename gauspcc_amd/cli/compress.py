@@ -98,7 +98,6 @@ def main(argv=None):
         from ..dist import launch_ranks
 
         return launch_ranks("gauspcc_amd.cli.compress", sys.argv[1:] if argv is None else list(argv), args.gpus, module=True)
-    io.export_hw_queues(args.jobs)
     import torch
 
     from .. import dist as gdist

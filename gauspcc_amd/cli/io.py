@@ -67,8 +67,8 @@ def run_jobs(fn, items, jobs=1, on_progress=None):
     """fn(item) for every item, results in item order (on_progress(results) after each completed item, with None for the
     items still running: the compress CLI rewrites its CSV there).  jobs > 1: that many host threads, each with its own torch stream (and,
     through runtime.context, its own gpcc context): the files of a batch are independent, and two in flight fill what one
-    leaves idle on the GPU (HISTORY.md section 7; the HIP runtime needs GPU_MAX_HW_QUEUES >= 3 x jobs for that, which main()
-    exports before the first GPU call)."""
+    leaves idle on the GPU (HISTORY.md section 7; how much they overlap depends on the hardware queues the HIP runtime gives
+    the process, which the environment decides)."""
     items = list(items)
     if jobs <= 1 or len(items) <= 1:
         out = []
@@ -116,15 +116,6 @@ def run_jobs(fn, items, jobs=1, on_progress=None):
         if err is not None:
             raise err
     return results
-
-
-def export_hw_queues(jobs):
-    """Before anything initialises HIP: the runtime maps a process's streams onto 4 hardware queues by default, a gpcc
-    context uses three streams."""
-    import os
-
-    if jobs > 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", str(max(8, 4 * jobs)))
 
 
 _WS_PEAK = [0]

@@ -1,7 +1,7 @@
 """Generate tests/golden/*.npz by IMPORTING the reference's pure-python helpers
-from /root/reference (this container only; the reference never travels).
+from a checkout of the reference project (it is not part of this repository).
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <reference checkout>
 
 Only inputs and the reference's outputs are stored -- no reference source text.
 torchsparse / torchac are absent here, so they are stubbed in
@@ -24,7 +24,6 @@ import types
 import numpy as np
 import torch
 
-REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -36,15 +35,15 @@ def _stub(name, **attrs):
     return m
 
 
-def import_reference():
+def import_reference(ref):
     _stub("torchac")
     ts = _stub("torchsparse", SparseTensor=object)
     nn = _stub("torchsparse.nn")
     fn = _stub("torchsparse.nn.functional")
     ts.nn = nn
     nn.functional = fn
-    sys.path.insert(0, os.path.join(REF, "src/ai_pcc/GausPcgc"))
-    sys.path.insert(0, os.path.join(REF, "src/gs_compress/HAC"))
+    sys.path.insert(0, os.path.join(ref, "src/ai_pcc/GausPcgc"))
+    sys.path.insert(0, os.path.join(ref, "src/gs_compress/HAC"))
     pcc_utils = importlib.import_module("utils.pcc_utils")
     op = importlib.import_module("kit.op")
     image_utils = importlib.import_module("utils.image_utils")
@@ -52,8 +51,8 @@ def import_reference():
     return pcc_utils, op, image_utils, graphics_utils
 
 
-def main():
-    pcc_utils, op, image_utils, graphics_utils = import_reference()
+def main(ref):
+    pcc_utils, op, image_utils, graphics_utils = import_reference(ref)
     rng = np.random.RandomState(20261001)
 
     # ---- calculate_morton_order: unique points, several shapes/dtypes/sign patterns
@@ -129,4 +128,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    main(sys.argv[1])

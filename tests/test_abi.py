@@ -40,7 +40,7 @@ def test_signatures_match_reference():
                    ("channels", 32), ("kernel_size", 5), ("is_data_pre_quantized", True)]
 
 
-def test_no_cpu_fallback():
+def test_no_cpu_fallback(tmp_path):
     """The product path must fail loudly without a GPU (this container has none)."""
     import numpy as np
     import torch
@@ -50,7 +50,7 @@ def test_no_cpu_fallback():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
     with pytest.raises(RuntimeError):
-        pcc_utils.compress_point_cloud(np.zeros((4, 3), np.int32), "synthetic", "/tmp/_x/y.bin")
+        pcc_utils.compress_point_cloud(np.zeros((4, 3), np.int32), "synthetic", str(tmp_path / "y.bin"))
     with pytest.raises(RuntimeError):
         pcc_utils.calculate_morton_order(torch.zeros((4, 3)))
 

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_prints_one_complete_json_line():
+def test_bench_prints_one_complete_json_line(tmp_path):
     import torch
 
     if not torch.cuda.is_available():
@@ -21,7 +21,7 @@ def test_bench_prints_one_complete_json_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--points", "100000", "--steps", "3", "--warmup", "1", "--cpu-sample", "20000",
-                        "--side-anchors", "20000"], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
+                        "--side-anchors", "20000", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]               # stdout carries the one JSON line only
@@ -52,3 +52,25 @@ def test_bench_prints_one_complete_json_line():
     sp = d["side_paths"]
     assert sp["torchac_shim"]["roundtrip"] and sp["torchac_shim"]["fan_out_roundtrip"] and sp["gaussian_coder"]["fused_bytes_equal_table_bytes"]
     assert sp["rd_loop"]["psnr_decoded_vs_encoder_side_dB"] > 40
+    # --dump-outputs: the last timed step's container and decoded points, exact (100 k points are far below the size limit)
+    import numpy as np
+
+    from gauspcc_amd import runtime
+    from gauspcc_amd.dist import scene_seed
+    from gauspcc_amd.synth import synthetic_cloud, synthetic_state_dict
+    from tests import gpu_helpers as gh
+
+    assert sorted(os.listdir(tmp_path / "out")) == ["scene0_container_bytes.npy", "scene0_decoded_points.npy"]
+    blob = np.load(tmp_path / "out" / "scene0_container_bytes.npy")
+    pts = np.load(tmp_path / "out" / "scene0_decoded_points.npy")
+    assert blob.dtype == np.float32 and len(blob) == d["container_bytes"]
+    assert pts.dtype == np.float64
+    # the dumped container is scene 0's: byte for byte an owned encode of the same cloud with the same weights
+    cloud = synthetic_cloud(100000, seed=scene_seed(1234, 0))
+    model = runtime.Model(synthetic_state_dict(32, 5), 32, 5, 0)
+    data = bytes(blob.astype(np.uint8))
+    assert np.array_equal(blob, np.frombuffer(data, np.uint8)) and data == gh.encode(model, cloud, 11)[0]
+    # ... and the dumped points are what decoding it returns, in the decoder's order; as a set they are the cloud
+    assert np.array_equal(gh.decode(model, data)[0].astype(np.float64), pts)
+    ref = cloud.astype(np.float64)
+    assert np.array_equal(pts[np.lexsort(pts.T[::-1])], ref[np.lexsort(ref.T[::-1])])

@@ -19,9 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(args, timeout):
-    e = dict(os.environ)
-    e.setdefault("GPU_MAX_HW_QUEUES", "8")
-    return subprocess.run([sys.executable] + args, cwd=ROOT, env=e, capture_output=True, text=True, timeout=timeout)
+    return subprocess.run([sys.executable] + args, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
 
 
 def test_two_scenes_in_flight_are_bit_identical_to_solo_runs():

@@ -1,7 +1,7 @@
 """How many bytes do the chunk tables of a version-3 container take, and what would delta coding save? (CPU, oracle)"""
-import sys, time, struct
+import os, sys, time, struct
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from gauspcc_amd.synth import synthetic_cloud, synthetic_state_dict
 from gauspcc_amd.model import tensor_table
 from oracle import oracle as orc

@@ -1,16 +1,19 @@
 #!/bin/bash
 # Run the PMC passes of bench.py (one rocprofv3 run per counter group; --pmc is never combined
 # with tracing).  Usage: tools/pmc_passes.sh OUTDIR [bench args...]
-set -u
+# (every GPU pass under its own time limit; the script stops at the first pass that fails)
+set -euo pipefail
 OUT=$1; shift
-cd /tmp && export TMPDIR=/tmp
-cd "$GRAFT_REPO_ROOT"
+cd "$(dirname "$0")/.."
+mkdir -p "$OUT"
 i=0
 while read -r grp; do
   [ -z "$grp" ] && continue
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $grp --output-format csv -d "$OUT/p$i" -o pmc -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --side-anchors 0 "$@" > "$OUT/p$i.log" 2>&1
-  echo "pass $i [$grp] exit $?"
+  rc=0
+  timeout -k 10 600 rocprofv3 --pmc $grp --output-format csv -d "$OUT/p$i" -o pmc -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --side-anchors 0 "$@" > "$OUT/p$i.log" 2>&1 || rc=$?
+  echo "pass $i [$grp] exit $rc"
+  [ $rc -eq 0 ] || exit $rc
 done <<'GROUPS'
 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM
 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_MFMA SQ_INST_LEVEL_VMEM SQ_ACTIVE_INST_LDS SQ_INSTS_VALU
