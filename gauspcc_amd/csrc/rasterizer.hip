@@ -1,8 +1,9 @@
-// rasterizer.hip -- forward pass of the tile-binned Gaussian splat rasteriser + visible_filter
+// rasterizer.hip -- the tile-binned Gaussian splat rasteriser: forward, visible_filter, and the training path (forward + backward)
 // (diff-gaussian-rasterization, Scaffold-GS fork; the zip is missing from the reference tree, see
 // SURVEY.md App. E; call contract: HAC/gaussian_renderer/__init__.py:199-225, 268-303 and
 // TC-GS/SIBR_viewers/src/projects/gaussianviewer/renderer/GaussianView.cpp:535-553, 660-688).
-// Forward only: RD evaluation (render -> PSNR) never needs the backward.
+// The inference forward (RD evaluation: render -> PSNR) is gsr_forward; training runs gsr_forward_train + gsr_backward (k_render<true>,
+// k_render_backward, k_preprocess_backward: below the forward's kernels).
 //
 // gfx950 mapping:
 //   k_preprocess     one lane per Gaussian, coalesced SoA outputs (HBM-bound); counts the tiles the splat can reach (tile_touches: exact tile culling)
@@ -304,6 +305,22 @@ __device__ __forceinline__ void blend_one(float power, float op, float r, float 
     C0 += r * w; C1 += g * w; C2 += b * w;
     T = upd ? tt : T;
 }
+// the same blend, plus the list position after the last Gaussian blended into the pixel (the training forward)
+__device__ __forceinline__ void blend_one_rec(float power, float op, float r, float g, float b, bool &done, float &T, float &C0, float &C1, float &C2,
+                                              uint32_t kend, uint32_t &e)
+{
+    const float e2 = __builtin_amdgcn_exp2f(power * 1.44269504088896341f);
+    const float alpha = fminf(0.99f, op * e2);
+    const bool ok = !done && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
+    const float tt = T * (1.0f - alpha);
+    const bool sat = ok && tt < 0.0001f;
+    done = done || sat;
+    const bool upd = ok && !sat;
+    const float w = upd ? alpha * T : 0.0f;
+    C0 += r * w; C1 += g * w; C2 += b * w;
+    T = upd ? tt : T;
+    e = upd ? kend : e;
+}
 
 // dispatch order of the tiles: longest list first (the lists of a frame differ by two orders of magnitude; a long tile that starts last is the
 // frame's tail).  The order is a schedule, not a result: lengths in steps of 64 entries, saturating at 16 k, make it ONE radix pass (20-bit keys: three).
@@ -316,9 +333,14 @@ __global__ __launch_bounds__(TB) void k_tile_order_keys(const uint2 *__restrict_
     idx[t] = (uint32_t)t;
 }
 
+// TRAIN (the training forward, gsr_forward_train): point_list holds the pair's SLOT (its position in the duplicate pass's output, see
+// k_render_backward) and the Gaussian is gathered through slot_ids; every in-image pixel leaves its final T and the list position after the last
+// Gaussian it blended (0: none).  The blend is the same code: the image is bit-identical to the inference path's.
+template <bool TRAIN>
 __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ point_list, int W, int H, int gx,
-                                               const float2 *__restrict__ xy, const float *__restrict__ colors, const float4 *__restrict__ conic_op,
-                                               const float *__restrict__ bg, float *__restrict__ out)
+                                            const float2 *__restrict__ xy, const float *__restrict__ colors, const float4 *__restrict__ conic_op,
+                                            const float *__restrict__ bg, float *__restrict__ out, const uint32_t *__restrict__ slot_ids, float *__restrict__ final_T,
+                                            uint32_t *__restrict__ n_end)
 {
     __shared__ float4 s_a[RT];   // x, y, conic.x, conic.y
     __shared__ float4 s_b[RT];   // conic.z, opacity, r, g
@@ -332,11 +354,14 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
     bool done0 = !in0, done1 = !in1;
     float T0 = 1.0f, A0 = 0.f, A1 = 0.f, A2 = 0.f;
     float T1 = 1.0f, B0 = 0.f, B1 = 0.f, B2 = 0.f;
+    uint32_t e0 = 0, e1 = 0;
     for (uint32_t b0 = range.x; b0 < range.y; b0 += RT) {
         if (__syncthreads_count(done0 && done1) == RT) break;
         const uint32_t k = b0 + threadIdx.x;
         if (k < range.y) {
-            const uint32_t id = point_list[k];
+            uint32_t id;
+            if constexpr (TRAIN) id = slot_ids[point_list[k]];
+            else id = point_list[k];
             const float2 p = xy[id];
             const float4 co = conic_op[id];
             s_a[threadIdx.x] = make_float4(p.x, p.y, co.x, co.y);
@@ -364,12 +389,22 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
             // a Gaussian whose footprint misses all 128 pixels of the wave (most of a tile's list at the corners of the 3-sigma boxes, and
             // every Gaussian that only touches the tile's other half) costs the twelve instructions above and no exponential
             if (__builtin_amdgcn_ballot_w64((!done0 && !(pa0 < cb.y) && !(pa0 > 0.0f)) || (!done1 && !(pa1 < cb.y) && !(pa1 > 0.0f))) != 0ull) {   // (a NaN power passes, as in the reference's `if (power > 0) continue`)
-                blend_one(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2);
-                blend_one(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2);
+                if constexpr (TRAIN) {
+                    blend_one_rec(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2, b0 + (uint32_t)j + 1u, e0);
+                    blend_one_rec(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2, b0 + (uint32_t)j + 1u, e1);
+                } else {
+                    blend_one(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2);
+                    blend_one(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2);
+                }
             }
             if (__builtin_amdgcn_ballot_w64((!done0 && !(pb0 < cb2.y) && !(pb0 > 0.0f)) || (!done1 && !(pb1 < cb2.y) && !(pb1 > 0.0f))) != 0ull) {
-                blend_one(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2);
-                blend_one(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2);
+                if constexpr (TRAIN) {
+                    blend_one_rec(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2, b0 + (uint32_t)j + 2u, e0);
+                    blend_one_rec(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2, b0 + (uint32_t)j + 2u, e1);
+                } else {
+                    blend_one(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2);
+                    blend_one(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2);
+                }
             }
         }
     }
@@ -378,10 +413,299 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
     if (in0) {
         const size_t pix = (size_t)py0 * W + pxi;
         out[pix] = A0 + T0 * bg0; out[plane + pix] = A1 + T0 * bg1; out[2 * plane + pix] = A2 + T0 * bg2;
+        if constexpr (TRAIN) { final_T[pix] = T0; n_end[pix] = e0; }
     }
     if (in1) {
         const size_t pix = (size_t)py1 * W + pxi;
         out[pix] = B0 + T1 * bg0; out[plane + pix] = B1 + T1 * bg1; out[2 * plane + pix] = B2 + T1 * bg2;
+        if constexpr (TRAIN) { final_T[pix] = T1; n_end[pix] = e1; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Backward (training).  The training forward (gsr_forward_train) sorts each pair's SLOT -- its position in k_duplicate_sorted's output, where
+// Gaussian perm[s]'s pairs fill offs[s] .. offs[s+1]-1 -- instead of the Gaussian id, so every entry of a tile's list knows its slot.
+// k_render_backward writes one record of NREC floats per pair at that slot; k_preprocess_backward sums each Gaussian's contiguous records in slot
+// order and chains the sum through the forward's projection.  Every sum has a fixed order: no float atomics, and the gradients are bitwise
+// reproducible run to run.
+constexpr int NREC = 9;   // per pair: dL/d(r, g, b, opacity, conic.x, conic.y, conic.z, pixel x, pixel y), summed over the tile's pixels
+
+__global__ __launch_bounds__(TB) void k_iota(uint32_t n, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i < n) out[i] = i;
+}
+
+// Sum over the 64 lanes of a wave in a fixed order, complete in lane 63: quad swaps, half-row and row mirrors (every lane of a row then holds
+// the row's sum -- IEEE addition commutes, so the partners agree bit for bit), then the two row broadcasts.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
+}
+template <int CTRL, int ROW_MASK, int N>
+__device__ __forceinline__ void dpp_add_all(float *v)
+{
+#pragma unroll
+    for (int c = 0; c < N; ++c) v[c] = dpp_add<CTRL, ROW_MASK>(v[c]);
+}
+// step-major over the N values: a DPP read of a register written one instruction earlier costs wait states (s_nop), N independent sums hide them
+template <int N>
+__device__ __forceinline__ void wave_sum_to_63(float *v)
+{
+    dpp_add_all<0xB1, 0xF, N>(v);     // quad_perm [1, 0, 3, 2]
+    dpp_add_all<0x4E, 0xF, N>(v);     // quad_perm [2, 3, 0, 1]
+    dpp_add_all<0x141, 0xF, N>(v);    // row_half_mirror
+    dpp_add_all<0x140, 0xF, N>(v);    // row_mirror
+    dpp_add_all<0x142, 0xA, N>(v);    // row_bcast15 into rows 1 and 3
+    dpp_add_all<0x143, 0xC, N>(v);    // row_bcast31 into rows 2 and 3
+}
+
+// One (pixel, Gaussian) step of the walk back to front.  T enters as the transmittance after the Gaussian and leaves as the one in front of it;
+// S is the colour blended behind it, normalised by the transmittance behind it.  tb = T_final * <dL/dpixel, bg>.  The decision is the forward's:
+// `cand` holds k < n_end and the power test, alpha the forward's expressions; the saturation test needs no repeat (a pair before the pixel's last
+// blended one was not saturated).  The gradient passes through min(0.99, .) as if it were not there.
+__device__ __forceinline__ bool grad_one(bool cand, float power, float dx, float dy, float A, float B, float C, float op, float r, float g, float b,
+                                         float gr, float gg, float gb, float tb, float &T, float &S0, float &S1, float &S2, float *v)
+{
+    const float G = __builtin_amdgcn_exp2f(power * 1.44269504088896341f);
+    const float alpha = fminf(0.99f, op * G);
+    const bool bl = cand && !(alpha < 1.0f / 255.0f);
+    const float inv = __builtin_amdgcn_rcpf(1.0f - alpha);
+    const float Ti = T * inv;
+    const float w = alpha * Ti;
+    const float dLda = Ti * (gr * (r - S0) + gg * (g - S1) + gb * (b - S2)) - tb * inv;
+    const float dLdp = op * G * dLda;            // dalpha / dpower = op G
+    v[0] += bl ? gr * w : 0.0f;
+    v[1] += bl ? gg * w : 0.0f;
+    v[2] += bl ? gb * w : 0.0f;
+    v[3] += bl ? G * dLda : 0.0f;
+    v[4] += bl ? -0.5f * dx * dx * dLdp : 0.0f;
+    v[5] += bl ? -dx * dy * dLdp : 0.0f;
+    v[6] += bl ? -0.5f * dy * dy * dLdp : 0.0f;
+    v[7] += bl ? -(A * dx + B * dy) * dLdp : 0.0f;
+    v[8] += bl ? -(C * dy + B * dx) * dLdp : 0.0f;
+    S0 = bl ? alpha * r + (1.0f - alpha) * S0 : S0;
+    S1 = bl ? alpha * g + (1.0f - alpha) * S1 : S1;
+    S2 = bl ? alpha * b + (1.0f - alpha) * S2 : S2;
+    T = bl ? Ti : T;
+    return bl;
+}
+
+// One 16 x 16 tile per workgroup of RT lanes, two pixels per lane, as k_render; the list is walked back to front in LDS-staged batches of RT from
+// the tile's largest n_end.  Per Gaussian a wave sums its 128 pixels' NREC values (wave_sum_to_63) only when one of its lanes blended it -- the
+// forward's ballot skip --, the two waves' sums meet in LDS, and the batch's records go out with plain stores at their slots (wave 0's sum + wave
+// 1's, in that order).  Entries behind the largest n_end are never reached: their records are written as zeros.
+__global__ __launch_bounds__(RT) void k_render_backward(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ slot_list,
+                                                        const uint32_t *__restrict__ slot_ids, int W, int H, int gx, const float2 *__restrict__ xy,
+                                                        const float *__restrict__ colors, const float4 *__restrict__ conic_op, const float *__restrict__ bg,
+                                                        const float *__restrict__ final_T, const uint32_t *__restrict__ n_end, const float *__restrict__ dout,
+                                                        float *__restrict__ rec)
+{
+    __shared__ float4 s_a[RT];   // x, y, conic.x, conic.y
+    __shared__ float4 s_b[RT];   // conic.z, opacity, r, g
+    __shared__ float2 s_c[RT];   // b, skip threshold (k_render's)
+    __shared__ uint32_t s_slot[RT];
+    __shared__ float s_part[2][NREC][RT];
+    __shared__ uint32_t s_top;
+    const int tile = (int)tile_order[blockIdx.x];
+    const int tbx = tile % gx, tby = tile / gx;
+    const int pxi = tbx * BX + (threadIdx.x & 15), py0 = tby * BY + (threadIdx.x >> 4), py1 = py0 + 8;
+    const bool in0 = pxi < W && py0 < H, in1 = pxi < W && py1 < H;
+    const float pxf = (float)pxi, pyf0 = (float)py0, pyf1 = (float)py1;
+    const uint2 range = ranges[tile];
+    const size_t plane = (size_t)W * H;
+    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+    float T0 = 1.0f, g00 = 0.f, g01 = 0.f, g02 = 0.f, T1 = 1.0f, g10 = 0.f, g11 = 0.f, g12 = 0.f;
+    uint32_t e0 = 0, e1 = 0;
+    if (in0) {
+        const size_t pix = (size_t)py0 * W + pxi;
+        T0 = final_T[pix]; e0 = n_end[pix]; g00 = dout[pix]; g01 = dout[plane + pix]; g02 = dout[2 * plane + pix];
+    }
+    if (in1) {
+        const size_t pix = (size_t)py1 * W + pxi;
+        T1 = final_T[pix]; e1 = n_end[pix]; g10 = dout[pix]; g11 = dout[plane + pix]; g12 = dout[2 * plane + pix];
+    }
+    const float tb0 = T0 * (g00 * bg0 + g01 * bg1 + g02 * bg2), tb1 = T1 * (g10 * bg0 + g11 * bg1 + g12 * bg2);
+    if (threadIdx.x == 0) s_top = 0u;
+    __syncthreads();
+    if (max(e0, e1) > 0u) atomicMax(&s_top, max(e0, e1));
+    __syncthreads();
+    const uint32_t top = max(s_top, range.x);
+    for (uint32_t k = top + threadIdx.x; k < range.y; k += RT) {
+        float *__restrict__ r = rec + (size_t)slot_list[k] * NREC;
+        for (int c = 0; c < NREC; ++c) r[c] = 0.0f;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float S00 = 0.f, S01 = 0.f, S02 = 0.f, S10 = 0.f, S11 = 0.f, S12 = 0.f;
+    for (uint32_t hi = top; hi > range.x;) {
+        const uint32_t lo = hi - range.x > (uint32_t)RT ? hi - RT : range.x;
+        const int cnt = (int)(hi - lo);
+        __syncthreads();   // the previous batch's LDS is read out
+        const int t = threadIdx.x;
+        if (t < cnt) {
+            const uint32_t slot = slot_list[lo + t];
+            const uint32_t id = slot_ids[slot];
+            const float2 p = xy[id];
+            const float4 co = conic_op[id];
+            s_slot[t] = slot;
+            s_a[t] = make_float4(p.x, p.y, co.x, co.y);
+            s_b[t] = make_float4(co.z, co.w, colors[3 * id], colors[3 * id + 1]);
+            s_c[t] = make_float2(colors[3 * id + 2], co.w > 0.0f ? -__logf(255.0f * co.w) - 1e-3f : (co.w != co.w ? -__builtin_inff() : __builtin_inff()));
+        }
+        for (int c = 0; c < NREC; ++c) { s_part[0][c][t] = 0.0f; s_part[1][c][t] = 0.0f; }
+        __syncthreads();
+        for (int j = cnt - 1; j >= 0; --j) {
+            const uint32_t k = lo + (uint32_t)j;
+            const float4 a = s_a[j], bq = s_b[j];
+            const float2 cb = s_c[j];
+            // the forward's expressions, operation for operation (-ffp-contract=off): the same power, so the same decisions
+            const float dxa = a.x - pxf, dya0 = a.y - pyf0, dya1 = a.y - pyf1;
+            const float pa0 = -0.5f * (a.z * dxa * dxa + bq.x * dya0 * dya0) - a.w * dxa * dya0;
+            const float pa1 = -0.5f * (a.z * dxa * dxa + bq.x * dya1 * dya1) - a.w * dxa * dya1;
+            const bool c0 = k < e0 && !(pa0 < cb.y) && !(pa0 > 0.0f);
+            const bool c1 = k < e1 && !(pa1 < cb.y) && !(pa1 > 0.0f);
+            if (__builtin_amdgcn_ballot_w64(c0 || c1) == 0ull) continue;
+            float v[NREC];
+            for (int c = 0; c < NREC; ++c) v[c] = 0.0f;
+            const bool b0 = grad_one(c0, pa0, dxa, dya0, a.z, a.w, bq.x, bq.y, bq.z, bq.w, cb.x, g00, g01, g02, tb0, T0, S00, S01, S02, v);
+            const bool b1 = grad_one(c1, pa1, dxa, dya1, a.z, a.w, bq.x, bq.y, bq.z, bq.w, cb.x, g10, g11, g12, tb1, T1, S10, S11, S12, v);
+            if (__builtin_amdgcn_ballot_w64(b0 || b1) == 0ull) continue;
+            wave_sum_to_63<NREC>(v);
+            if (lane == 63)
+                for (int c = 0; c < NREC; ++c) s_part[wave][c][j] = v[c];
+        }
+        __syncthreads();
+        if (t < cnt) {
+            float *__restrict__ r = rec + (size_t)s_slot[t] * NREC;
+            for (int c = 0; c < NREC; ++c) r[c] = s_part[0][c][t] + s_part[1][c][t];
+        }
+        hi = lo;
+    }
+}
+
+// One lane per Gaussian in depth order (position s of the first-level sort: its records are the contiguous slots offs[s] .. offs[s+1]-1), summed
+// in slot order; then the chain back through k_preprocess's math: pixel centre -> NDC -> means3D; conic -> 2-D covariance -> J and the view
+// rotation -> 3-D covariance -> scales (with scale_modifier) and the raw quaternion, or cov3D_precomp.  A coordinate clamped at +-1.3 tan(fov)
+// enters J as a constant; Gaussians with radius 0 get exactly zero.
+__global__ __launch_bounds__(TB) void k_preprocess_backward(int P, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ offs, const float *__restrict__ rec,
+                                                            const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ rots,
+                                                            const float *__restrict__ cov3d_pre, Cam cam, const int *__restrict__ radii,
+                                                            float *__restrict__ g_means3D, float *__restrict__ g_means2D, float *__restrict__ g_colors,
+                                                            float *__restrict__ g_opac, float *__restrict__ g_scales, float *__restrict__ g_rots,
+                                                            float *__restrict__ g_cov3D)
+{
+    const int s = blockIdx.x * TB + threadIdx.x;
+    if (s >= P) return;
+    const uint32_t i = perm[s];
+    float acc[NREC];
+    for (int c = 0; c < NREC; ++c) acc[c] = 0.0f;
+    float gm0 = 0.f, gm1 = 0.f, gm2 = 0.f, gnx = 0.f, gny = 0.f;
+    float gc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
+    if (radii[i] > 0) {
+        for (uint32_t q = offs[s], qe = offs[s + 1]; q < qe; ++q)
+            for (int c = 0; c < NREC; ++c) acc[c] += rec[(size_t)q * NREC + c];
+        // k_preprocess's forward values
+        const float px = means[3 * i], py = means[3 * i + 1], pz = means[3 * i + 2];
+        const float *__restrict__ V = cam.view, *__restrict__ M = cam.proj;
+        const float tx0 = V[0] * px + V[4] * py + V[8] * pz + V[12];
+        const float ty0 = V[1] * px + V[5] * py + V[9] * pz + V[13];
+        const float tz = V[2] * px + V[6] * py + V[10] * pz + V[14];
+        const float hx = M[0] * px + M[4] * py + M[8] * pz + M[12];
+        const float hy = M[1] * px + M[5] * py + M[9] * pz + M[13];
+        const float hw = M[3] * px + M[7] * py + M[11] * pz + M[15];
+        const float pw = 1.0f / (hw + 0.0000001f);
+        float c[6], R[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, sc[3] = {0.f, 0.f, 0.f};
+        float qr = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
+        if (cov3d_pre) {
+            for (int k = 0; k < 6; ++k) c[k] = cov3d_pre[6 * i + k];
+        } else {
+            sc[0] = cam.scale_modifier * scales[3 * i]; sc[1] = cam.scale_modifier * scales[3 * i + 1]; sc[2] = cam.scale_modifier * scales[3 * i + 2];
+            qr = rots[4 * i]; qx = rots[4 * i + 1]; qy = rots[4 * i + 2]; qz = rots[4 * i + 3];
+            R[0][0] = 1.f - 2.f * (qy * qy + qz * qz); R[0][1] = 2.f * (qx * qy - qr * qz); R[0][2] = 2.f * (qx * qz + qr * qy);
+            R[1][0] = 2.f * (qx * qy + qr * qz); R[1][1] = 1.f - 2.f * (qx * qx + qz * qz); R[1][2] = 2.f * (qy * qz - qr * qx);
+            R[2][0] = 2.f * (qx * qz - qr * qy); R[2][1] = 2.f * (qy * qz + qr * qx); R[2][2] = 1.f - 2.f * (qx * qx + qy * qy);
+            const float ax = sc[0] * sc[0], ay = sc[1] * sc[1], az = sc[2] * sc[2];
+            c[0] = ax * R[0][0] * R[0][0] + ay * R[0][1] * R[0][1] + az * R[0][2] * R[0][2];
+            c[1] = ax * R[0][0] * R[1][0] + ay * R[0][1] * R[1][1] + az * R[0][2] * R[1][2];
+            c[2] = ax * R[0][0] * R[2][0] + ay * R[0][1] * R[2][1] + az * R[0][2] * R[2][2];
+            c[3] = ax * R[1][0] * R[1][0] + ay * R[1][1] * R[1][1] + az * R[1][2] * R[1][2];
+            c[4] = ax * R[1][0] * R[2][0] + ay * R[1][1] * R[2][1] + az * R[1][2] * R[2][2];
+            c[5] = ax * R[2][0] * R[2][0] + ay * R[2][1] * R[2][1] + az * R[2][2] * R[2][2];
+        }
+        const float limx = 1.3f * cam.tan_fovx, limy = 1.3f * cam.tan_fovy;
+        const float txtz = tx0 / tz, tytz = ty0 / tz;
+        const float tx = fminf(limx, fmaxf(-limx, txtz)) * tz;
+        const float ty = fminf(limy, fmaxf(-limy, tytz)) * tz;
+        const bool clx = txtz < -limx || txtz > limx, cly = tytz < -limy || tytz > limy;
+        const float fx = cam.focal_x, fy = cam.focal_y;
+        const float j00 = fx / tz, j02 = -(fx * tx) / (tz * tz);
+        const float j11 = fy / tz, j12 = -(fy * ty) / (tz * tz);
+        const float a0x = j00 * V[0] + j02 * V[2], a0y = j00 * V[4] + j02 * V[6], a0z = j00 * V[8] + j02 * V[10];
+        const float a1x = j11 * V[1] + j12 * V[2], a1y = j11 * V[5] + j12 * V[6], a1z = j11 * V[9] + j12 * V[10];
+        const float s0x = c[0] * a0x + c[1] * a0y + c[2] * a0z, s0y = c[1] * a0x + c[3] * a0y + c[4] * a0z, s0z = c[2] * a0x + c[4] * a0y + c[5] * a0z;
+        const float s1x = c[0] * a1x + c[1] * a1y + c[2] * a1z, s1y = c[1] * a1x + c[3] * a1y + c[4] * a1z, s1z = c[2] * a1x + c[4] * a1y + c[5] * a1z;
+        const float cxx = a0x * s0x + a0y * s0y + a0z * s0z + 0.3f;
+        const float cxy = a0x * s1x + a0y * s1y + a0z * s1z;
+        const float cyy = a1x * s1x + a1y * s1y + a1z * s1z + 0.3f;
+        const float det = cxx * cyy - cxy * cxy;
+        const float id2 = 1.0f / (det * det);
+        // pixel centre -> NDC (ix = ((ndc + 1) W - 1) / 2) -> clip -> means3D
+        gnx = acc[7] * (0.5f * (float)cam.W); gny = acc[8] * (0.5f * (float)cam.H);
+        const float ghx = gnx * pw, ghy = gny * pw, ghw = -(gnx * hx + gny * hy) * pw * pw;
+        gm0 = ghx * M[0] + ghy * M[1] + ghw * M[3];
+        gm1 = ghx * M[4] + ghy * M[5] + ghw * M[7];
+        gm2 = ghx * M[8] + ghy * M[9] + ghw * M[11];
+        // conic (cyy, -cxy, cxx) / det -> 2-D covariance
+        const float gA = acc[4], gB = acc[5], gC = acc[6];
+        const float ga = (-cyy * cyy * gA + cxy * cyy * gB - cxy * cxy * gC) * id2;
+        const float gb = (2.0f * cxy * cyy * gA - (cxx * cyy + cxy * cxy) * gB + 2.0f * cxx * cxy * gC) * id2;
+        const float gd = (-cxy * cxy * gA + cxx * cxy * gB - cxx * cxx * gC) * id2;
+        // cxx = a0' S a0 + 0.3, cxy = a0' S a1, cyy = a1' S a1 + 0.3 -> the rows a0, a1 of J W and the 3-D covariance (off-diagonals: both uses)
+        const float ga0x = 2.0f * ga * s0x + gb * s1x, ga0y = 2.0f * ga * s0y + gb * s1y, ga0z = 2.0f * ga * s0z + gb * s1z;
+        const float ga1x = gb * s0x + 2.0f * gd * s1x, ga1y = gb * s0y + 2.0f * gd * s1y, ga1z = gb * s0z + 2.0f * gd * s1z;
+        gc[0] = ga * a0x * a0x + gb * a0x * a1x + gd * a1x * a1x;
+        gc[1] = 2.0f * ga * a0x * a0y + gb * (a0x * a1y + a0y * a1x) + 2.0f * gd * a1x * a1y;
+        gc[2] = 2.0f * ga * a0x * a0z + gb * (a0x * a1z + a0z * a1x) + 2.0f * gd * a1x * a1z;
+        gc[3] = ga * a0y * a0y + gb * a0y * a1y + gd * a1y * a1y;
+        gc[4] = 2.0f * ga * a0y * a0z + gb * (a0y * a1z + a0z * a1y) + 2.0f * gd * a1y * a1z;
+        gc[5] = ga * a0z * a0z + gb * a0z * a1z + gd * a1z * a1z;
+        // J -> view-space position (a clamped coordinate is a constant in J)
+        const float gj00 = ga0x * V[0] + ga0y * V[4] + ga0z * V[8], gj02 = ga0x * V[2] + ga0y * V[6] + ga0z * V[10];
+        const float gj11 = ga1x * V[1] + ga1y * V[5] + ga1z * V[9], gj12 = ga1x * V[2] + ga1y * V[6] + ga1z * V[10];
+        const float tz2 = tz * tz, tz3 = tz2 * tz;
+        const float gtz = -fx / tz2 * gj00 + 2.0f * fx * tx / tz3 * gj02 - fy / tz2 * gj11 + 2.0f * fy * ty / tz3 * gj12;
+        const float gtx = clx ? 0.0f : -fx / tz2 * gj02, gty = cly ? 0.0f : -fy / tz2 * gj12;
+        gm0 += gtx * V[0] + gty * V[1] + gtz * V[2];
+        gm1 += gtx * V[4] + gty * V[5] + gtz * V[6];
+        gm2 += gtx * V[8] + gty * V[9] + gtz * V[10];
+        if (!cov3d_pre) {
+            // Sigma = R diag(s^2) R': dL/d(s_m^2) = (R' G R)_mm, dL/dR = 2 G R diag(s^2), G the symmetric gradient of Sigma
+            const float G[3][3] = {{gc[0], 0.5f * gc[1], 0.5f * gc[2]}, {0.5f * gc[1], gc[3], 0.5f * gc[4]}, {0.5f * gc[2], 0.5f * gc[4], gc[5]}};
+            float GR[3][3], gR[3][3];
+            for (int r = 0; r < 3; ++r)
+                for (int m = 0; m < 3; ++m) GR[r][m] = G[r][0] * R[0][m] + G[r][1] * R[1][m] + G[r][2] * R[2][m];
+            for (int m = 0; m < 3; ++m) {
+                const float gam = R[0][m] * GR[0][m] + R[1][m] * GR[1][m] + R[2][m] * GR[2][m];
+                gs[m] = gam * 2.0f * sc[m] * cam.scale_modifier;
+                const float am = sc[m] * sc[m];
+                for (int r = 0; r < 3; ++r) gR[r][m] = 2.0f * am * GR[r][m];
+            }
+            gq[0] = 2.0f * (-qz * gR[0][1] + qy * gR[0][2] + qz * gR[1][0] - qx * gR[1][2] - qy * gR[2][0] + qx * gR[2][1]);
+            gq[1] = 2.0f * (qy * gR[0][1] + qz * gR[0][2] + qy * gR[1][0] - 2.0f * qx * gR[1][1] - qr * gR[1][2] + qz * gR[2][0] + qr * gR[2][1] - 2.0f * qx * gR[2][2]);
+            gq[2] = 2.0f * (-2.0f * qy * gR[0][0] + qx * gR[0][1] + qr * gR[0][2] + qx * gR[1][0] + qz * gR[1][2] - qr * gR[2][0] + qz * gR[2][1] - 2.0f * qy * gR[2][2]);
+            gq[3] = 2.0f * (-2.0f * qz * gR[0][0] - qr * gR[0][1] + qx * gR[0][2] + qr * gR[1][0] - 2.0f * qz * gR[1][1] + qy * gR[1][2] + qx * gR[2][0] + qy * gR[2][1]);
+        }
+    }
+    g_means3D[3 * i] = gm0; g_means3D[3 * i + 1] = gm1; g_means3D[3 * i + 2] = gm2;
+    g_means2D[3 * i] = gnx; g_means2D[3 * i + 1] = gny; g_means2D[3 * i + 2] = 0.0f;
+    g_colors[3 * i] = acc[0]; g_colors[3 * i + 1] = acc[1]; g_colors[3 * i + 2] = acc[2];
+    g_opac[i] = acc[3];
+    if (cov3d_pre) {
+        for (int k = 0; k < 6; ++k) g_cov3D[6 * i + k] = gc[k];
+    } else {
+        for (int k = 0; k < 3; ++k) g_scales[3 * i + k] = gs[k];
+        for (int k = 0; k < 4; ++k) g_rots[4 * i + k] = gq[k];
     }
 }
 
@@ -513,10 +837,165 @@ extern "C" int gsr_forward(gpcc_ctx *ctx, int P, const float *background, int W,
             GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, ntiles, 8));
             tile_order = v0;
         }
-        k_render<<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, vals_sorted, W, H, cam.gx, xy, colors_precomp, conic_op, background, out_color);
+        k_render<false><<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, vals_sorted, W, H, cam.gx, xy, colors_precomp, conic_op, background, out_color, nullptr, nullptr, nullptr);
         LAUNCH_CHECK();
         HIP_TRY(hipStreamSynchronize(st));
         return device_error_check(ctx);
     }
     return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
+}
+
+// The training forward: gsr_forward's two-level path, with the frame state the backward needs placed in memory the caller hands out through
+// `alloc` (so that it outlives this call and any other call on the context); only the scratch of the sorts stays in ctx->arena.
+extern "C" int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                                 const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                                 const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
+                                 int *radii, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state, int64_t *num_rendered_out, void *stream)
+{
+    (void)prefiltered;
+    if (!ctx || !background || !viewmatrix || !projmatrix || !out_color || !alloc || !state) return fail(GPCC_ERR_ARG, "null argument");
+    if (P > 0 && (!means3D || !colors_precomp || !opacities || !radii)) return fail(GPCC_ERR_ARG, "null argument");
+    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) return fail(GPCC_ERR_ARG, "provide scales + rotations or cov3D_precomp");
+    if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
+    for (int k = 0; k < GSR_STATE_WORDS; ++k) state[k] = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    Cam cam;
+    GP_TRY(make_cam(&cam, W, H, viewmatrix, projmatrix, tan_fovx, tan_fovy, scale_modifier));
+    const int ntiles = cam.gx * cam.gy;
+    const size_t P1 = (size_t)std::max(P, 1), npix = (size_t)W * H;
+    // frame state sized by P, the tiles and the pixels: one block from the caller
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_xy = 0, o_co = o_xy + al(8 * P1), o_pa = o_co + al(16 * P1), o_pb = o_pa + al(4 * P1), o_offs = o_pb + al(4 * P1);
+    const size_t o_rng = o_offs + al(4 * (P1 + 1)), o_ta = o_rng + al(8 * (size_t)ntiles), o_tb = o_ta + al(4 * (size_t)ntiles);
+    const size_t o_T = o_tb + al(4 * (size_t)ntiles), o_end = o_T + al(4 * npix), bytes_a = o_end + al(4 * npix);
+    char *blk = static_cast<char *>(alloc(alloc_user, bytes_a));
+    if (!blk) return fail(GPCC_ERR_NOMEM, "rasteriser frame state (%zu bytes)", bytes_a);
+    float2 *xy = reinterpret_cast<float2 *>(blk + o_xy);
+    float4 *conic_op = reinterpret_cast<float4 *>(blk + o_co);
+    uint32_t *perm_a = reinterpret_cast<uint32_t *>(blk + o_pa), *perm_b = reinterpret_cast<uint32_t *>(blk + o_pb), *offs = reinterpret_cast<uint32_t *>(blk + o_offs);
+    uint2 *ranges = reinterpret_cast<uint2 *>(blk + o_rng);
+    uint32_t *ord_a = reinterpret_cast<uint32_t *>(blk + o_ta), *ord_b = reinterpret_cast<uint32_t *>(blk + o_tb);
+    float *final_T = reinterpret_cast<float *>(blk + o_T);
+    uint32_t *n_end = reinterpret_cast<uint32_t *>(blk + o_end);
+    char *blk_l = nullptr;           // sized by the pair count: slot -> Gaussian, and the sorted slots (two buffers: the sort ping-pongs)
+    size_t want = P1 * 112 + (size_t)ntiles * 32 + ((size_t)8 << 20);
+    uint32_t L = 0;
+    GP_TRY(ctx->hstage.reserve(64));
+    volatile uint32_t *hL = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
+    volatile unsigned long long *hrect = reinterpret_cast<volatile unsigned long long *>(ctx->hstage.p + 8);
+    static const int cull = dev_env_int("GAUSPCC_RASTER_CULL", 1) != 0 ? 1 : 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        GP_TRY(ctx->arena.reserve(want + (size_t)L * 40));
+        ctx->arena.reset();
+        TAKE(depth, float, P1); TAKE(touched, uint32_t, P1 + 1);
+        TAKE(rect_total, unsigned long long, RECT_SLOTS + 1);
+        TAKE(dka, uint64_t, P1); TAKE(dkb, uint64_t, P1); TAKE(recs, uint4, P1);
+        HIP_TRY(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)ntiles, st));
+        HIP_TRY(hipMemsetAsync(rect_total, 0, 8 * (RECT_SLOTS + 1), st));
+        unsigned long long rect_host = 0;
+        const uint32_t *perm = perm_a;
+        if (P > 0) {
+            k_preprocess<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, means3D, scales, rotations, cov3D_precomp, opacities, cam, radii, xy, depth, conic_op, touched, cull,
+                                                               cull ? rect_total : nullptr, dka, perm_a, recs);
+            LAUNCH_CHECK();
+            if (cull) { k_sum_slots<<<1, RECT_SLOTS, 0, st>>>(rect_total, rect_total + RECT_SLOTS); LAUNCH_CHECK(); }
+            uint64_t *k0 = dka, *k1 = dkb; uint32_t *v0 = perm_a, *v1 = perm_b;
+            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, P, 32));
+            k_sorted_counts<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, k0, offs);
+            LAUNCH_CHECK();
+            GP_TRY(exclusive_scan_u32(ctx, st, offs, offs, P, offs + P));
+            HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(hL), offs + P, 4, hipMemcpyDeviceToHost, st));
+            if (cull) HIP_TRY(hipMemcpyAsync(const_cast<unsigned long long *>(hrect), rect_total + RECT_SLOTS, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            L = *hL;
+            if (cull) rect_host = *hrect;
+            perm = v0;
+        }
+        if (num_rendered_out) *num_rendered_out = cull ? (int64_t)rect_host : (int64_t)L;
+        const size_t o_sa = al(4 * (size_t)L), o_sb = o_sa + al(4 * (size_t)L), bytes_l = o_sb + al(4 * (size_t)L);
+        uint32_t *slot_ids = nullptr, *slots = nullptr;
+        if (L > 0) {
+            if (!blk_l) {
+                blk_l = static_cast<char *>(alloc(alloc_user, bytes_l));
+                if (!blk_l) return fail(GPCC_ERR_NOMEM, "rasteriser pair state (%zu bytes)", bytes_l);
+            }
+            slot_ids = reinterpret_cast<uint32_t *>(blk_l);
+            uint32_t *sa = reinterpret_cast<uint32_t *>(blk_l + o_sa), *sb = reinterpret_cast<uint32_t *>(blk_l + o_sb);
+            uint64_t *ka = ctx->arena.take<uint64_t>(L), *kb = ctx->arena.take<uint64_t>(L);
+            if (!ka || !kb || ctx->arena.cap - ctx->arena.off < (size_t)L * 2 + ((size_t)2 << 20)) { want += (size_t)L * 4; continue; }  // grow and redo
+            int tbits = 1;
+            while ((1 << tbits) < ntiles) ++tbits;
+            k_duplicate_sorted<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, perm, recs, xy, offs, radii, cam.gx, cam.gy, ka, slot_ids, conic_op, cull);
+            LAUNCH_CHECK();
+            k_iota<<<(unsigned)cdiv(L, TB), TB, 0, st>>>(L, sa);
+            LAUNCH_CHECK();
+            uint64_t *k0 = ka, *k1 = kb; uint32_t *v0 = sa, *v1 = sb;
+            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, L, tbits));   // stable on the same keys: gsr_forward's permutation, carrying slots
+            k_tile_ranges<<<(unsigned)cdiv(L, TB), TB, 0, st>>>((int)L, k0, 0, ranges);
+            LAUNCH_CHECK();
+            slots = v0;
+        }
+        uint32_t *tile_order = nullptr;
+        {
+            uint64_t *oka = ctx->arena.take<uint64_t>(ntiles), *okb = ctx->arena.take<uint64_t>(ntiles);
+            if (!oka || !okb) { want += (size_t)ntiles * 32; continue; }
+            k_tile_order_keys<<<(unsigned)cdiv(ntiles, TB), TB, 0, st>>>(ranges, ntiles, oka, ord_a);
+            LAUNCH_CHECK();
+            uint64_t *k0 = oka, *k1 = okb; uint32_t *v0 = ord_a, *v1 = ord_b;
+            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, ntiles, 8));
+            tile_order = v0;
+        }
+        k_render<true><<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, slots, W, H, cam.gx, xy, colors_precomp, conic_op, background, out_color,
+                                                        slot_ids, final_T, n_end);
+        LAUNCH_CHECK();
+        HIP_TRY(hipStreamSynchronize(st));
+        state[0] = L; state[1] = (uint64_t)P; state[2] = (uint64_t)W; state[3] = (uint64_t)H;
+        state[4] = (uint64_t)(uintptr_t)xy; state[5] = (uint64_t)(uintptr_t)conic_op; state[6] = (uint64_t)(uintptr_t)perm; state[7] = (uint64_t)(uintptr_t)offs;
+        state[8] = (uint64_t)(uintptr_t)ranges; state[9] = (uint64_t)(uintptr_t)tile_order; state[10] = (uint64_t)(uintptr_t)slots;
+        state[11] = (uint64_t)(uintptr_t)slot_ids; state[12] = (uint64_t)(uintptr_t)final_T; state[13] = (uint64_t)(uintptr_t)n_end;
+        return device_error_check(ctx);
+    }
+    return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
+}
+
+extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                            const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                            const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, const int *radii, const float *dL_dout,
+                            gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
+                            float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream)
+{
+    (void)opacities;
+    if (!ctx || !state || !background || !viewmatrix || !projmatrix || !dL_dout || !alloc) return fail(GPCC_ERR_ARG, "null argument");
+    if (state[1] != (uint64_t)P || state[2] != (uint64_t)W || state[3] != (uint64_t)H) return fail(GPCC_ERR_ARG, "frame state of another frame");
+    if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
+    if (P <= 0) return GPCC_OK;
+    if (!means3D || !colors_precomp || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities) return fail(GPCC_ERR_ARG, "null argument");
+    if (cov3D_precomp ? !dL_dcov3D : (!scales || !rotations || !dL_dscales || !dL_drotations)) return fail(GPCC_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    Cam cam;
+    GP_TRY(make_cam(&cam, W, H, viewmatrix, projmatrix, tan_fovx, tan_fovy, scale_modifier));
+    const int ntiles = cam.gx * cam.gy;
+    const uint64_t L = state[0];
+    const float2 *xy = reinterpret_cast<const float2 *>(state[4]);
+    const float4 *conic_op = reinterpret_cast<const float4 *>(state[5]);
+    const uint32_t *perm = reinterpret_cast<const uint32_t *>(state[6]), *offs = reinterpret_cast<const uint32_t *>(state[7]);
+    const uint2 *ranges = reinterpret_cast<const uint2 *>(state[8]);
+    const uint32_t *tile_order = reinterpret_cast<const uint32_t *>(state[9]), *slots = reinterpret_cast<const uint32_t *>(state[10]);
+    const uint32_t *slot_ids = reinterpret_cast<const uint32_t *>(state[11]);
+    const float *final_T = reinterpret_cast<const float *>(state[12]);
+    const uint32_t *n_end = reinterpret_cast<const uint32_t *>(state[13]);
+    float *rec = nullptr;
+    if (L > 0) {
+        rec = static_cast<float *>(alloc(alloc_user, (size_t)L * NREC * sizeof(float)));
+        if (!rec) return fail(GPCC_ERR_NOMEM, "rasteriser backward records (%llu pairs)", (unsigned long long)L);
+        k_render_backward<<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, slots, slot_ids, W, H, cam.gx, xy, colors_precomp, conic_op, background,
+                                                           final_T, n_end, dL_dout, rec);
+        LAUNCH_CHECK();
+    }
+    k_preprocess_backward<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, perm, offs, rec, means3D, scales, rotations, cov3D_precomp, cam, radii, dL_dmeans3D,
+                                                                dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D);
+    LAUNCH_CHECK();
+    return GPCC_OK;
 }

@@ -13,6 +13,7 @@
 #ifndef GAUSPCC_H
 #define GAUSPCC_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -405,7 +406,7 @@ GPCC_API int gsnn_generate(gpcc_ctx *ctx, int64_t n, const int32_t *rows, int fe
                            const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, float *xyz_out,
                            float *color_out, float *opacity_out, float *scale_out, float *rot_out, int64_t *count_out, void *stream);
 
-/* ================= Gaussian splat rasteriser, forward only (a20) =================
+/* ================= Gaussian splat rasteriser, forward (a20) =================
  * diff_gaussian_rasterization (Scaffold-GS fork; zip missing from the reference tree).  Mirrors the C++ API the
  * reference's viewer calls: CudaRasterizer::Rasterizer::visible_filter / ::forward,
  * TC-GS/SIBR_viewers/src/projects/gaussianviewer/renderer/GaussianView.cpp:535-553, 660-688; Python call
@@ -421,6 +422,37 @@ GPCC_API int gsr_forward(gpcc_ctx *ctx, int P, const float *background, int W, i
                          const float *opacities, const float *scales, float scale_modifier, const float *rotations,
                          const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
                          int prefiltered, float *out_color, int *radii, int64_t *num_rendered_out, void *stream);
+
+/* ================= Rasteriser backward (training) =================
+ * The training forward writes the image, radii and *num_rendered_out of gsr_forward (the image bit for bit) and keeps what the backward
+ * needs in device memory the caller hands out: alloc(alloc_user, bytes) returns a device pointer (256-byte aligned) that stays valid until the
+ * caller has run gsr_backward, or NULL (the call then fails with GPCC_ERR_NOMEM).  It is called twice per frame at most: once for the state
+ * sized by P, the tiles and the pixels (per Gaussian: pixel centre, conic and opacity, depth order, pair offsets; per tile: list range and
+ * dispatch order; per pixel: final transmittance and the list position after the last Gaussian blended into it), once, after the pair count L
+ * is known, for the sorted pair list (12 L bytes).  Nothing of the frame lives in ctx's workspace, so other calls on ctx may run between the
+ * forward and the backward.  state (host, GSR_STATE_WORDS words) receives the pair count, P, W, H and the device addresses of that state; it
+ * is opaque to the caller and is handed back to gsr_backward unchanged.  Always the two-level sort; colours precomputed. */
+#define GSR_STATE_WORDS 16
+typedef void *(*gsr_alloc_fn)(void *user, size_t bytes);
+GPCC_API int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                               const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                               const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
+                               int prefiltered, float *out_color, int *radii, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state,
+                               int64_t *num_rendered_out, void *stream);
+/* Gradients of a loss L given dL_dout = dL/d(out_color) (3, H, W) of the frame gsr_forward_train left in state; the forward's inputs and radii
+ * are passed again, unchanged.  alloc is called once, for 36 L bytes of per-pair records that the call no longer needs when it returns (the
+ * kernels are enqueued on `stream`; the call does not wait for them).  Outputs (P rows each, every row written): dL_dmeans3D (P, 3); dL_dmeans2D
+ * (P, 3) = dL/d(NDC x, NDC y) of the projected centre and 0; dL_dcolors (P, 3); dL_dopacities (P); with scales + rotations dL_dscales (P, 3) and
+ * dL_drotations (P, 4) (the quaternion as the forward uses it: unnormalised), with cov3D_precomp dL_dcov3D (P, 6) (an off-diagonal entry counts
+ * both of its uses); the unused pair may be NULL.  Conventions of diff_gaussian_rasterization: the gradient passes through alpha's min(0.99, .)
+ * as if it were not there, a view-space coordinate clamped at +-1.3 tan(fov) is a constant of the projection's Jacobian, the discrete decisions
+ * (frustum, radius and tiles, the 1 / 255 and saturation tests) are not differentiated, Gaussians of radius 0 get 0.  No background gradient.
+ * The sums have a fixed order: the result is bitwise reproducible. */
+GPCC_API int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D,
+                          const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                          const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
+                          const int *radii, const float *dL_dout, gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D,
+                          float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream);
 
 #ifdef __cplusplus
 }
