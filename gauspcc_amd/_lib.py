@@ -42,14 +42,14 @@ class Stage(C.Structure):
 
 
 GSR_STATE_WORDS = 16                                       # include/gauspcc.h
-GSR_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)   # gsr_alloc_fn: device memory for the training forward's frame state
+GSR_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)   # gsr_alloc_fn: device memory for the training paths (frame state, backward workspace)
 
 EXPORTS = [
     "gpcc_last_error", "gpcc_version", "gpcc_ctx_create", "gpcc_ctx_destroy", "gpcc_ctx_bytes", "gpcc_ctx_set_container_version", "gpcc_raster_order", "gpcc_voxelise",
     "gpcc_model_create", "gpcc_model_destroy", "gpcc_encode", "gpcc_decode", "gpcc_decode_to", "gpcc_encode_batch", "gpcc_decode_batch", "gpcc_sort_zyx",
     "gpcc_build_octree", "gpcc_conv3d", "gpcc_head_cdf", "gpcc_rc_encode", "gpcc_rc_decode", "gpcc_memcpy_d2d",
     "gpcc_profile_enable", "gpcc_profile_get", "gpcc_profile_stages", "gpcc_debug_trace_enable", "gpcc_debug_trace_get", "gpcc_debug_capture", "gpcc_debug_capture_get", "gpcc_debug_exclusive_scan", "gpcc_debug_launches", "gpcc_device_error_check",
-    "gsac_calculate_cdf", "gsac_encode", "gsac_decode", "gsac_encode_u16", "gsac_decode_u16", "gsac_encode_const", "gsac_decode_const", "gsac_host_encode_u16", "gsac_host_decode_u16", "gsac_host_encode_f32", "gsac_host_decode_f32", "gpcc_write_files", "gpcc_read_files", "gsac_encode_gaussian", "gsac_decode_gaussian", "gsac_encode_gaussian_mixed", "gsac_decode_gaussian_mixed", "gsac_calculate_cdf_mixed", "gsac_encode_gaussian_slices", "gsac_decode_gaussian_slices", "gsac_encode_gaussian_mixed_slices", "gsac_decode_gaussian_mixed_slices", "gshac_mlp2", "gshac_mlp2_act", "gsge_forward", "gsr_visible_filter", "gsr_forward", "gsr_forward_train", "gsr_backward", "gsnn_generate",
+    "gsac_calculate_cdf", "gsac_encode", "gsac_decode", "gsac_encode_u16", "gsac_decode_u16", "gsac_encode_const", "gsac_decode_const", "gsac_host_encode_u16", "gsac_host_decode_u16", "gsac_host_encode_f32", "gsac_host_decode_f32", "gpcc_write_files", "gpcc_read_files", "gsac_encode_gaussian", "gsac_decode_gaussian", "gsac_encode_gaussian_mixed", "gsac_decode_gaussian_mixed", "gsac_calculate_cdf_mixed", "gsac_encode_gaussian_slices", "gsac_decode_gaussian_slices", "gsac_encode_gaussian_mixed_slices", "gsac_decode_gaussian_mixed_slices", "gshac_mlp2", "gshac_mlp2_act", "gsge_forward", "gsge_forward_train", "gsge_backward", "gsr_visible_filter", "gsr_forward", "gsr_forward_train", "gsr_backward", "gsnn_generate",
 ]
 
 
@@ -129,6 +129,8 @@ def lib():
     L.gsac_encode_gaussian_mixed_slices.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), vp]
     L.gsac_decode_gaussian_mixed_slices.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i64, vp, i32, vp, vp]
     L.gsge_forward.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp]
+    L.gsge_forward_train.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.gsge_backward.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp, GSR_ALLOC, vp, vp]
     f32 = C.c_float
     L.gsr_visible_filter.argtypes = [vp, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, f32, f32, i32, vp, vp]
     L.gsr_forward.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, f32, f32, i32, vp, vp, C.POINTER(i64), vp]

@@ -2,6 +2,8 @@
 //   gsac_calculate_cdf   arithmetic.calculate_cdf      arithmetic.zip!arithmetic/arithmetic_kernel.cu:7-54
 //   gsac_encode/_decode  arithmetic.arithmetic_encode / arithmetic_decode   ...:94-232, 265-403
 //   gsge_forward         _gridencoder.grid_encode_forward   gridencoder.zip!gridencoder/src/gridencoder.cu:46-361
+//   gsge_forward_train   the same plus dy_dx                ...:363-657
+//   gsge_backward        _gridencoder.grid_encode_backward  ...:663-881, store-and-sum instead of atomicAdd
 // Same byte format as the reference's CUDA coder (chunks of `chunk_size` symbols, per-chunk byte
 // counts), same integerisation of the float CDF rows (rint(cdf * (65536 - (Lp-1))) + index).
 //
@@ -371,22 +373,13 @@ __device__ __forceinline__ uint32_t grid_index(int D, uint32_t F, uint32_t hashm
     return (index % hashmap_size) * F;
 }
 
-template <int D, int F>
-__global__ __launch_bounds__(TB) void k_grid_forward(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
-                                                     const int *__restrict__ resolutions, float *__restrict__ outputs, uint32_t N, uint32_t Rb,
-                                                     const uint8_t *__restrict__ binary_vxl, const int *__restrict__ min_level_id)
+// The corners of point x at one level (gridencoder.cu:180-330), shared by the forward and the backward's key pass: per corner its
+// weight, whether it is used (no coordinate at 0 or res - 1, and an occupied voxel in its binary_vxl footprint) and, when used, its
+// element offset (index % hashmap_size) * F in the level's table.  Returns wn_re = 1 / (sum of the used weights, 1e-9 when none).
+template <int D>
+__device__ __forceinline__ float grid_corners(const float *x, uint32_t res, uint32_t hashmap_size, uint32_t F, uint32_t Rb, const uint8_t *__restrict__ binary_vxl,
+                                              float *w_list, uint32_t *idx_list, bool *use)
 {
-    const uint32_t b = blockIdx.x * TB + threadIdx.x;
-    if (b >= N) return;
-    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
-    grid += (size_t)(uint32_t)offsets[level] * F;
-    const float *x = inputs + (size_t)b * D;
-    float *out = outputs + ((size_t)blockIdx.y * N + b) * F;
-    bool oob = false;
-    for (int d = 0; d < D; ++d) oob |= (x[d] < 0.0f || x[d] > 1.0f);
-    if (oob) { for (int ch = 0; ch < F; ++ch) out[ch] = 0.0f; return; }
-    const uint32_t hashmap_size = (uint32_t)(offsets[level + 1] - offsets[level]);
-    const uint32_t res = (uint32_t)resolutions[level];
     float pos[D];
     uint32_t pg[D];
     for (int d = 0; d < D; ++d) {
@@ -395,9 +388,6 @@ __global__ __launch_bounds__(TB) void k_grid_forward(const float *__restrict__ i
         pg[d] = (uint32_t)floorf(pos[d]);
         pos[d] -= (float)pg[d];
     }
-    float w_list[1 << D];
-    uint32_t idx_list[1 << D];
-    bool use[1 << D];
     float wn = 0.0f;
     for (int c = 0; c < (1 << D); ++c) {
         float w = 1.0f;
@@ -439,7 +429,29 @@ __global__ __launch_bounds__(TB) void k_grid_forward(const float *__restrict__ i
         if (use[c]) { idx_list[c] = grid_index(D, F, hashmap_size, res, pl); wn += w; }
     }
     if (wn == 0.0f) wn = (float)((double)wn + 1e-9);
-    const float wn_re = (float)(1.0 / (double)wn);
+    return (float)(1.0 / (double)wn);
+}
+
+template <int D, int F>
+__global__ __launch_bounds__(TB) void k_grid_forward(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
+                                                     const int *__restrict__ resolutions, float *__restrict__ outputs, uint32_t N, uint32_t Rb,
+                                                     const uint8_t *__restrict__ binary_vxl, const int *__restrict__ min_level_id)
+{
+    const uint32_t b = blockIdx.x * TB + threadIdx.x;
+    if (b >= N) return;
+    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
+    grid += (size_t)(uint32_t)offsets[level] * F;
+    const float *x = inputs + (size_t)b * D;
+    float *out = outputs + ((size_t)blockIdx.y * N + b) * F;
+    bool oob = false;
+    for (int d = 0; d < D; ++d) oob |= (x[d] < 0.0f || x[d] > 1.0f);
+    if (oob) { for (int ch = 0; ch < F; ++ch) out[ch] = 0.0f; return; }
+    const uint32_t hashmap_size = (uint32_t)(offsets[level + 1] - offsets[level]);
+    const uint32_t res = (uint32_t)resolutions[level];
+    float w_list[1 << D];
+    uint32_t idx_list[1 << D];
+    bool use[1 << D];
+    const float wn_re = grid_corners<D>(x, res, hashmap_size, F, Rb, binary_vxl, w_list, idx_list, use);
     float r[F];
     for (int ch = 0; ch < F; ++ch) r[ch] = 0.0f;
     for (int c = 0; c < (1 << D); ++c)
@@ -463,6 +475,246 @@ int grid_launch_f(hipStream_t st, int F, dim3 g, const float *in, const float *e
     }
     LAUNCH_CHECK();
     return GPCC_OK;
+}
+
+// ------------------------------------------------------------------ hash-grid training: dy_dx and backward
+// dy_dx[gd][ch] of one point at one level as gridencoder.cu:363-657 writes it: per axis gd, over the 2^(D-1) edges along gd in ascending
+// edge index, w = (res - 2) * prod_{d != gd} (1 - pos[d] or pos[d]) times (g_right - g_left), the two corners at pg[gd] and
+// min(pg[gd] + 1, res - 1); a corner with a coordinate at 0 or res - 1 reads as 0.  No wn normalisation and no binary_vxl mask (the
+// reference's formula: the exact derivative only inside the grid with all corners used).
+template <int D, int F>
+__device__ __forceinline__ void grid_dydx(const float *x, const float *__restrict__ grid, uint32_t res, uint32_t hashmap_size, float (&g)[D][F])
+{
+    float pos[D];
+    uint32_t pg[D];
+    for (int d = 0; d < D; ++d) {
+        const float t = x[d] * (float)(res - 2);
+        pos[d] = t + 0.5f;
+        pg[d] = (uint32_t)floorf(pos[d]);
+        pos[d] -= (float)pg[d];
+    }
+    for (int gd = 0; gd < D; ++gd) {
+        for (int ch = 0; ch < F; ++ch) g[gd][ch] = 0.0f;
+        for (int e = 0; e < (1 << (D - 1)); ++e) {
+            float w = (float)(res - 2);
+            uint32_t pl[D];
+            for (int nd = 0; nd < D - 1; ++nd) {
+                const int d = nd >= gd ? nd + 1 : nd;
+                if ((e & (1 << nd)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
+                else { w *= pos[d]; pl[d] = min(pg[d] + 1u, res - 1u); }
+            }
+            bool zl = false, zr = false;
+            pl[gd] = pg[gd];
+            for (int d = 0; d < D; ++d) zl |= (pl[d] == 0u || pl[d] == res - 1u);
+            const uint32_t il = zl ? 0u : grid_index(D, F, hashmap_size, res, pl);
+            pl[gd] = min(pg[gd] + 1u, res - 1u);
+            for (int d = 0; d < D; ++d) zr |= (pl[d] == 0u || pl[d] == res - 1u);
+            const uint32_t ir = zr ? 0u : grid_index(D, F, hashmap_size, res, pl);
+            for (int ch = 0; ch < F; ++ch) {
+                const float gl = zl ? 0.0f : grid[il + ch], gr = zr ? 0.0f : grid[ir + ch];
+                g[gd][ch] = __builtin_fmaf(w, gr - gl, g[gd][ch]);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ bool grid_oob(const float *x, int D)
+{
+    bool oob = false;
+    for (int d = 0; d < D; ++d) oob |= (x[d] < 0.0f || x[d] > 1.0f);
+    return oob;
+}
+
+// dy_dx (N, L, D, F) of the training forward: one thread per (point, level), beside the unchanged k_grid_forward
+template <int D, int F>
+__global__ __launch_bounds__(TB) void k_grid_dydx(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
+                                                  const int *__restrict__ resolutions, float *__restrict__ dy_dx, uint32_t N, const int *__restrict__ min_level_id)
+{
+    const uint32_t b = blockIdx.x * TB + threadIdx.x;
+    if (b >= N) return;
+    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
+    const float *x = inputs + (size_t)b * D;
+    float *out = dy_dx + ((size_t)b * gridDim.y + blockIdx.y) * D * F;
+    float g[D][F];
+    if (grid_oob(x, D)) {
+        for (int d = 0; d < D; ++d)
+            for (int ch = 0; ch < F; ++ch) g[d][ch] = 0.0f;
+    } else {
+        grid_dydx<D, F>(x, grid + (size_t)(uint32_t)offsets[level] * F, (uint32_t)resolutions[level], (uint32_t)(offsets[level + 1] - offsets[level]), g);
+    }
+    for (int d = 0; d < D; ++d)
+        for (int ch = 0; ch < F; ++ch) out[d * F + ch] = g[d][ch];
+}
+
+// Backward, embedding gradient: store and sum, no float atomics.
+//   key pass   one thread per (point b, level l): corner c's contribution lives at slot s = (b L + l) 2^D + c; the key is its table row
+//              offsets[level] + idx / F (the sentinel n_rows when the corner is unused or the point out of range), the value the slot,
+//              and wts[s] = w_c wn_re.
+//   sort       stable LSD radix sort on the key: each row's contributions become one run in ascending slot order.
+//   sum        one thread per chunk of GB_CHUNK sorted entries sums each run it holds in order (fmaf(w, grad[l, b, ch], acc)).  A run
+//              wholly inside the chunk goes straight into grad_embeddings; a chunk's first run continued from the previous chunk leaves
+//              a head partial, a run that starts in it and continues leaves a tail partial and makes the chunk that row's owner.
+//   combine    each owner adds the following chunks' head partials to its tail partial in chunk order, then the total into the row.
+// Every row is written by exactly one thread and summed in an order fixed by the sorted keys alone: bitwise reproducible.
+constexpr int GB_CHUNK = 32;
+
+template <int D>
+__global__ __launch_bounds__(TB) void k_grid_bwd_keys(const float *__restrict__ inputs, const int *__restrict__ offsets, const int *__restrict__ resolutions,
+                                                      uint32_t N, uint32_t F, uint32_t Rb, const uint8_t *__restrict__ binary_vxl,
+                                                      const int *__restrict__ min_level_id, uint32_t n_rows, uint64_t *__restrict__ keys,
+                                                      uint32_t *__restrict__ slots, float *__restrict__ wts)
+{
+    const uint32_t b = blockIdx.x * TB + threadIdx.x;
+    if (b >= N) return;
+    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
+    const uint32_t s0 = (b * gridDim.y + blockIdx.y) << D;
+    const float *x = inputs + (size_t)b * D;
+    float w_list[1 << D];
+    uint32_t idx_list[1 << D];
+    bool use[1 << D];
+    float wn_re = 0.0f;
+    const bool oob = grid_oob(x, D);
+    const uint32_t off = (uint32_t)offsets[level];
+    if (!oob) wn_re = grid_corners<D>(x, (uint32_t)resolutions[level], (uint32_t)(offsets[level + 1] - offsets[level]), F, Rb, binary_vxl, w_list, idx_list, use);
+    for (int c = 0; c < (1 << D); ++c) {
+        uint32_t row = n_rows;
+        if (!oob && use[c]) {
+            row = off + idx_list[c] / F;
+            if (row >= n_rows) row = n_rows;     // offsets beyond the caller's table: dropped, never written out of bounds
+            else wts[s0 + c] = w_list[c] * wn_re;
+        }
+        keys[s0 + c] = row;
+        slots[s0 + c] = s0 + c;
+    }
+}
+
+template <int F>
+__device__ __forceinline__ void gb_add(float (&acc)[F], const float *__restrict__ grad, const uint32_t *__restrict__ slots, const float *__restrict__ wts,
+                                       int64_t i, int D, uint32_t N, uint32_t L)
+{
+    const uint32_t s = slots[i], q = s >> D, b = q / L, l = q - b * L;
+    const float w = wts[s];
+    const float *g = grad + ((size_t)l * N + b) * F;
+    for (int ch = 0; ch < F; ++ch) acc[ch] = __builtin_fmaf(w, g[ch], acc[ch]);
+}
+
+template <int F>
+__global__ __launch_bounds__(TB) void k_grid_bwd_sum(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ slots, const float *__restrict__ wts,
+                                                     const float *__restrict__ grad, int D, uint32_t N, uint32_t L, int64_t E, uint32_t n_rows,
+                                                     float *__restrict__ grad_emb, float *__restrict__ head, float *__restrict__ tail, uint8_t *__restrict__ own)
+{
+    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x, i0 = t * GB_CHUNK;
+    if (i0 >= E) return;
+    const int64_t i1 = min(i0 + (int64_t)GB_CHUNK, E);
+    uint32_t row = (uint32_t)keys[i0];
+    bool first = true, starts = i0 == 0 || (uint32_t)keys[i0 - 1] != row;
+    uint8_t owner = 0;
+    float acc[F];
+    for (int ch = 0; ch < F; ++ch) acc[ch] = 0.0f;
+    auto flush = [&](bool cont) {
+        if (row >= n_rows) return;
+        if (first && !starts) { for (int ch = 0; ch < F; ++ch) head[t * F + ch] = acc[ch]; }
+        else if (cont) { for (int ch = 0; ch < F; ++ch) tail[t * F + ch] = acc[ch]; owner = 1; }
+        else { for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += acc[ch]; }
+    };
+    for (int64_t i = i0; i < i1; ++i) {
+        const uint32_t k = (uint32_t)keys[i];
+        if (k != row) {
+            flush(false);
+            row = k; first = false; starts = true;
+            for (int ch = 0; ch < F; ++ch) acc[ch] = 0.0f;
+        }
+        if (row < n_rows) gb_add<F>(acc, grad, slots, wts, i, D, N, L);
+    }
+    flush(i1 < E && (uint32_t)keys[i1] == row);
+    own[t] = owner;
+}
+
+// the owners' walk: partials are read GB_WALK chunks at a time, so that a long run waits on memory once per GB_WALK chunks
+constexpr int GB_WALK = 8;
+
+template <int F>
+__global__ __launch_bounds__(TB) void k_grid_bwd_combine(const uint64_t *__restrict__ keys, int64_t E, int64_t nchunks, const float *__restrict__ head,
+                                                         const float *__restrict__ tail, const uint8_t *__restrict__ own, float *__restrict__ grad_emb)
+{
+    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (t >= nchunks || !own[t]) return;
+    const uint32_t row = (uint32_t)keys[min((t + 1) * GB_CHUNK, E) - 1];
+    float s[F];
+    for (int ch = 0; ch < F; ++ch) s[ch] = tail[t * F + ch];
+    for (int64_t j0 = t + 1; j0 < nchunks; j0 += GB_WALK) {
+        float h[GB_WALK][F];
+        bool more[GB_WALK];
+#pragma unroll
+        for (int u = 0; u < GB_WALK; ++u) {
+            const int64_t j = j0 + u, nxt = (j + 1) * GB_CHUNK;
+            for (int ch = 0; ch < F; ++ch) h[u][ch] = j < nchunks ? head[j * F + ch] : 0.0f;
+            more[u] = j < nchunks && nxt < E && (uint32_t)keys[nxt] == row;
+        }
+        bool done = false;
+#pragma unroll
+        for (int u = 0; u < GB_WALK; ++u) {
+            if (done) break;
+            for (int ch = 0; ch < F; ++ch) s[ch] += h[u][ch];
+            done = !more[u];
+        }
+        if (done) break;
+    }
+    for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += s[ch];
+}
+
+// Backward, input gradient: one thread per point, dy_dx recomputed; levels outer, channels inner (gridencoder.cu:857-881)
+template <int D, int F>
+__global__ __launch_bounds__(TB) void k_grid_bwd_inputs(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
+                                                        const int *__restrict__ resolutions, const float *__restrict__ grad, uint32_t N, uint32_t L,
+                                                        const int *__restrict__ min_level_id, float *__restrict__ grad_inputs)
+{
+    const uint32_t b = blockIdx.x * TB + threadIdx.x;
+    if (b >= N) return;
+    const float *x = inputs + (size_t)b * D;
+    float r[D];
+    for (int d = 0; d < D; ++d) r[d] = 0.0f;
+    if (!grid_oob(x, D)) {
+        const uint32_t ml = min_level_id ? (uint32_t)min_level_id[b] : 0u;
+        for (uint32_t l = 0; l < L; ++l) {
+            const uint32_t level = ml + l;
+            float g[D][F];
+            grid_dydx<D, F>(x, grid + (size_t)(uint32_t)offsets[level] * F, (uint32_t)resolutions[level], (uint32_t)(offsets[level + 1] - offsets[level]), g);
+            const float *gp = grad + ((size_t)l * N + b) * F;
+            for (int ch = 0; ch < F; ++ch)
+                for (int d = 0; d < D; ++d) r[d] = __builtin_fmaf(gp[ch], g[d][ch], r[d]);
+        }
+    }
+    for (int d = 0; d < D; ++d) grad_inputs[(size_t)b * D + d] = r[d];
+}
+
+template <int D>
+int grid_dydx_launch(hipStream_t st, int F, dim3 g, const float *in, const float *emb, const int *off, const int *res, float *dy_dx, uint32_t N, const int *ml)
+{
+    switch (F) {
+    case 1: k_grid_dydx<D, 1><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
+    case 2: k_grid_dydx<D, 2><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
+    case 4: k_grid_dydx<D, 4><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
+    case 8: k_grid_dydx<D, 8><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
+    default: return fail(GPCC_ERR_ARG, "GridEncoding: n_features must be 1, 2, 4 or 8");
+    }
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
+
+template <int D, int F>
+void grid_bwd_inputs_launch(hipStream_t st, const float *in, const float *emb, const int *off, const int *res, const float *grad, uint32_t N, uint32_t L,
+                            const int *ml, float *gi)
+{
+    k_grid_bwd_inputs<D, F><<<(unsigned)cdiv(N, TB), TB, 0, st>>>(in, emb, off, res, grad, N, L, ml, gi);
+}
+
+template <int F>
+void grid_bwd_sum_launch(hipStream_t st, const uint64_t *keys, const uint32_t *slots, const float *wts, const float *grad, int D, uint32_t N, uint32_t L,
+                         int64_t E, uint32_t n_rows, float *grad_emb, float *head, float *tail, uint8_t *own, int64_t nchunks)
+{
+    k_grid_bwd_sum<F><<<(unsigned)cdiv(nchunks, TB), TB, 0, st>>>(keys, slots, wts, grad, D, N, L, E, n_rows, grad_emb, head, tail, own);
+    k_grid_bwd_combine<F><<<(unsigned)cdiv(nchunks, TB), TB, 0, st>>>(keys, E, nchunks, head, tail, own, grad_emb);
 }
 
 }  // namespace
@@ -1258,4 +1510,87 @@ extern "C" int gsge_forward(gpcc_ctx *ctx, const float *inputs, const float *emb
     case 3: return grid_launch_f<3>(st, n_features, g, inputs, embeddings, offsets, resolutions, outputs, (uint32_t)N, (uint32_t)Rb, binary_vxl, min_level_id);
     default: return fail(GPCC_ERR_ARG, "GridEncoding: num_dim must be 1, 2 or 3");
     }
+}
+
+// gsge_forward plus dy_dx (N, L, D, F) for the input gradient of _gridencoder's caller (NULL: outputs only).  outputs come from the same
+// k_grid_forward launch as gsge_forward's.
+extern "C" int gsge_forward_train(gpcc_ctx *ctx, const float *inputs, const float *embeddings, const int32_t *offsets, const int32_t *resolutions,
+                                  float *outputs, int64_t N, int num_dim, int n_features, int n_levels, int Rb, const uint8_t *binary_vxl,
+                                  const int32_t *min_level_id, float *dy_dx, void *stream)
+{
+    GP_TRY(gsge_forward(ctx, inputs, embeddings, offsets, resolutions, outputs, N, num_dim, n_features, n_levels, Rb, binary_vxl, min_level_id, stream));
+    if (!dy_dx || N <= 0 || n_levels <= 0) return GPCC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g((unsigned)cdiv(N, TB), (unsigned)n_levels);
+    switch (num_dim) {
+    case 1: return grid_dydx_launch<1>(st, n_features, g, inputs, embeddings, offsets, resolutions, dy_dx, (uint32_t)N, min_level_id);
+    case 2: return grid_dydx_launch<2>(st, n_features, g, inputs, embeddings, offsets, resolutions, dy_dx, (uint32_t)N, min_level_id);
+    default: return grid_dydx_launch<3>(st, n_features, g, inputs, embeddings, offsets, resolutions, dy_dx, (uint32_t)N, min_level_id);
+    }
+}
+
+// _gridencoder.grid_encode_backward without float atomics (see k_grid_bwd_keys): adds into grad_embeddings (n_rows, F), overwrites grad_inputs
+// (N, D) when given.  Workspace (about 28 bytes per (point, level, corner)) through `alloc`; no synchronisation.
+extern "C" int gsge_backward(gpcc_ctx *ctx, const float *grad, const float *inputs, const float *embeddings, const int32_t *offsets, const int32_t *resolutions,
+                             int64_t n_rows, float *grad_embeddings, float *grad_inputs, int64_t N, int num_dim, int n_features, int n_levels, int Rb,
+                             const uint8_t *binary_vxl, const int32_t *min_level_id, gsr_alloc_fn alloc, void *alloc_user, void *stream)
+{
+    if (!ctx || !grad || !inputs || !embeddings || !offsets || !resolutions || !grad_embeddings || !alloc) return fail(GPCC_ERR_ARG, "null argument");
+    if (num_dim < 1 || num_dim > 3) return fail(GPCC_ERR_ARG, "GridEncoding: num_dim must be 1, 2 or 3");
+    if (n_features != 1 && n_features != 2 && n_features != 4 && n_features != 8) return fail(GPCC_ERR_ARG, "GridEncoding: n_features must be 1, 2, 4 or 8");
+    if (N <= 0 || n_levels <= 0) {
+        if (grad_inputs && N > 0) HIP_TRY(hipMemsetAsync(grad_inputs, 0, (size_t)N * num_dim * sizeof(float), (hipStream_t)stream));
+        return GPCC_OK;
+    }
+    if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31) - 1) return fail(GPCC_ERR_ARG, "bad embedding row count");
+    const int64_t E = (N * n_levels) << num_dim;
+    if (E >= ((int64_t)1 << 32)) return fail(GPCC_ERR_ARG, "too many (point, level, corner) slots for 32-bit slot ids");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int F = n_features;
+    const int64_t nchunks = cdiv(E, GB_CHUNK);
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_kb = al(8 * (size_t)E), o_va = o_kb + al(8 * (size_t)E), o_vb = o_va + al(4 * (size_t)E), o_w = o_vb + al(4 * (size_t)E);
+    const size_t o_h = o_w + al(4 * (size_t)E), o_hd = o_h + al(4 * (size_t)radix_sort_hist_words(E)), o_tl = o_hd + al(4 * (size_t)nchunks * F);
+    const size_t o_own = o_tl + al(4 * (size_t)nchunks * F), bytes = o_own + al((size_t)nchunks);
+    char *blk = static_cast<char *>(alloc(alloc_user, bytes));
+    if (!blk) return fail(GPCC_ERR_NOMEM, "grid encoder backward workspace (%zu bytes)", bytes);
+    uint64_t *ka = reinterpret_cast<uint64_t *>(blk), *kb = reinterpret_cast<uint64_t *>(blk + o_kb);
+    uint32_t *va = reinterpret_cast<uint32_t *>(blk + o_va), *vb = reinterpret_cast<uint32_t *>(blk + o_vb);
+    float *wts = reinterpret_cast<float *>(blk + o_w), *head = reinterpret_cast<float *>(blk + o_hd), *tail = reinterpret_cast<float *>(blk + o_tl);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(blk + o_h);
+    uint8_t *own = reinterpret_cast<uint8_t *>(blk + o_own);
+    const uint32_t n = (uint32_t)N, L = (uint32_t)n_levels, nr = (uint32_t)n_rows;
+    dim3 g((unsigned)cdiv(N, TB), L);
+    switch (num_dim) {
+    case 1: k_grid_bwd_keys<1><<<g, TB, 0, st>>>(inputs, offsets, resolutions, n, (uint32_t)F, (uint32_t)Rb, binary_vxl, min_level_id, nr, ka, va, wts); break;
+    case 2: k_grid_bwd_keys<2><<<g, TB, 0, st>>>(inputs, offsets, resolutions, n, (uint32_t)F, (uint32_t)Rb, binary_vxl, min_level_id, nr, ka, va, wts); break;
+    default: k_grid_bwd_keys<3><<<g, TB, 0, st>>>(inputs, offsets, resolutions, n, (uint32_t)F, (uint32_t)Rb, binary_vxl, min_level_id, nr, ka, va, wts); break;
+    }
+    LAUNCH_CHECK();
+    int bits = 1;
+    while (((int64_t)1 << bits) <= n_rows) ++bits;    // the sentinel n_rows sorts last
+    uint64_t *k0 = ka, *k1 = kb;
+    uint32_t *v0 = va, *v1 = vb;
+    GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, E, bits, hist));
+    switch (F) {
+    case 1: grid_bwd_sum_launch<1>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
+    case 2: grid_bwd_sum_launch<2>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
+    case 4: grid_bwd_sum_launch<4>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
+    default: grid_bwd_sum_launch<8>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
+    }
+    LAUNCH_CHECK();
+    if (grad_inputs) {
+#define GB_IN(D, F) grid_bwd_inputs_launch<D, F>(st, inputs, embeddings, offsets, resolutions, grad, n, L, min_level_id, grad_inputs)
+#define GB_IN_F(D) switch (F) { case 1: GB_IN(D, 1); break; case 2: GB_IN(D, 2); break; case 4: GB_IN(D, 4); break; default: GB_IN(D, 8); break; }
+        switch (num_dim) {
+        case 1: GB_IN_F(1); break;
+        case 2: GB_IN_F(2); break;
+        default: GB_IN_F(3); break;
+        }
+#undef GB_IN_F
+#undef GB_IN
+        LAUNCH_CHECK();
+    }
+    return GPCC_OK;
 }

@@ -618,8 +618,10 @@ __global__ __launch_bounds__(64) void k_radix_small(uint64_t *__restrict__ keys,
     }
 }
 
+int64_t radix_sort_hist_words(int64_t n) { return 256 * cdiv(n, RS_TILE); }
+
 int radix_sort_u64(gpcc_ctx *ctx, hipStream_t st, uint64_t **keys_io, uint64_t **keys_tmp_io, uint32_t **vals_io,
-                   uint32_t **vals_tmp_io, int64_t n, int bits)
+                   uint32_t **vals_tmp_io, int64_t n, int bits, uint32_t *hist_ws)
 {
     if (n <= 1 || bits <= 0) return GPCC_OK;
     if (bits > 64) bits = 64;
@@ -631,7 +633,11 @@ int radix_sort_u64(gpcc_ctx *ctx, hipStream_t st, uint64_t **keys_io, uint64_t *
     }
     const int64_t ntiles = cdiv(n, RS_TILE);
     size_t mk = ctx->arena.mark();
-    TAKE(hist, uint32_t, 256 * ntiles);
+    uint32_t *hist = hist_ws;
+    if (!hist) {
+        TAKE(arena_hist, uint32_t, 256 * ntiles);
+        hist = arena_hist;
+    }
     const bool has_val = vals_io && *vals_io;
     for (int shift = 0; shift < bits; shift += 8) {
         k_radix_hist<<<dim3((unsigned)ntiles), RS_T, 0, st>>>(*keys_io, n, shift, hist, ntiles);

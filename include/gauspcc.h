@@ -386,10 +386,29 @@ GPCC_API int gshac_mlp2_act(gpcc_ctx *ctx, const float *x_dev, const float *w1_d
 
 /* _gridencoder.grid_encode_forward (inputs (N,D) in [0,1], embeddings (sO,F), offsets (L+1), resolutions (L),
  * outputs (L,N,F), ..., Rb, binary_vxl, min_level_id)   gridencoder.zip!gridencoder/src/gridencoder.h:12-22,
- * gridencoder.cu:100-361 (forward only; dy_dx / backward are training-side and out of scope).  All device. */
+ * gridencoder.cu:100-361 (the inference forward: no dy_dx).  All device. */
 GPCC_API int gsge_forward(gpcc_ctx *ctx, const float *inputs_dev, const float *embeddings_dev, const int32_t *offsets_dev,
                           const int32_t *resolutions_dev, float *outputs_dev, int64_t n, int num_dim, int n_features, int n_levels,
                           int rb, const uint8_t *binary_vxl_dev, const int32_t *min_level_id_dev, void *stream);
+
+/* Device memory from the caller for the training paths (the grid encoder's backward workspace; the rasteriser's frame state, below):
+ * alloc(alloc_user, bytes) returns a 256-byte aligned device pointer, or NULL (the call then fails with GPCC_ERR_NOMEM). */
+typedef void *(*gsr_alloc_fn)(void *user, size_t bytes);
+
+/* The training forward: gsge_forward's outputs (bit-identical) and, when dy_dx_dev is not NULL, dy_dx (N, L, D, F) with the
+ * reference's formula (gridencoder.cu:363-657: edge differences times res - 2, border corners read as 0, no wn, no binary_vxl). */
+GPCC_API int gsge_forward_train(gpcc_ctx *ctx, const float *inputs_dev, const float *embeddings_dev, const int32_t *offsets_dev,
+                                const int32_t *resolutions_dev, float *outputs_dev, int64_t n, int num_dim, int n_features, int n_levels,
+                                int rb, const uint8_t *binary_vxl_dev, const int32_t *min_level_id_dev, float *dy_dx_dev, void *stream);
+
+/* _gridencoder.grid_encode_backward (gridencoder.cu:663-881): grad (L,N,F).  ADDS the embedding gradient into grad_embeddings
+ * (n_rows, F) -- rows without contributions are untouched -- and OVERWRITES grad_inputs (N, D) when it is not NULL (dy_dx recomputed
+ * from the inputs).  Bitwise reproducible: no float atomics (key pass, stable radix sort by table row, fixed-order sums).  Workspace
+ * (about 28 bytes per (point, level, corner)) through `alloc`; enqueued on `stream` without synchronising. */
+GPCC_API int gsge_backward(gpcc_ctx *ctx, const float *grad_dev, const float *inputs_dev, const float *embeddings_dev, const int32_t *offsets_dev,
+                           const int32_t *resolutions_dev, int64_t n_rows, float *grad_embeddings_dev, float *grad_inputs_dev, int64_t n,
+                           int num_dim, int n_features, int n_levels, int rb, const uint8_t *binary_vxl_dev, const int32_t *min_level_id_dev,
+                           gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
 /* ================= generate_neural_gaussians, inference path =================
  * src/gs_compress/HAC/gaussian_renderer/__init__.py:25-172 after attribute quantisation (:103-114, done by the caller):
@@ -433,7 +452,6 @@ GPCC_API int gsr_forward(gpcc_ctx *ctx, int P, const float *background, int W, i
  * forward and the backward.  state (host, GSR_STATE_WORDS words) receives the pair count, P, W, H and the device addresses of that state; it
  * is opaque to the caller and is handed back to gsr_backward unchanged.  Always the two-level sort; colours precomputed. */
 #define GSR_STATE_WORDS 16
-typedef void *(*gsr_alloc_fn)(void *user, size_t bytes);
 GPCC_API int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
                                const float *opacities, const float *scales, float scale_modifier, const float *rotations,
                                const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
