@@ -472,6 +472,37 @@ GPCC_API int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const flo
                           const int *radii, const float *dL_dout, gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D,
                           float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream);
 
+/* ================= GausPcgc context network, training path (network_ue_4stage_conv.py:100-182 with gradients) =================
+ * The frame is the encoder's teacher-forced layout: one octree (the FOG loop), a "prior set" of rows (levels 0..L-2 concatenated, base
+ * level first, each level in Morton order) and a "target set" (levels 1..L-1), and ONE tile pool for the convolutions of both.  Rows of
+ * features are (rows, 32) float32 in the library's PHYSICAL channel order (logical channel c sits at column 4 (c % 4) + c / 4 for c < 16,
+ * 16 + 4 (c % 4) + (c - 16) / 4 above); weights and weight gradients use the upstream (K, Cin, Cout) layout in this library's offset
+ * enumeration (gauspcc_amd.model.conv_offset_layout).  32 channels only; k = 3, 5 or 7.
+ *
+ * gpcc_train_frame: xyz (n, 3) int32 device, duplicate-free, any sign.  Everything a convolution or its backward needs is copied into ONE
+ * block of caller memory (alloc is called once), so other calls on ctx may run between the forward and the backward; state (host,
+ * GPCC_TRAIN_STATE_WORDS words) is opaque and stays valid while that block lives.  levels_out / level_nodes_out (24) as in gpcc_stats. */
+#define GPCC_TRAIN_STATE_WORDS 256
+GPCC_API int gpcc_train_frame(gpcc_ctx *ctx, const int32_t *xyz_dev, int64_t n, int kernel_size, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state,
+                              int32_t *levels_out, int64_t *level_nodes_out, void *stream);
+/* The frame's nodes, all levels concatenated base first (Morton order inside a level, so the children of a node are contiguous and
+ * octant-ascending): occ (nodes) uint8, coords (nodes, 3) int32; for the target set's rows parent (rows) int32 = the parent's row in the
+ * prior set and octant (rows) uint8 = x%2 + 2 (y%2) + 4 (z%2).  Any pointer may be NULL. */
+GPCC_API int gpcc_train_frame_nodes(gpcc_ctx *ctx, const uint64_t *state, uint8_t *occ_dev, int32_t *parent_dev, uint8_t *octant_dev, int32_t *coords_dev,
+                                    void *stream);
+/* w (K, 32, 32) device -> frag (K x 2048 floats) device, the layouts the convolution reads; mirror != 0 builds W'[o] = W[K-1-o]^T, the
+ * weights of the input gradient.  channels != 32: GPCC_ERR_ARG. */
+GPCC_API int gpcc_train_weights(gpcc_ctx *ctx, const float *w_dev, int channels, int kernel_size, int mirror, float *frag_dev, void *stream);
+/* out = conv(in) (+ res) (ReLU if relu) over the rows of one set (0 = prior, 1 = target): the codec's convolution kernels, bit-identical to
+ * gpcc_conv3d on the same coordinates.  With mirrored fragments and the (masked) output gradient as `in` this is the input gradient. */
+GPCC_API int gpcc_train_conv(gpcc_ctx *ctx, const uint64_t *state, int set, const float *in_dev, const float *frag_dev, const float *res_dev, int relu,
+                             float *out_dev, void *stream);
+/* grad_w (K, 32, 32) = sum over the (output row i, neighbour row j) pairs of offset o of x[j]^T dy[i] (x, dy rows of the set, physical order).
+ * OVERWRITES grad_w.  Fixed-order sums, no atomics: bitwise reproducible.  alloc is called once for K x groups x 4 KiB of partials
+ * (groups <= ceil(8192 / K)), which the call no longer needs once its kernels have run (enqueued on `stream`, not waited for). */
+GPCC_API int gpcc_train_wgrad(gpcc_ctx *ctx, const uint64_t *state, int set, const float *x_dev, const float *dy_dev, gsr_alloc_fn alloc, void *alloc_user,
+                              float *grad_w_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
