@@ -503,6 +503,20 @@ GPCC_API int gpcc_train_conv(gpcc_ctx *ctx, const uint64_t *state, int set, cons
 GPCC_API int gpcc_train_wgrad(gpcc_ctx *ctx, const uint64_t *state, int set, const float *x_dev, const float *dy_dev, gsr_alloc_fn alloc, void *alloc_user,
                               float *grad_w_dev, void *stream);
 
+/* ================= Exact k-nearest neighbours (training initialisation) =================
+ * simple_knn._C.distCUDA2(points) (simple-knn.zip!simple-knn/spatial.cu:16-23, simple_knn.cu:185-219: k = 3, the mean) and sklearn's
+ * NearestNeighbors(K).kneighbors(X) on its fit data (TC-GS/scene/gaussian_model.py:1052-1059: k = K - 1 plus the point itself).
+ * xyz (n, 3) float32 device, 0 <= n < 2^31, 1 <= k <= 16.  With d(i, j) = (dx*dx + dy*dy) + dz*dz, dx = x_j - x_i, in float32 without
+ * contraction: L_i = the k smallest pairs (d(i, j), j) over j != i in lexicographic order (distance, then index), pairs with d > FLT_MAX
+ * (overflow) left out, padded with (FLT_MAX, -1).  Outputs, each may be NULL: idx_out (n, k) int64 and dist2_out (n, k) float32 = L_i,
+ * mean_out (n) = the sequential float32 sum of L_i's distances / (float)k (for k = 3 simple_knn's value, its P <= 3 sentinels included).
+ * A NaN or infinite coordinate: GPCC_ERR_ARG, nothing written.  The cost is below quadratic on every input (a Morton-sorted 64-ary tree of
+ * boxes, csrc/knn.hip), 1M identical points included.  alloc is called once, for at most 26 n + 65536 bytes that the call no longer needs
+ * once its kernels have run; ctx's workspace arena holds nothing that grows with n.  Enqueued on `stream`; the only synchronisation is the
+ * read-back of the non-finite flag. */
+GPCC_API int gpcc_knn(gpcc_ctx *ctx, const float *xyz_dev, int64_t n, int k, int64_t *idx_out, float *dist2_out, float *mean_out,
+                     gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
