@@ -517,6 +517,35 @@ GPCC_API int gpcc_train_wgrad(gpcc_ctx *ctx, const uint64_t *state, int set, con
 GPCC_API int gpcc_knn(gpcc_ctx *ctx, const float *xyz_dev, int64_t n, int k, int64_t *idx_out, float *dist2_out, float *mean_out,
                      gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
+/* ================= Anchor growing (training densification, HAC/scene/gaussian_model.py:823-911) =================
+ * torch_scatter.scatter_max in row form: src (m, c) float32, index (m) int64 in [0, dim_size); out, arg (dim_size, c).  For slot s and
+ * column c over G = {j : index[j] = s}: out = the maximum over G (and over out's initial value when include_self), a NaN in G making it
+ * NaN; arg = the smallest j in G with src[j, c] == out (with a NaN out: the smallest j holding a NaN), or m if there is none; out's bits
+ * are src[arg, c]'s when arg < m.  Without include_self this is torch_scatter's own output: initialised to -FLT_MAX, maximised, and then
+ * every value still equal to -FLT_MAX set to 0 (masked_fill(out == lowest, 0)): an empty slot gives (0, m), a group whose maximum is
+ * -FLT_MAX gives (0, its smallest such j), a group of -inf only gives (0, m).  torch_scatter's tie rule depends on the order of atomics;
+ * this one does not, and no float atomics are used.  An index outside [0, dim_size): GPCC_ERR_ARG, nothing written (the call's only
+ * synchronisation reads that flag back).  alloc is called once, for at most 24 m + 8 dim_size c bytes plus the sort's digit table and
+ * 256 bytes, that the call no longer needs once its kernels have run.  m < 2^31.  Enqueued on `stream`. */
+GPCC_API int gpcc_scatter_max(gpcc_ctx *ctx, const float *src_dev, const int64_t *index_dev, int64_t m, int64_t c, int64_t dim_size,
+                              int include_self, float *out_dev, int64_t *arg_dev, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
+/* One grid level of anchor_growing.  Candidates xyz (m, 3) float32 with feature rows rows (m) int64 into feats (nrows, c) float32 (rows
+ * NULL: row j is candidate j); existing anchors (n, 3) float32.  Voxel g = (int32)rint(x * inv) per axis (one rounded float32 product,
+ * round half to even: torch's `round(x / size).int()` on the GPU, whose division by a CPU scalar multiplies by inv = 1.0f / size).
+ * A non-finite coordinate or one outside int32 after rounding (candidates or anchors), or a row outside [0, nrows): GPCC_ERR_ARG with
+ * nothing written.  Result: the U unique candidate voxels that hold no anchor voxel, in lexicographic signed (x, y, z) order (that of
+ * torch.unique(dim=0)); anchors (U, 3) = (float)g * size; features (U, c) = scatter_max over each voxel's candidates of feats[rows[j]]
+ * without include_self (the rule above, -FLT_MAX masked to 0).  *count_out = U.  Two synchronisations: the read-back of the
+ * candidates' box and the invalid-input flag, and that of U.  alloc is called (1) once for the workspace, at most 84 m + 56 n bytes plus
+ * the sort's digit table and 1 KiB, then, only when U > 0, (2) for the outputs, anchors at offset 0 and features at offset
+ * (12 U + 255) & ~255, and (3) for 8 U c bytes of per-column maxima.  (1) and (3) are not needed once the kernels have run.  When the
+ * candidates' voxels span less than 2^21 per axis one packed key is sorted; otherwise two sorts (z, then x and y) handle any int32
+ * voxel.  m, n < 2^31; enqueued on `stream`. */
+GPCC_API int gpcc_grow_voxels(gpcc_ctx *ctx, const float *xyz_dev, int64_t m, const int64_t *rows_dev, const float *feats_dev, int64_t nrows,
+                              int64_t c, const float *anchors_dev, int64_t n, float inv, float size, int64_t *count_out, gsr_alloc_fn alloc,
+                              void *alloc_user, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
