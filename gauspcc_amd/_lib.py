@@ -50,7 +50,7 @@ EXPORTS = [
     "gpcc_model_create", "gpcc_model_destroy", "gpcc_encode", "gpcc_decode", "gpcc_decode_to", "gpcc_encode_batch", "gpcc_decode_batch", "gpcc_sort_zyx",
     "gpcc_build_octree", "gpcc_conv3d", "gpcc_head_cdf", "gpcc_rc_encode", "gpcc_rc_decode", "gpcc_memcpy_d2d",
     "gpcc_profile_enable", "gpcc_profile_get", "gpcc_profile_stages", "gpcc_debug_trace_enable", "gpcc_debug_trace_get", "gpcc_debug_capture", "gpcc_debug_capture_get", "gpcc_debug_exclusive_scan", "gpcc_debug_launches", "gpcc_device_error_check",
-    "gsac_calculate_cdf", "gsac_encode", "gsac_decode", "gsac_encode_u16", "gsac_decode_u16", "gsac_encode_const", "gsac_decode_const", "gsac_host_encode_u16", "gsac_host_decode_u16", "gsac_host_encode_f32", "gsac_host_decode_f32", "gpcc_write_files", "gpcc_read_files", "gsac_encode_gaussian", "gsac_decode_gaussian", "gsac_encode_gaussian_mixed", "gsac_decode_gaussian_mixed", "gsac_calculate_cdf_mixed", "gsac_encode_gaussian_slices", "gsac_decode_gaussian_slices", "gsac_encode_gaussian_mixed_slices", "gsac_decode_gaussian_mixed_slices", "gshac_mlp2", "gshac_mlp2_act", "gsge_forward", "gsge_forward_train", "gsge_backward", "gsr_visible_filter", "gsr_forward", "gsr_forward_train", "gsr_backward", "gsnn_generate",
+    "gsac_calculate_cdf", "gsac_encode", "gsac_decode", "gsac_encode_u16", "gsac_decode_u16", "gsac_encode_const", "gsac_decode_const", "gsac_host_encode_u16", "gsac_host_decode_u16", "gsac_host_encode_f32", "gsac_host_decode_f32", "gpcc_write_files", "gpcc_read_files", "gsac_encode_gaussian", "gsac_decode_gaussian", "gsac_encode_gaussian_mixed", "gsac_decode_gaussian_mixed", "gsac_calculate_cdf_mixed", "gsac_encode_gaussian_slices", "gsac_decode_gaussian_slices", "gsac_encode_gaussian_mixed_slices", "gsac_decode_gaussian_mixed_slices", "gshac_mlp2", "gshac_mlp2_act", "gsge_forward", "gsge_forward_train", "gsge_backward", "gsr_visible_filter", "gsr_forward", "gsr_forward_train", "gsr_backward", "gsnn_generate", "gsnn_forward_train", "gsnn_backward",
     "gpcc_train_frame", "gpcc_train_frame_nodes", "gpcc_train_weights", "gpcc_train_conv", "gpcc_train_wgrad",
     "gpcc_knn", "gpcc_scatter_max", "gpcc_grow_voxels",
 ]
@@ -142,6 +142,9 @@ def lib():
     L.gsr_backward.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, f32, f32, vp, vp, GSR_ALLOC, vp,
                                vp, vp, vp, vp, vp, vp, vp, vp]
     L.gsnn_generate.argtypes = [vp, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), vp]
+    L.gsnn_forward_train.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, C.POINTER(vp),
+                                     C.POINTER(i64), vp]
+    L.gsnn_backward.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
     st = C.POINTER(C.c_uint64)
     L.gpcc_train_frame.argtypes = [vp, vp, i64, i32, GSR_ALLOC, vp, st, C.POINTER(i32), C.POINTER(i64), vp]
     L.gpcc_train_frame_nodes.argtypes = [vp, st, vp, vp, vp, vp, vp]

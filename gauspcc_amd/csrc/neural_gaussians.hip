@@ -1,4 +1,4 @@
-// neural_gaussians.hip -- generate_neural_gaussians (inference path) on gfx950: SURVEY.md 8(f) row 2.
+// neural_gaussians.hip -- generate_neural_gaussians on gfx950 (inference path; the training path at the end of the file): SURVEY.md 8(f) row 2.
 //
 // Reference: src/gs_compress/HAC/gaussian_renderer/__init__.py:25-172 (the same function in HAC-plus / TC-GS / CAT-3DGS):
 // per visible anchor the view direction and distance, the optional feature bank, three two-layer MLPs (opacity / colour /
@@ -32,6 +32,8 @@ struct NGArgs {
     float *nopa;                     // (n K)     neural opacity * mask
     float *dense;                    // (n K, 10) colour (3) | scale_rot (7)
     uint32_t *keep;                  // (n K)     neural opacity > 0
+    int mafter;                      // training path (TR): HAC++'s order -- keep = tanh > 0, the mask applied to the kept rows' opacity and scale
+    uint8_t *keep8;                  // training path (TR): the keep flags as bool (n K)
 };
 
 template <int F, int DIN>
@@ -57,7 +59,7 @@ __device__ __forceinline__ float out_unit(const float (&h)[F], const Mlp &m, int
     return a;
 }
 
-template <int F>
+template <int F, bool TR = false>
 __global__ __launch_bounds__(TB) void k_anchor_mlps(NGArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
@@ -91,9 +93,11 @@ __global__ __launch_bounds__(TB) void k_anchor_mlps(NGArgs a)
     // opacity: tanh head, times the binary grid mask; a Gaussian survives when the product is positive (:136-141)
     hidden_layer<F, DIN>(x, a.opacity, h);
     for (int j = 0; j < K; ++j) {
-        const float o = tanhf(out_unit<F>(h, a.opacity, j)) * a.mask[src * K + j];
+        const float t = tanhf(out_unit<F>(h, a.opacity, j));
+        const float o = TR && a.mafter ? t : t * a.mask[src * K + j];
         a.nopa[i * K + j] = o;
         a.keep[i * K + j] = o > 0.0f ? 1u : 0u;
+        if (TR) a.keep8[i * K + j] = o > 0.0f ? 1 : 0;
     }
     // colour: sigmoid head (:147-148)
     hidden_layer<F, DIN>(x, a.color, h);
@@ -113,8 +117,10 @@ struct AsmArgs {
     int64_t nk;
     int K;
     float *xyz, *color, *opacity, *scale, *rot;
+    const float *mask;               // TR with HAC++'s order: (n K) multiplies the kept rows' opacity and scale; otherwise null
 };
 
+template <bool TR = false>
 __global__ __launch_bounds__(TB) void k_assemble(AsmArgs a)
 {
     const int64_t g = (int64_t)blockIdx.x * TB + threadIdx.x;
@@ -123,11 +129,12 @@ __global__ __launch_bounds__(TB) void k_assemble(AsmArgs a)
     const int64_t gs = i * a.K + g % a.K;      // the candidate's row in the model's (n, K, 3) offsets
     const uint32_t p = a.pos[g];
     const float *d = a.dense + g * 10, *sc = a.scaling + i * 6;
-    a.opacity[p] = a.nopa[g];
+    const float mk = TR && a.mask ? a.mask[gs] : 1.0f;
+    a.opacity[p] = TR ? a.nopa[g] * mk : a.nopa[g];
     a.color[3 * p] = d[0]; a.color[3 * p + 1] = d[1]; a.color[3 * p + 2] = d[2];
     // scaling = scaling[3:] * sigmoid(scale_rot[:3]); rot = normalize(scale_rot[3:7]) (:166-168)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a.scale[3 * p + k] = sc[3 + k] * (1.0f / (1.0f + expf(-d[3 + k])));
+    for (int k = 0; k < 3; ++k) a.scale[3 * p + k] = TR ? sc[3 + k] * (1.0f / (1.0f + expf(-d[3 + k]))) * mk : sc[3 + k] * (1.0f / (1.0f + expf(-d[3 + k])));
     const float q0 = d[6], q1 = d[7], q2 = d[8], q3 = d[9];
     const float nrm = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);   // F.normalize: x / max(|x|, eps)
     a.rot[4 * p] = q0 / nrm; a.rot[4 * p + 1] = q1 / nrm; a.rot[4 * p + 2] = q2 / nrm; a.rot[4 * p + 3] = q3 / nrm;
@@ -365,7 +372,7 @@ __device__ __forceinline__ void ng_build_x(const NGArgs &a, const float (&cam)[3
     ng_wave_sync();
 }
 
-template <int F, bool ROWS>
+template <int F, bool ROWS, bool TR = false>
 __global__ __launch_bounds__(512) void k_ng_opacity(NGArgs a)
 {
     using M = NGM<F>;
@@ -407,9 +414,10 @@ __global__ __launch_bounds__(512) void k_ng_opacity(NGArgs a)
             for (int i = 0; i < 4; ++i) {
                 const int64_t row = row0 + 4 * g + i;
                 if (row < a.n) {
-                    const float o = tanhf(v[i]) * mk[i];
+                    const float o = TR && a.mafter ? tanhf(v[i]) : tanhf(v[i]) * mk[i];
                     a.nopa[row * a.K + e] = o;
                     a.keep[row * a.K + e] = o > 0.0f ? 1u : 0u;
+                    if (TR) a.keep8[row * a.K + e] = o > 0.0f ? 1 : 0;
                 }
             }
         }
@@ -428,7 +436,7 @@ struct EmitArgs {
 #ifndef NG_EMIT_LOADS_AT
 #define NG_EMIT_LOADS_AT 1
 #endif
-template <int F, bool ROWS, int NIT>
+template <int F, bool ROWS, int NIT, bool TR = false>
 __global__ __launch_bounds__(512) void k_ng_emit(NGArgs a, EmitArgs o)
 {
     using M = NGM<F>;
@@ -456,7 +464,7 @@ __global__ __launch_bounds__(512) void k_ng_emit(NGArgs a, EmitArgs o)
         int64_t gis[NIT], srcs[NIT];
         int rr[NIT], jj[NIT];
         uint32_t kf[NIT], pp[NIT];
-        float no[NIT];
+        float no[NIT], mm[NIT];
         float of[NIT][3];
         auto emission_loads = [&]() {
 #pragma unroll
@@ -474,6 +482,7 @@ __global__ __launch_bounds__(512) void k_ng_emit(NGArgs a, EmitArgs o)
             for (int it = 0; it < NIT; ++it) {
                 const int64_t gi = kp[it] ? gis[it] : 0;
                 kf[it] = keepp[gi]; pp[it] = posp[gi]; no[it] = nopap[gi];
+                mm[it] = TR && a.mafter ? a.mask[srcs[it] * K + (kp[it] ? jj[it] : 0)] : 1.0f;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) of[it][k] = offp[(srcs[it] * K + (kp[it] ? jj[it] : 0)) * 3 + k];
             }
@@ -522,10 +531,10 @@ __global__ __launch_bounds__(512) void k_ng_emit(NGArgs a, EmitArgs o)
                 if (kp[it]) {
                     const uint32_t p = pp[it];
                     const float *c3 = xs + rr[it] * PX + 3 * jj[it], *d = xs + rr[it] * PX + 3 * K + 7 * jj[it], *ar = aux + rr[it] * NG_AUX;
-                    oop[p] = no[it];
+                    oop[p] = TR ? no[it] * mm[it] : no[it];
                     ocol[3 * p] = c3[0]; ocol[3 * p + 1] = c3[1]; ocol[3 * p + 2] = c3[2];
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) osc[3 * p + k] = ar[6 + k] * (1.0f / (1.0f + expf(-d[k])));
+                    for (int k = 0; k < 3; ++k) osc[3 * p + k] = TR ? ar[6 + k] * (1.0f / (1.0f + expf(-d[k]))) * mm[it] : ar[6 + k] * (1.0f / (1.0f + expf(-d[k])));
                     const float q0 = d[3], q1 = d[4], q2 = d[5], q3 = d[6];
                     const float nrm = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
                     orot[4 * p] = q0 / nrm; orot[4 * p + 1] = q1 / nrm; orot[4 * p + 2] = q2 / nrm; orot[4 * p + 3] = q3 / nrm;
@@ -561,45 +570,45 @@ template <int F> static int ng_mfma_waves(bool bank, int K)
     return 0;
 }
 
-template <int F, bool ROWS>
+template <int F, bool ROWS, bool TR = false>
 static int ng_mfma_opacity(gpcc_ctx *ctx, const NGArgs &a, int waves, hipStream_t st)
 {
     const size_t lds = ng_lds_opacity<F>(a.bank.w1 != nullptr, waves);
     static PerDeviceOnce attr;
     GP_TRY(attr.run(ctx->device, [&]() -> int {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ng_opacity<F, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NG_LDS_MAX));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ng_opacity<F, ROWS, TR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NG_LDS_MAX));
         return GPCC_OK;
     }));
     const unsigned grid = (unsigned)std::min<int64_t>(256, cdiv(cdiv(a.n, 16), waves));
-    k_ng_opacity<F, ROWS><<<grid, 64 * waves, lds, st>>>(a);
+    k_ng_opacity<F, ROWS, TR><<<grid, 64 * waves, lds, st>>>(a);
     LAUNCH_CHECK();
     return GPCC_OK;
 }
 
-template <int F, bool ROWS, int NIT>
+template <int F, bool ROWS, int NIT, bool TR = false>
 static int ng_mfma_emit_n(gpcc_ctx *ctx, const NGArgs &a, EmitArgs o, int waves, hipStream_t st)
 {
     const size_t lds = ng_lds_emit<F>(a.bank.w1 != nullptr, a.K, waves);
     o.px = ng_emit_pitch<F>(a.K);
     static PerDeviceOnce attr;
     GP_TRY(attr.run(ctx->device, [&]() -> int {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ng_emit<F, ROWS, NIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NG_LDS_MAX));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ng_emit<F, ROWS, NIT, TR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NG_LDS_MAX));
         return GPCC_OK;
     }));
     const unsigned grid = (unsigned)std::min<int64_t>(256, cdiv(cdiv(a.n, 16), waves));
-    k_ng_emit<F, ROWS, NIT><<<grid, 64 * waves, lds, st>>>(a, o);
+    k_ng_emit<F, ROWS, NIT, TR><<<grid, 64 * waves, lds, st>>>(a, o);
     LAUNCH_CHECK();
     return GPCC_OK;
 }
 
-template <int F, bool ROWS>
+template <int F, bool ROWS, bool TR = false>
 static int ng_mfma_emit(gpcc_ctx *ctx, const NGArgs &a, const EmitArgs &o, int waves, hipStream_t st)
 {
     switch ((16 * a.K + 63) / 64) {
-    case 1: return ng_mfma_emit_n<F, ROWS, 1>(ctx, a, o, waves, st);
-    case 2: return ng_mfma_emit_n<F, ROWS, 2>(ctx, a, o, waves, st);
-    case 3: return ng_mfma_emit_n<F, ROWS, 3>(ctx, a, o, waves, st);
-    default: return ng_mfma_emit_n<F, ROWS, 4>(ctx, a, o, waves, st);
+    case 1: return ng_mfma_emit_n<F, ROWS, 1, TR>(ctx, a, o, waves, st);
+    case 2: return ng_mfma_emit_n<F, ROWS, 2, TR>(ctx, a, o, waves, st);
+    case 3: return ng_mfma_emit_n<F, ROWS, 3, TR>(ctx, a, o, waves, st);
+    default: return ng_mfma_emit_n<F, ROWS, 4, TR>(ctx, a, o, waves, st);
     }
 }
 
@@ -656,12 +665,482 @@ extern "C" int gsnn_generate(gpcc_ctx *ctx, int64_t n, const int32_t *rows, int 
         LAUNCH_CHECK();
         GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
         HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
-        AsmArgs b = {anchor, offsets, scaling, nopa, dense, rows, keep, pos, nk, n_offsets, xyz_out, color_out, opacity_out, scale_out, rot_out};
+        AsmArgs b = {anchor, offsets, scaling, nopa, dense, rows, keep, pos, nk, n_offsets, xyz_out, color_out, opacity_out, scale_out, rot_out, nullptr};
         k_assemble<<<(unsigned)cdiv(nk, TB), TB, 0, st>>>(b);
         LAUNCH_CHECK();
     }
     HIP_TRY(hipStreamSynchronize(st));
     GP_TRY(device_error_check(ctx));
     *count_out = (int64_t)*htotal;
+    return GPCC_OK;
+}
+
+
+// ==== training path: gsnn_forward_train / gsnn_backward ================================================================================
+// The forward is the inference launches above with TR set (the HAC++ order, the bool keep flags); the scan's positions land in memory of the
+// caller (the state the backward needs: keep of candidate g is pos[g + 1] != pos[g], its output row pos[g]).  Nothing of the MLPs is kept.
+//
+// The backward, three launches:
+//   k_ngb_anchor   one lane per anchor: x, the hidden layers and the head outputs recomputed (the inference lane kernel's loops), the kept
+//                  candidates' output gradients gathered through pos, dZ per head, dH = (dZ W2) * [h > 0], dX = sum dH W1, the bank and the
+//                  view / dist chain back to feat and anchor; the per-anchor input gradients written with plain stores.  Per anchor it also
+//                  writes the GEMM operands of the weight gradients, feature-major (column c of anchor i at c * np + i, np = n rounded up to
+//                  16, rows n .. np - 1 zero): x | 1, h | 1 and dZ, dH of every MLP.
+//   k_ngb_wgrad    dW = dA^T B over the anchors on the matrix pipe (v_mfma_f32_16x16x4_f32, exact fp32 products), the anchors the reduction
+//                  dimension: workgroup (r, s) owns the fixed contiguous anchor range r (its size depends on n only) and the 64-row output
+//                  strip s of one weight matrix, and writes one 64 x 64 partial.  The ones column of B gives the bias.
+//   k_ngb_wsum     the partials of a strip added in range order.
+// No float atomics: every sum has one order, so the gradients are bitwise reproducible across runs and streams.
+namespace {
+
+struct NGBArgs {
+    const float *anchor, *feat, *offsets, *scaling, *mask, *cam;   // (n,3) (n,F) (n,K,3) (n,6) (n,K) (3)
+    const uint32_t *pos;                                             // (n K + 1) from gsnn_forward_train
+    int64_t n, np;
+    int K, mafter;
+    Mlp bank, opacity, cov, color;
+    const float *g_xyz, *g_color, *g_opacity, *g_scale, *g_rot, *g_nopa;   // (m,3) (m,3) (m) (m,3) (m,4) (n K)
+    float *d_anchor, *d_feat, *d_offsets, *d_scaling, *d_mask;              // (n,3) (n,F) (n,K,3) (n,6) (n,K)
+    // GEMM operands, feature-major with pitch np
+    float *X, *Hop, *Hcol, *Hcov, *dHop, *dHcol, *dHcov, *dZop, *dZcol, *dZcov;   // X: F + 5 columns, H*: F + 1, dH*: F, dZ: K / 3K / 7K
+    float *Xb, *Hb, *dHb, *dZb;                                                     // bank: 5, F + 1, F, 3
+};
+
+template <int F>
+__device__ __forceinline__ void ngb_store_h(const NGBArgs &a, int64_t i, const float (&h)[F], const float (&dh)[F], float *H, float *dH)
+{
+#pragma unroll
+    for (int c = 0; c < F; ++c) { H[c * a.np + i] = h[c]; dH[c * a.np + i] = dh[c]; }
+    H[F * a.np + i] = 1.0f;
+}
+
+// dh = (dz W2) * [h > 0] has been accumulated; dx += dh W1
+template <int F, int DIN>
+__device__ __forceinline__ void ngb_dx(const Mlp &m, float (&dh)[F], const float (&h)[F], float (&dx)[DIN])
+{
+#pragma unroll
+    for (int c = 0; c < F; ++c) dh[c] = h[c] > 0.0f ? dh[c] : 0.0f;
+#pragma unroll 2
+    for (int c = 0; c < F; ++c) {
+        const float *w = m.w1 + c * DIN;
+#pragma unroll
+        for (int k = 0; k < DIN; ++k) dx[k] = __builtin_fmaf(dh[c], w[k], dx[k]);
+    }
+}
+
+template <int F>
+__device__ __forceinline__ void ngb_acc_dh(const Mlp &m, int j, float dz, float (&dh)[F])
+{
+    const float *w = m.w2 + j * F;
+#pragma unroll
+    for (int c = 0; c < F; ++c) dh[c] = __builtin_fmaf(dz, w[c], dh[c]);
+}
+
+template <int F>
+__global__ __launch_bounds__(TB) void k_ngb_anchor(NGBArgs a)
+{
+    constexpr int DIN = F + 4;
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= a.np) return;
+    const bool bank = a.bank.w1 != nullptr;
+    const int K = a.K;
+    if (i >= a.n) {   // padding rows of the GEMM operands: zero
+        for (int c = 0; c < DIN + 1; ++c) a.X[c * a.np + i] = 0.0f;
+        for (int c = 0; c < F + 1; ++c) { a.Hop[c * a.np + i] = 0.0f; a.Hcol[c * a.np + i] = 0.0f; a.Hcov[c * a.np + i] = 0.0f; }
+        for (int c = 0; c < F; ++c) { a.dHop[c * a.np + i] = 0.0f; a.dHcol[c * a.np + i] = 0.0f; a.dHcov[c * a.np + i] = 0.0f; }
+        for (int c = 0; c < K; ++c) a.dZop[c * a.np + i] = 0.0f;
+        for (int c = 0; c < 3 * K; ++c) a.dZcol[c * a.np + i] = 0.0f;
+        for (int c = 0; c < 7 * K; ++c) a.dZcov[c * a.np + i] = 0.0f;
+        if (bank) {
+            for (int c = 0; c < 5; ++c) a.Xb[c * a.np + i] = 0.0f;
+            for (int c = 0; c < F + 1; ++c) a.Hb[c * a.np + i] = 0.0f;
+            for (int c = 0; c < F; ++c) a.dHb[c * a.np + i] = 0.0f;
+            for (int c = 0; c < 3; ++c) a.dZb[c * a.np + i] = 0.0f;
+        }
+        return;
+    }
+    float x[DIN];
+    const float vx = a.anchor[3 * i] - a.cam[0], vy = a.anchor[3 * i + 1] - a.cam[1], vz = a.anchor[3 * i + 2] - a.cam[2];
+    const float dist = sqrtf(vx * vx + vy * vy + vz * vz);
+    x[F] = vx / dist; x[F + 1] = vy / dist; x[F + 2] = vz / dist; x[F + 3] = dist;
+#pragma unroll
+    for (int k = 0; k < F; ++k) x[k] = a.feat[i * F + k];
+    float bw[3] = {0.0f, 0.0f, 1.0f};
+    if (bank) {   // the forward's feature bank (k_anchor_mlps), its softmax weights kept
+        float hb[F];
+        const float cv[4] = {x[F], x[F + 1], x[F + 2], x[F + 3]};
+        hidden_layer<F, 4>(cv, a.bank, hb);
+        float z0 = out_unit<F>(hb, a.bank, 0), z1 = out_unit<F>(hb, a.bank, 1), z2 = out_unit<F>(hb, a.bank, 2);
+        const float zm = fmaxf(z0, fmaxf(z1, z2));
+        z0 = expf(z0 - zm); z1 = expf(z1 - zm); z2 = expf(z2 - zm);
+        const float zs = z0 + z1 + z2;
+        bw[0] = z0 / zs; bw[1] = z1 / zs; bw[2] = z2 / zs;
+        float y[F];
+#pragma unroll
+        for (int k = 0; k < F; ++k) y[k] = x[(k % (F / 4)) * 4] * bw[0] + x[(k % (F / 2)) * 2] * bw[1] + x[k] * bw[2];
+#pragma unroll
+        for (int k = 0; k < F; ++k) x[k] = y[k];
+    }
+#pragma unroll
+    for (int k = 0; k < DIN; ++k) a.X[k * a.np + i] = x[k];
+    a.X[DIN * a.np + i] = 1.0f;
+    float sc[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sc[k] = a.scaling[6 * i + k];
+    float da[3] = {0.0f, 0.0f, 0.0f}, dsc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    // xyz = anchor + offsets * scaling[:3]
+    for (int j = 0; j < K; ++j) {
+        const int64_t g = i * K + j;
+        const uint32_t p = a.pos[g];
+        const bool kp = a.pos[g + 1] != p;
+        float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+        if (kp) {
+            const float gx = a.g_xyz[3 * p], gy = a.g_xyz[3 * p + 1], gz = a.g_xyz[3 * p + 2];
+            const float *of = a.offsets + 3 * g;
+            d0 = gx * sc[0]; d1 = gy * sc[1]; d2 = gz * sc[2];
+            dsc[0] = __builtin_fmaf(gx, of[0], dsc[0]); dsc[1] = __builtin_fmaf(gy, of[1], dsc[1]); dsc[2] = __builtin_fmaf(gz, of[2], dsc[2]);
+            da[0] += gx; da[1] += gy; da[2] += gz;
+        }
+        a.d_offsets[3 * g] = d0; a.d_offsets[3 * g + 1] = d1; a.d_offsets[3 * g + 2] = d2;
+    }
+    float dx[DIN];
+#pragma unroll
+    for (int k = 0; k < DIN; ++k) dx[k] = 0.0f;
+    float h[F], dh[F];
+    // opacity head: HAC  neural_opacity = tanh(z) * mask, opacity = the kept neural_opacity
+    //               HAC++ neural_opacity = tanh(z),    opacity = the kept tanh(z) * mask
+    hidden_layer<F, DIN>(x, a.opacity, h);
+#pragma unroll
+    for (int c = 0; c < F; ++c) dh[c] = 0.0f;
+    for (int j = 0; j < K; ++j) {
+        const int64_t g = i * K + j;
+        const uint32_t p = a.pos[g];
+        const bool kp = a.pos[g + 1] != p;
+        const float t = tanhf(out_unit<F>(h, a.opacity, j)), m = a.mask[g];
+        const float gop = kp ? a.g_opacity[p] : 0.0f, gno = a.g_nopa[g];
+        float dz, dm;
+        if (a.mafter) { dz = (gno + gop * m) * (1.0f - t * t); dm = gop * t; }
+        else { const float dn = gno + gop; dz = dn * m * (1.0f - t * t); dm = dn * t; }
+        a.d_mask[g] = dm;
+        a.dZop[j * a.np + i] = dz;
+        ngb_acc_dh<F>(a.opacity, j, dz, dh);
+    }
+    ngb_dx<F, DIN>(a.opacity, dh, h, dx);
+    ngb_store_h<F>(a, i, h, dh, a.Hop, a.dHop);
+    // colour head: sigmoid
+    hidden_layer<F, DIN>(x, a.color, h);
+#pragma unroll
+    for (int c = 0; c < F; ++c) dh[c] = 0.0f;
+    for (int j = 0; j < 3 * K; ++j) {
+        const int64_t g = i * K + j / 3;
+        const uint32_t p = a.pos[g];
+        float dz = 0.0f;
+        if (a.pos[g + 1] != p) {
+            const float s = 1.0f / (1.0f + expf(-out_unit<F>(h, a.color, j)));
+            dz = a.g_color[3 * p + j % 3] * s * (1.0f - s);
+        }
+        a.dZcol[j * a.np + i] = dz;
+        ngb_acc_dh<F>(a.color, j, dz, dh);
+    }
+    ngb_dx<F, DIN>(a.color, dh, h, dx);
+    ngb_store_h<F>(a, i, h, dh, a.Hcol, a.dHcol);
+    // covariance head: scaling = scaling[3:] * sigmoid(z[:3]) (* mask, HAC++), rot = z[3:7] / max(|z[3:7]|, 1e-12)
+    hidden_layer<F, DIN>(x, a.cov, h);
+#pragma unroll
+    for (int c = 0; c < F; ++c) dh[c] = 0.0f;
+    for (int j = 0; j < K; ++j) {
+        const int64_t g = i * K + j;
+        const uint32_t p = a.pos[g];
+        float dz[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (a.pos[g + 1] != p) {
+            float z[7];
+#pragma unroll
+            for (int q = 0; q < 7; ++q) z[q] = out_unit<F>(h, a.cov, 7 * j + q);
+            const float mk = a.mafter ? a.mask[g] : 1.0f;
+            float dmk = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float s = 1.0f / (1.0f + expf(-z[k])), gs = a.g_scale[3 * p + k];
+                dz[k] = gs * sc[3 + k] * mk * s * (1.0f - s);
+                dsc[3 + k] = __builtin_fmaf(gs * s, mk, dsc[3 + k]);
+                dmk = __builtin_fmaf(gs * sc[3 + k], s, dmk);
+            }
+            if (a.mafter) a.d_mask[g] += dmk;
+            const float q0 = z[3], q1 = z[4], q2 = z[5], q3 = z[6];
+            const float nrm = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+            const float r0 = a.g_rot[4 * p], r1 = a.g_rot[4 * p + 1], r2 = a.g_rot[4 * p + 2], r3 = a.g_rot[4 * p + 3];
+            if (nrm >= 1e-12f) {   // d(q / |q|) = (g - r (r . g)) / |q|
+                const float u0 = q0 / nrm, u1 = q1 / nrm, u2 = q2 / nrm, u3 = q3 / nrm;
+                const float rg = u0 * r0 + u1 * r1 + u2 * r2 + u3 * r3;
+                dz[3] = (r0 - u0 * rg) / nrm; dz[4] = (r1 - u1 * rg) / nrm; dz[5] = (r2 - u2 * rg) / nrm; dz[6] = (r3 - u3 * rg) / nrm;
+            } else {               // the denominator is the clamp's eps: a constant
+                dz[3] = r0 / 1e-12f; dz[4] = r1 / 1e-12f; dz[5] = r2 / 1e-12f; dz[6] = r3 / 1e-12f;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+            a.dZcov[(7 * j + q) * a.np + i] = dz[q];
+            ngb_acc_dh<F>(a.cov, 7 * j + q, dz[q], dh);
+        }
+    }
+    ngb_dx<F, DIN>(a.cov, dh, h, dx);
+    ngb_store_h<F>(a, i, h, dh, a.Hcov, a.dHcov);
+    // dx -> feat (through the bank) and view / dist
+    float dview[4] = {dx[F], dx[F + 1], dx[F + 2], dx[F + 3]};
+    if (bank) {
+        float fr[F], df[F];
+#pragma unroll
+        for (int k = 0; k < F; ++k) { fr[k] = a.feat[i * F + k]; df[k] = 0.0f; }
+        float dw0 = 0.0f, dw1 = 0.0f, dw2 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < F; ++k) {
+            const int k0 = (k % (F / 4)) * 4, k1 = (k % (F / 2)) * 2;
+            dw0 = __builtin_fmaf(dx[k], fr[k0], dw0); dw1 = __builtin_fmaf(dx[k], fr[k1], dw1); dw2 = __builtin_fmaf(dx[k], fr[k], dw2);
+            df[k0] = __builtin_fmaf(dx[k], bw[0], df[k0]); df[k1] = __builtin_fmaf(dx[k], bw[1], df[k1]); df[k] = __builtin_fmaf(dx[k], bw[2], df[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < F; ++k) a.d_feat[i * F + k] = df[k];
+        // softmax: dz_s = w_s (dw_s - sum_t w_t dw_t)
+        const float sdw = bw[0] * dw0 + bw[1] * dw1 + bw[2] * dw2;
+        const float dzb[3] = {bw[0] * (dw0 - sdw), bw[1] * (dw1 - sdw), bw[2] * (dw2 - sdw)};
+        const float cv[4] = {x[F], x[F + 1], x[F + 2], x[F + 3]};
+        hidden_layer<F, 4>(cv, a.bank, h);
+#pragma unroll
+        for (int c = 0; c < F; ++c) dh[c] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) { a.dZb[s * a.np + i] = dzb[s]; ngb_acc_dh<F>(a.bank, s, dzb[s], dh); }
+        ngb_dx<F, 4>(a.bank, dh, h, dview);
+        ngb_store_h<F>(a, i, h, dh, a.Hb, a.dHb);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.Xb[k * a.np + i] = cv[k];
+        a.Xb[4 * a.np + i] = 1.0f;
+    } else {
+#pragma unroll
+        for (int k = 0; k < F; ++k) a.d_feat[i * F + k] = dx[k];
+    }
+    // view = v / |v|, dist = |v|, v = anchor - cam:  dv = (dview - view (view . dview)) / dist + ddist view
+    const float ux = x[F], uy = x[F + 1], uz = x[F + 2];
+    const float ud = ux * dview[0] + uy * dview[1] + uz * dview[2];
+    da[0] += (dview[0] - ux * ud) / dist + dview[3] * ux;
+    da[1] += (dview[1] - uy * ud) / dist + dview[3] * uy;
+    da[2] += (dview[2] - uz * ud) / dist + dview[3] * uz;
+    a.d_anchor[3 * i] = da[0]; a.d_anchor[3 * i + 1] = da[1]; a.d_anchor[3 * i + 2] = da[2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a.d_scaling[6 * i + k] = dsc[k];
+}
+
+// one 64-row output strip of a weight gradient: dW[m][c] = sum_r A[m][r] B[c][r] for m0 <= m < min(m0 + 64, M), c < N (the last column of B
+// is ones: c == N - 1 is the bias); dW[m][c] goes to w[m * (N - 1) + c], the bias to b[m]
+struct NGStrip { const float *A, *B; float *w, *b; int M, N, m0; };
+constexpr int NG_MAX_STRIPS = 16;
+struct NGWArgs { NGStrip s[NG_MAX_STRIPS]; int64_t np, chunk; int ranges; float *partial; };
+
+__global__ __launch_bounds__(64) void k_ngb_wgrad(NGWArgs a)
+{
+    const NGStrip s = a.s[blockIdx.y];
+    const int lane = threadIdx.x, e = lane & 15, g = lane >> 4;
+    const int64_t r0 = (int64_t)blockIdx.x * a.chunk, r1 = min(a.np, r0 + a.chunk);
+    const int nmt = min(4, (s.M - s.m0 + 15) / 16), nnt = (s.N + 15) / 16;
+    f32x4n acc[4][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4n{0.0f, 0.0f, 0.0f, 0.0f};
+    // lane (g, e) supplies anchors r + 4 g .. r + 4 g + 3 (one float4 per operand tile) at the four k-steps: A row m0 + 16 mt + e, B column 16 nt + e
+    for (int64_t r = r0; r < r1; r += 16) {
+        f32x4n av[4], bv[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int m = s.m0 + 16 * mt + e;
+            av[mt] = mt < nmt && m < s.M ? *reinterpret_cast<const f32x4n *>(s.A + m * a.np + r + 4 * g) : f32x4n{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int c = 16 * nt + e;
+            bv[nt] = nt < nnt && c < s.N ? *reinterpret_cast<const f32x4n *>(s.B + c * a.np + r + 4 * g) : f32x4n{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+                if (mt < nmt) {
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt)
+                        if (nt < nnt) NG_MF(acc[mt][nt], av[mt][kk], bv[nt][kk]);
+                }
+    }
+    float *out = a.partial + ((int64_t)blockIdx.y * a.ranges + blockIdx.x) * 4096;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out[(16 * mt + 4 * g + i) * 64 + 16 * nt + e] = acc[mt][nt][i];
+}
+
+__global__ __launch_bounds__(256) void k_ngb_wsum(NGWArgs a)
+{
+    const NGStrip s = a.s[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x, m = s.m0 + idx / 64, c = idx % 64;
+    if (m >= s.M || m >= s.m0 + 64 || c >= s.N) return;
+    const float *p = a.partial + (int64_t)blockIdx.y * a.ranges * 4096 + idx;
+    float v = 0.0f;
+    for (int r = 0; r < a.ranges; ++r) v += p[(int64_t)r * 4096];
+    if (c < s.N - 1) s.w[(int64_t)m * (s.N - 1) + c] = v;
+    else s.b[m] = v;
+}
+
+__global__ void k_ngb_zero(float *p, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0.0f;
+}
+
+int ngb_check(int64_t n, int feat_dim, int n_offsets, const float *const *mlp, int mlp_count)
+{
+    if (feat_dim != 32 && feat_dim != 50) return fail(GPCC_ERR_ARG, "neural_gaussians_train: feat_dim must be 32 or 50 (got %d)", feat_dim);
+    if (n_offsets < 1 || n_offsets > 64) return fail(GPCC_ERR_ARG, "neural_gaussians_train: bad n_offsets %d", n_offsets);
+    if (n < 0 || n * n_offsets >= ((int64_t)1 << 31)) return fail(GPCC_ERR_ARG, "neural_gaussians_train: too many Gaussians");
+    for (int q = 4; q < mlp_count; ++q)
+        if (!mlp[q]) return fail(GPCC_ERR_ARG, "null MLP tensor %d", q);
+    if (mlp[0] && feat_dim % 4) return fail(GPCC_ERR_ARG, "the feature bank needs feat_dim divisible by 4");
+    return GPCC_OK;
+}
+
+}  // namespace
+
+extern "C" int gsnn_forward_train(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
+                                  const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, int mask_after_opacity,
+                                  float *xyz_out, float *color_out, float *opacity_out, float *scale_out, float *rot_out, float *nopa_out, uint8_t *keep_out,
+                                  gsr_alloc_fn alloc, void *alloc_user, uint32_t **pos_out, int64_t *count_out, void *stream)
+{
+    if (!ctx || !mlp || !alloc || !pos_out || !count_out) return fail(GPCC_ERR_ARG, "null argument");
+    *count_out = 0;
+    *pos_out = nullptr;
+    GP_TRY(ngb_check(n, feat_dim, n_offsets, mlp, 16));
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nk = n * n_offsets;
+    uint32_t *pos = static_cast<uint32_t *>(alloc(alloc_user, (size_t)(nk + 1) * 4));
+    if (!pos) return fail(GPCC_ERR_NOMEM, "neural_gaussians_train: allocator returned NULL");
+    *pos_out = pos;
+    if (n == 0) { HIP_TRY(hipMemsetAsync(pos, 0, 4, st)); return GPCC_OK; }
+    if (!anchor || !feat || !offsets || !scaling || !mask || !cam_center || !xyz_out || !color_out || !opacity_out || !scale_out || !rot_out || !nopa_out ||
+        !keep_out)
+        return fail(GPCC_ERR_ARG, "null argument");
+    const int waves = feat_dim == 32 ? ng_mfma_waves<32>(mlp[0] != nullptr, n_offsets) : ng_mfma_waves<50>(mlp[0] != nullptr, n_offsets);
+    GP_TRY(ctx->arena.reserve((size_t)nk * (4 + (waves ? 0 : 40) + 8) + ((size_t)4 << 20)));
+    ctx->arena.reset();
+    TAKE(keep, uint32_t, nk);
+    NGArgs a = {};
+    a.anchor = anchor; a.feat = feat; a.offsets = offsets; a.scaling = scaling; a.mask = mask; a.rows = nullptr; a.n = n; a.K = n_offsets;
+    a.cam = cam_center;
+    a.bank = Mlp{mlp[0], mlp[1], mlp[2], mlp[3]};
+    a.opacity = Mlp{mlp[4], mlp[5], mlp[6], mlp[7]};
+    a.cov = Mlp{mlp[8], mlp[9], mlp[10], mlp[11]};
+    a.color = Mlp{mlp[12], mlp[13], mlp[14], mlp[15]};
+    a.nopa = nopa_out; a.keep = keep; a.mafter = mask_after_opacity != 0; a.keep8 = keep_out;
+    GP_TRY(ctx->hstage.reserve(64));
+    volatile uint32_t *htotal = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
+    *htotal = 0;
+    if (waves) {
+        if (feat_dim == 32) GP_TRY((ng_mfma_opacity<32, false, true>(ctx, a, waves, st))); else GP_TRY((ng_mfma_opacity<50, false, true>(ctx, a, waves, st)));
+        GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
+        HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
+        EmitArgs o = {offsets, scaling, pos, 0, xyz_out, color_out, opacity_out, scale_out, rot_out};
+        if (feat_dim == 32) GP_TRY((ng_mfma_emit<32, false, true>(ctx, a, o, waves, st))); else GP_TRY((ng_mfma_emit<50, false, true>(ctx, a, o, waves, st)));
+    } else {
+        TAKE(dense, float, nk * 10);
+        a.dense = dense;
+        if (feat_dim == 32) k_anchor_mlps<32, true><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(a);
+        else k_anchor_mlps<50, true><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(a);
+        LAUNCH_CHECK();
+        GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
+        HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
+        AsmArgs b = {anchor, offsets, scaling, nopa_out, dense, nullptr, keep, pos, nk, n_offsets, xyz_out, color_out, opacity_out, scale_out, rot_out,
+                     mask_after_opacity ? mask : nullptr};
+        k_assemble<true><<<(unsigned)cdiv(nk, TB), TB, 0, st>>>(b);
+        LAUNCH_CHECK();
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    GP_TRY(device_error_check(ctx));
+    *count_out = (int64_t)*htotal;
+    return GPCC_OK;
+}
+
+extern "C" int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
+                             const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, int mask_after_opacity,
+                             const uint32_t *pos, const float *g_xyz, const float *g_color, const float *g_opacity, const float *g_scale, const float *g_rot,
+                             const float *g_nopa, float *d_anchor, float *d_feat, float *d_offsets, float *d_scaling, float *d_mask, float *const *d_mlp,
+                             gsr_alloc_fn alloc, void *alloc_user, void *stream)
+{
+    if (!ctx || !mlp || !d_mlp || !alloc) return fail(GPCC_ERR_ARG, "null argument");
+    GP_TRY(ngb_check(n, feat_dim, n_offsets, mlp, 16));
+    const bool bank = mlp[0] != nullptr;
+    for (int q = bank ? 0 : 4; q < 16; ++q)
+        if (!d_mlp[q]) return fail(GPCC_ERR_ARG, "null MLP gradient %d", q);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int F = feat_dim, K = n_offsets;
+    if (n == 0) {   // no anchors: zero weight gradients
+        const int64_t sz[16] = {(int64_t)F * 4, F, 3 * (int64_t)F, 3, (int64_t)F * (F + 4), F, (int64_t)K * F, K, (int64_t)F * (F + 4), F, 7 * (int64_t)K * F, 7 * K,
+                                (int64_t)F * (F + 4), F, 3 * (int64_t)K * F, 3 * K};
+        for (int q = bank ? 0 : 4; q < 16; ++q) {
+            k_ngb_zero<<<(unsigned)cdiv(sz[q], 256), 256, 0, st>>>(d_mlp[q], sz[q]);
+            LAUNCH_CHECK();
+        }
+        return GPCC_OK;
+    }
+    if (!anchor || !feat || !offsets || !scaling || !mask || !cam_center || !pos || !g_nopa || !d_anchor || !d_feat || !d_offsets || !d_scaling || !d_mask)
+        return fail(GPCC_ERR_ARG, "null argument");
+    const int64_t np = (n + 15) / 16 * 16;
+    const int ncol = (F + 5) + 3 * (F + 1) + 3 * F + 11 * K + (bank ? 5 + (F + 1) + F + 3 : 0);
+    // anchor ranges of the weight-gradient pass: a function of n only
+    const int ranges = (int)std::min<int64_t>(256, cdiv(np, 2048));
+    const int64_t chunk = cdiv(cdiv(np, ranges), 16) * 16;
+    NGWArgs w = {};
+    w.np = np; w.chunk = chunk; w.ranges = ranges;
+    float *ws = static_cast<float *>(alloc(alloc_user, (size_t)ncol * np * 4 + (size_t)NG_MAX_STRIPS * ranges * 4096 * 4));
+    if (!ws) return fail(GPCC_ERR_NOMEM, "neural_gaussians_train: allocator returned NULL");
+    NGBArgs b = {};
+    b.anchor = anchor; b.feat = feat; b.offsets = offsets; b.scaling = scaling; b.mask = mask; b.cam = cam_center; b.pos = pos;
+    b.n = n; b.np = np; b.K = K; b.mafter = mask_after_opacity != 0;
+    b.bank = Mlp{mlp[0], mlp[1], mlp[2], mlp[3]};
+    b.opacity = Mlp{mlp[4], mlp[5], mlp[6], mlp[7]};
+    b.cov = Mlp{mlp[8], mlp[9], mlp[10], mlp[11]};
+    b.color = Mlp{mlp[12], mlp[13], mlp[14], mlp[15]};
+    b.g_xyz = g_xyz; b.g_color = g_color; b.g_opacity = g_opacity; b.g_scale = g_scale; b.g_rot = g_rot; b.g_nopa = g_nopa;
+    b.d_anchor = d_anchor; b.d_feat = d_feat; b.d_offsets = d_offsets; b.d_scaling = d_scaling; b.d_mask = d_mask;
+    float *q = ws;
+    auto take = [&](int cols) { float *p = q; q += (int64_t)cols * np; return p; };
+    b.X = take(F + 5);
+    b.Hop = take(F + 1); b.Hcol = take(F + 1); b.Hcov = take(F + 1);
+    b.dHop = take(F); b.dHcol = take(F); b.dHcov = take(F);
+    b.dZop = take(K); b.dZcol = take(3 * K); b.dZcov = take(7 * K);
+    if (bank) { b.Xb = take(5); b.Hb = take(F + 1); b.dHb = take(F); b.dZb = take(3); }
+    w.partial = q;
+    if (F == 32) k_ngb_anchor<32><<<(unsigned)cdiv(np, TB), TB, 0, st>>>(b);
+    else k_ngb_anchor<50><<<(unsigned)cdiv(np, TB), TB, 0, st>>>(b);
+    LAUNCH_CHECK();
+    // the strips: {A, B, w, b, M, N}; every M here is <= 448, N <= 55
+    int ns = 0;
+    auto strips = [&](const float *A, const float *B, float *wt, float *bs, int M, int N) {
+        for (int m0 = 0; m0 < M; m0 += 64) w.s[ns++] = NGStrip{A, B, wt, bs, M, N, m0};
+    };
+    // mlp / d_mlp order: bank, opacity, cov, colour; {w1, b1, w2, b2} each
+    strips(b.dHop, b.X, d_mlp[4], d_mlp[5], F, F + 5);
+    strips(b.dZop, b.Hop, d_mlp[6], d_mlp[7], K, F + 1);
+    strips(b.dHcov, b.X, d_mlp[8], d_mlp[9], F, F + 5);
+    strips(b.dZcov, b.Hcov, d_mlp[10], d_mlp[11], 7 * K, F + 1);
+    strips(b.dHcol, b.X, d_mlp[12], d_mlp[13], F, F + 5);
+    strips(b.dZcol, b.Hcol, d_mlp[14], d_mlp[15], 3 * K, F + 1);
+    if (bank) {
+        strips(b.dHb, b.Xb, d_mlp[0], d_mlp[1], F, 5);
+        strips(b.dZb, b.Hb, d_mlp[2], d_mlp[3], 3, F + 1);
+    }
+    k_ngb_wgrad<<<dim3((unsigned)ranges, (unsigned)ns), 64, 0, st>>>(w);
+    LAUNCH_CHECK();
+    k_ngb_wsum<<<dim3(16, (unsigned)ns), 256, 0, st>>>(w);
+    LAUNCH_CHECK();
     return GPCC_OK;
 }

@@ -8,8 +8,10 @@ test (:188-205) where HAC multiplies them into the opacity before it (:136-137) 
     from gauspcc_amd.neural_gaussians import generate_neural_gaussians
     xyz, color, opacity, scaling, rot, time_sub = generate_neural_gaussians(viewpoint_camera, pc, visible_mask)
 
-Inference only (`is_training=False`): the training branches add noise and rate terms and need autograd.  The model `pc`
-is used through the attributes the reference uses.  When `pc.decoded_version` is false the attributes are first quantised
+`is_training=True` serves HAC's training branch (:47-98 and the 11-tuple of :170): the gathers, the quantisation noise, the
+context model's rate terms on the 5 % chosen anchors (the model's own torch modules: they train too) and then the differentiable core
+neural_gaussians_train (gsnn_forward_train / gsnn_backward), which HAC++, TC-GS and CAT-3DGS callers can use after their own rate code.
+The model `pc` is used through the attributes the reference uses.  When `pc.decoded_version` is false the attributes are first quantised
 with the context model's step sizes exactly as the reference does (:103-114); everything after that -- view vectors,
 feature bank, the three MLPs, masking, assembly -- is ONE call into libgauspcc (gsnn_generate: two kernels and a scan
 instead of ~40 PyTorch kernels and an (n K, 22) concatenate / mask / split).  For a decoded model the visible anchors go in as an
@@ -19,6 +21,7 @@ import ctypes as C
 import time
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
 from .hac_codec import Q_FEAT, Q_OFFSETS, Q_SCALING, grid_mlp, ste_multistep
@@ -45,10 +48,14 @@ def _linears(seq):
     return [t.detach().float().contiguous() for t in (mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias)]
 
 
-@torch.no_grad()
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0):
     if is_training:
-        raise NotImplementedError("gauspcc_amd.generate_neural_gaussians is the inference path (RD evaluation); training needs autograd")
+        return _generate_training(viewpoint_camera, pc, visible_mask, step)
+    return _generate_inference(viewpoint_camera, pc, visible_mask)
+
+
+@torch.no_grad()
+def _generate_inference(viewpoint_camera, pc, visible_mask):
     time_sub = 0
     f32 = lambda t: t.detach().float().contiguous()
     dev = pc.get_anchor.device
@@ -95,3 +102,147 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
                                         opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), C.byref(m), runtime.stream_ptr(dev)))
     m = m.value
     return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m], time_sub
+
+
+# ---- training path ----------------------------------------------------------------------------------------------------------------------
+
+def _mlp_params(pc):
+    """The 16 parameters {w1, b1, w2, b2} of mlp_feature_bank (None x 4 without the bank), mlp_opacity, mlp_cov, mlp_color: the tensors
+    themselves, so that autograd delivers their gradients."""
+    def lin(seq):
+        mods = [m for m in seq if isinstance(m, torch.nn.Linear)]
+        if len(mods) != 2:
+            raise TypeError("expected nn.Sequential(Linear, ReLU, Linear, ...) as built in HAC/scene/gaussian_model.py:229-256")
+        return [mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias]
+    bank = lin(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
+    return bank + lin(pc.get_opacity_mlp) + lin(pc.get_cov_mlp) + lin(pc.get_color_mlp)
+
+
+def _alloc_cb(dev, keep):
+    def alloc(user, nbytes):
+        try:
+            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        except RuntimeError:
+            return None
+        keep.append(t)
+        return t.data_ptr()
+    return _lib.GSR_ALLOC(alloc)
+
+
+def _ptrs(ts):
+    return (C.c_void_p * 16)(*[None if t is None else t.data_ptr() for t in ts])
+
+
+class _NeuralGaussians(torch.autograd.Function):
+    """gsnn_forward_train / gsnn_backward.  The backward's state is the scan of the keep flags, (n K + 1) uint32 in a tensor on the autograd
+    context (through the library's allocator callback): the hidden layers are recomputed, so other library calls may run in between."""
+
+    @staticmethod
+    def forward(ctx, mask_after, anchor, feat, grid_offsets, grid_scaling, masks, cam, *params):
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        dev = anchor.device
+        n, F = feat.shape
+        K = grid_offsets.shape[1]
+        ins = [f32(anchor), f32(feat), f32(grid_offsets), f32(grid_scaling), f32(masks).view(n, K), f32(cam).view(3)]
+        ws = [None if p is None else f32(p) for p in params]
+        nk = n * K
+        xyz, color, scaling = (torch.empty(nk, 3, device=dev) for _ in range(3))
+        opacity, rot = torch.empty(nk, 1, device=dev), torch.empty(nk, 4, device=dev)
+        nopa = torch.empty(nk, 1, device=dev)
+        keep = torch.empty(nk, dtype=torch.bool, device=dev)
+        bufs = []
+        cb = _alloc_cb(dev, bufs)
+        pos, m = C.c_void_p(), C.c_int64()
+        wp = _ptrs(ws)
+        _lib.check(_lib.lib().gsnn_forward_train(runtime.context(dev), n, F, K, *[t.data_ptr() for t in ins], wp, int(bool(mask_after)), xyz.data_ptr(),
+                                                 color.data_ptr(), opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), nopa.data_ptr(), keep.data_ptr(),
+                                                 cb, None, C.byref(pos), C.byref(m), runtime.stream_ptr(dev)))
+        m = m.value
+        ctx.state = (bufs, pos.value, bool(mask_after), n, F, K, masks.shape, grid_offsets.shape)
+        ctx.save_for_backward(*ins, *ws)
+        ctx.mark_non_differentiable(keep)
+        return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m], nopa, keep
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_xyz, g_color, g_opacity, g_scaling, g_rot, g_nopa, g_keep):
+        bufs, pos, mask_after, n, F, K, mshape, oshape = ctx.state
+        saved = ctx.saved_tensors
+        ins, ws = saved[:6], list(saved[6:])
+        dev = ins[0].device
+        f32 = lambda t: t.to(torch.float32).contiguous()
+        gs = [f32(g) for g in (g_xyz, g_color, g_opacity, g_scaling, g_rot, g_nopa)]
+        d_anchor, d_feat = torch.empty(n, 3, device=dev), torch.empty(n, F, device=dev)
+        d_off, d_sc, d_mask = torch.empty(n, K, 3, device=dev), torch.empty(n, 6, device=dev), torch.empty(n, K, device=dev)
+        d_ws = [None if w is None else torch.empty_like(w) for w in ws]
+        work = []
+        cb = _alloc_cb(dev, work)
+        _lib.check(_lib.lib().gsnn_backward(runtime.context(dev), n, F, K, *[t.data_ptr() for t in ins], _ptrs(ws), int(mask_after), pos,
+                                            *[g.data_ptr() for g in gs], d_anchor.data_ptr(), d_feat.data_ptr(), d_off.data_ptr(), d_sc.data_ptr(),
+                                            d_mask.data_ptr(), _ptrs(d_ws), cb, None, runtime.stream_ptr(dev)))
+        return (None, d_anchor, d_feat, d_off.view(oshape), d_sc, d_mask.view(mshape), None, *d_ws)
+
+
+def neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, masks, cam_center, pc, mask_after_opacity=False):
+    """The differentiable core of the training branch: anchors (n, 3), feat (n, F), grid_offsets (n, K, 3), grid_scaling (n, 6) and
+    masks (n, K, 1) -- used as given, the straight-through value included -- to the kept Gaussians.  Returns (xyz, color, opacity, scaling,
+    rot, neural_opacity (n K, 1), keep (n K) bool).  mask_after_opacity=False: HAC (:134-141, the mask in the opacity before the test);
+    True: HAC++ (HAC-plus/gaussian_renderer/__init__.py:158-203: keep = tanh > 0, the mask multiplies the kept rows' opacity and scaling).
+    Gradients reach the five attribute tensors and every Linear of the three or four MLPs; camera centre and keep get none."""
+    F, K = feat.shape[1], grid_offsets.shape[1]
+    if F not in (32, 50) or not 1 <= K <= 64:
+        raise _lib.GpccError(-1, f"neural_gaussians_train: feat_dim must be 32 or 50 and n_offsets 1..64 (got {F}, {K})")
+    cam = cam_center.reshape(3)
+    return _NeuralGaussians.apply(bool(mask_after_opacity), anchor, feat, grid_offsets, grid_scaling, masks, cam, *_mlp_params(pc))
+
+
+def _generate_training(viewpoint_camera, pc, visible_mask, step):
+    """HAC's training branch (:25-98, 170): noise, rate terms, then the core.  The random draws are the reference's, in its order, with its
+    shapes, dtypes and devices, so that under one torch.manual_seed the noise and the chosen anchors are the reference's."""
+    F, K = pc.feat_dim, pc.n_offsets
+    out_cols = [m for m in pc.get_grid_mlp if isinstance(m, torch.nn.Linear)][-1].out_features
+    if out_cols != 2 * F + 12 + 6 * K + 3:
+        raise NotImplementedError("generate_neural_gaussians(is_training=True) serves HAC's rate branch (nine-way mlp_grid split); for HAC++ call "
+                                  "gauspcc_amd.neural_gaussians.neural_gaussians_train(..., mask_after_opacity=True) after the model's own rate code")
+    if visible_mask is None:
+        visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
+    anchor = pc.get_anchor[visible_mask]
+    feat = pc._anchor_feat[visible_mask]
+    grid_offsets = pc._offset[visible_mask]
+    grid_scaling = pc.get_scaling[visible_mask]
+    binary_grid_masks = pc.get_mask[visible_mask]
+    mask_anchor = pc.get_mask_anchor[visible_mask]
+    mask_anchor_bool = mask_anchor.to(torch.bool)
+    mask_anchor_rate = (mask_anchor.sum() / mask_anchor.numel()).detach()
+    bit_per_param = bit_per_feat_param = bit_per_scaling_param = bit_per_offsets_param = None
+    Q_feat, Q_scaling, Q_offsets = 1, 0.001, 0.2
+    if 3000 < step <= 10000:
+        feat = feat + torch.empty_like(feat).uniform_(-0.5, 0.5) * Q_feat
+        grid_scaling = grid_scaling + torch.empty_like(grid_scaling).uniform_(-0.5, 0.5) * Q_scaling
+        grid_offsets = grid_offsets + torch.empty_like(grid_offsets).uniform_(-0.5, 0.5) * Q_offsets
+    if step == 10000:
+        pc.update_anchor_bound()
+    if step > 10000:
+        ctxf = pc.get_grid_mlp(pc.calc_interp_feat(anchor))
+        mean, scale, mean_scaling, scale_scaling, mean_offsets, scale_offsets, qf, qs, qo = torch.split(ctxf, [F, F, 6, 6, 3 * K, 3 * K, 1, 1, 1], dim=-1)
+        Q_feat = Q_feat * (1 + torch.tanh(qf))
+        Q_scaling = Q_scaling * (1 + torch.tanh(qs))
+        Q_offsets = Q_offsets * (1 + torch.tanh(qo))
+        feat = feat + torch.empty_like(feat).uniform_(-0.5, 0.5) * Q_feat
+        grid_scaling = grid_scaling + torch.empty_like(grid_scaling).uniform_(-0.5, 0.5) * Q_scaling
+        grid_offsets = grid_offsets + torch.empty_like(grid_offsets).uniform_(-0.5, 0.5) * Q_offsets.unsqueeze(1)
+        choose = (torch.rand_like(anchor[:, 0]) <= 0.05) & mask_anchor_bool
+        masks_chosen = binary_grid_masks[choose].repeat(1, 1, 3).view(-1, 3 * K)
+        bit_feat = pc.entropy_gaussian.forward(feat[choose], mean[choose], scale[choose], Q_feat[choose], pc._anchor_feat.mean())
+        bit_scaling = pc.entropy_gaussian.forward(grid_scaling[choose], mean_scaling[choose], scale_scaling[choose], Q_scaling[choose], pc.get_scaling.mean())
+        bit_offsets = pc.entropy_gaussian.forward(grid_offsets[choose].view(-1, 3 * K), mean_offsets[choose], scale_offsets[choose], Q_offsets[choose],
+                                                  pc._offset.mean())
+        bit_offsets = bit_offsets * masks_chosen
+        bit_per_feat_param = torch.sum(bit_feat) / bit_feat.numel() * mask_anchor_rate
+        bit_per_scaling_param = torch.sum(bit_scaling) / bit_scaling.numel() * mask_anchor_rate
+        bit_per_offsets_param = torch.sum(bit_offsets) / bit_offsets.numel() * mask_anchor_rate
+        bit_per_param = ((torch.sum(bit_feat) + torch.sum(bit_scaling) + torch.sum(bit_offsets))
+                         / (bit_feat.numel() + bit_scaling.numel() + bit_offsets.numel()) * mask_anchor_rate)
+    xyz, color, opacity, scaling, rot, neural_opacity, keep = neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, binary_grid_masks,
+                                                                                     viewpoint_camera.camera_center, pc)
+    return xyz, color, opacity, scaling, rot, neural_opacity, keep, bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param

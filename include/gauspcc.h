@@ -425,6 +425,29 @@ GPCC_API int gsnn_generate(gpcc_ctx *ctx, int64_t n, const int32_t *rows, int fe
                            const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, float *xyz_out,
                            float *color_out, float *opacity_out, float *scale_out, float *rot_out, int64_t *count_out, void *stream);
 
+/* ================= generate_neural_gaussians, training path =================
+ * The same Gaussians as gsnn_generate for the n anchors of the call (no row list: the caller gathers), plus what training needs:
+ * nopa_out (n K) the neural opacity and keep_out (n K) bool.  mask (n, K) is used as given (HAC's straight-through value (b - s) + s is
+ * only nearly {0, 1}).  mask_after_opacity = 0: HAC -- neural_opacity = tanh(z) * mask, keep = neural_opacity > 0, opacity = the kept
+ * neural_opacity.  mask_after_opacity = 1: HAC++ -- neural_opacity = tanh(z), keep = tanh(z) > 0, and the mask multiplies the kept rows'
+ * opacity and scaling.  The state the backward needs is the exclusive scan of keep, (n K + 1) uint32 in memory from `alloc` (one call),
+ * returned in *pos_out and handed to gsnn_backward unchanged; other library calls may run in between.  Synchronises on the survivor count. */
+GPCC_API int gsnn_forward_train(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
+                                const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, int mask_after_opacity,
+                                float *xyz_out, float *color_out, float *opacity_out, float *scale_out, float *rot_out, float *nopa_out, uint8_t *keep_out,
+                                gsr_alloc_fn alloc, void *alloc_user, uint32_t **pos_out, int64_t *count_out, void *stream);
+/* Gradients of a loss given the output gradients g_xyz (m, 3), g_color (m, 3), g_opacity (m), g_scale (m, 3), g_rot (m, 4) of the m kept
+ * Gaussians and g_nopa (n K) of neural_opacity.  OVERWRITES d_anchor (n, 3), d_feat (n, F), d_offsets (n, K, 3), d_scaling (n, 6),
+ * d_mask (n, K) and the 16 MLP gradients d_mlp (the layout of mlp; the bank's four are not written when mlp[0] is NULL).  The hidden
+ * layers are recomputed; the weight gradients are fixed-order sums over fixed anchor ranges (no float atomics): bitwise reproducible.
+ * alloc is called once for the workspace (about (4 F + 11 K + 10) floats per anchor, the bank's 2 F + 9 more), which the call no longer
+ * needs once its kernels have run.  Enqueued on `stream` without synchronising. */
+GPCC_API int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
+                           const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, int mask_after_opacity,
+                           const uint32_t *pos, const float *g_xyz, const float *g_color, const float *g_opacity, const float *g_scale, const float *g_rot,
+                           const float *g_nopa, float *d_anchor, float *d_feat, float *d_offsets, float *d_scaling, float *d_mask, float *const *d_mlp,
+                           gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 /* ================= Gaussian splat rasteriser, forward (a20) =================
  * diff_gaussian_rasterization (Scaffold-GS fork; zip missing from the reference tree).  Mirrors the C++ API the
  * reference's viewer calls: CudaRasterizer::Rasterizer::visible_filter / ::forward,
