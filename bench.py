@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's metric on its configs[1]: Mpoints/s for GausPcgc
 encode + decode of a 1M-anchor synthetic cloud on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one scene: gpcc_encode (points resident in
@@ -15,6 +15,10 @@ from the in-repo counter-based generator -- "data": "synthetic".
 One JSON line on stdout (rank 0).  Besides the contract keys it carries
   roofline      the dominant kernel (k_sparse_conv, fp32 MFMA) timed live with HIP
                 events on its own stream inside libgauspcc (gpcc_profile_*)
+That is all a plain run does: set up, warm up, time the steps, write --dump-outputs,
+print the line.  --full adds the untimed passes behind the timed region, whose keys
+are null, empty or absent otherwise: bytes_v0, roofline.stages, scenes_in_flight,
+sizes, batched, reference_layout, low_rate, chunk_sweep, side_paths and
   cpu_baseline  the oracle (CPU restatement of the reference algorithm) on a bounded sample
 """
 import argparse
@@ -115,6 +119,9 @@ def main():
                     "(K scenes through one chain of launches: gpcc_encode_batch / gpcc_decode_batch)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned to its caller -- every scene's "
                     "container bytes and decoded points -- as DIR/scene<i>_<name>.npy (float32 / float64, at most 64 MB in all: a seeded sample of rows beyond that)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every untimed pass behind them (bytes_v0, roofline.stages, "
+                    "scenes_in_flight, sizes, batched, reference_layout, low_rate, chunk_sweep, side_paths, cpu_baseline); the --skip-* / --cpu-* / "
+                    "--side-anchors / --scenes-in-flight options shape those passes.  Off: the line carries the headline and the timed steps' own figures only")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)   # tests/test_dist_cpu.py: the N > 1 launch path on gloo, no GPU
     ap.add_argument("--selftest-scenes", type=int, default=0, help=argparse.SUPPRESS)     # (selftest) scenes of the batch in all; 0 = scenes_per_gpu x ranks
     ap.add_argument("--selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)  # (selftest) this rank exits before the rendezvous
@@ -236,7 +243,7 @@ def main():
     # size of the same cloud in the reference's container layout (one coder stream per level and stage, chunk_log2 = 0):
     # what the chunked default costs in bytes, outside the timed region
     bytes_v0 = None
-    if args.chunk_log2 and rank == 0 and not args.skip_v0:
+    if args.full and args.chunk_log2 and rank == 0 and not args.skip_v0:
         v0, _ = _encode_view(x, model, 0, 1)
         bytes_v0 = len(v0)
         data, st = _encode_view(x, model, args.chunk_log2, 1)   # the view above shares the context's buffer: restore `data`
@@ -244,7 +251,7 @@ def main():
     # HBM-bound stages (SURVEY 8d "which roofline"): one more encode + decode with every stage bracketed by HIP events on the
     # stream it runs on (gpcc_profile_enable(ctx, 2)) -- behind the timed region, because the brackets cost stream time
     stages = []
-    if rank == 0 and not args.skip_stages:
+    if args.full and rank == 0 and not args.skip_stages:
         _lib.check(L.gpcc_profile_enable(ctx, 2))
         d2, _ = _encode_view(x, model, args.chunk_log2, 1)
         _decode_bytes(d2, model, device)
@@ -267,7 +274,7 @@ def main():
     # stream and host thread -- what one scene leaves idle (launch tails, the range decoder's serial stretches, the small
     # levels) another fills.  Behind the timed region; per-scene latency grows.
     inflight = None
-    if rank == 0 and world == 1 and args.scenes_in_flight > 1:
+    if args.full and rank == 0 and world == 1 and args.scenes_in_flight > 1:
         import threading
 
         S = args.scenes_in_flight
@@ -333,7 +340,7 @@ def main():
     # batched: K scenes through ONE chain of launches (gpcc_encode_batch / gpcc_decode_batch, csrc/forest.hpp; BASELINE configs[3] is a
     #          batched encode): Mpoints/s over all K scenes, launches per call, every scene's bytes compared with its solo encode.
     sizes, batched = None, None
-    if rank == 0 and world == 1 and not args.skip_sizes:
+    if args.full and rank == 0 and world == 1 and not args.skip_sizes:
         from gauspcc_amd.pcc_utils import _decode_batch, _encode_batch
 
         def timed(fn, reps):
@@ -390,7 +397,7 @@ def main():
     # spatial context, i.e. a trained checkpoint), (ii) a SOLID cloud (synth.solid_cloud) under its own peaky model: 2.5 bits per coded node,
     # the range coder's low-entropy regime.  chunk_overhead_frac is measured (chunked bytes against chunk_log2 = 0 bytes), not extrapolated.
     reference_layout, low_rate, chunk_sweep = None, None, None
-    if rank == 0 and world == 1 and not args.skip_sizes and args.chunk_log2:
+    if args.full and rank == 0 and world == 1 and not args.skip_sizes and args.chunk_log2:
         from gauspcc_amd.synth import peaky_state_dict, solid_cloud, stage_symbol_frequencies
 
         def timed2(fn, reps):
@@ -576,7 +583,7 @@ def main():
                 "frac_all_levels": round((conv_flops + 2.0 * 32 * 32 * prof.fused_pair_jobs) / max((prof.conv_ms + prof.fused_ms) * 1e-3, 1e-9) / 1e12 / 157.3, 4),
             },
         }
-        if args.side_anchors > 0 and world == 1:
+        if args.full and args.side_anchors > 0 and world == 1:
             # the callers either side of the path, measured behind the timed region on a synthetic
             # scene: seconds / ms / symbol rates as observed in THIS run (tools/bench_side_paths.py holds the harness)
             import importlib.util
@@ -598,7 +605,7 @@ def main():
                 "rd_loop": {k: sp["rd_loop"][k] for k in ("gaussians", "generate_neural_gaussians_ms", "generate_plus_rasterise_ms", "psnr_decoded_vs_encoder_side_dB")},
                 "torchac_shim": sp["torchac_shim"],
             }
-        if args.cpu_sample > 0 and world == 1:   # the CPU baseline is a rank-0, N = 1 figure
+        if args.full and args.cpu_sample > 0 and world == 1:   # the CPU baseline is a rank-0, N = 1 figure
             from gauspcc_amd.model import tensor_table
             from oracle import oracle as orc
 

@@ -1,8 +1,8 @@
-"""bench.py end to end on the GPU box, at a reduced point count: the ONE JSON line the driver parses carries the contract keys, the
-`roofline` and `cpu_baseline` objects, and every untimed pass behind the timed region ran (sizes, batched, reference_layout, low_rate,
-chunk_sweep, scenes_in_flight, side_paths) -- a pass that raises takes the whole line with it, and nothing else in the suite runs the
-script as the driver does.  (Round 6: a function-local `import tempfile` in tools/bench_side_paths.py shadowed the module's and broke
-exactly this path; no test saw it.)"""
+"""bench.py end to end on the GPU box, at a reduced point count: the ONE JSON line the driver parses carries the contract keys and
+the `roofline` object; with --full also the `cpu_baseline` object, and every untimed pass behind the timed region ran (sizes, batched,
+reference_layout, low_rate, chunk_sweep, scenes_in_flight, side_paths) -- a pass that raises takes the whole line with it, and nothing
+else in the suite runs the script as the driver does.  (Round 6: a function-local `import tempfile` in tools/bench_side_paths.py
+shadowed the module's and broke exactly this path; no test saw it.)  A plain run (no --full) runs none of those passes."""
 import json
 import os
 import subprocess
@@ -21,7 +21,7 @@ def test_bench_prints_one_complete_json_line(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--points", "100000", "--steps", "3", "--warmup", "1", "--cpu-sample", "20000",
-                        "--side-anchors", "20000", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
+                        "--side-anchors", "20000", "--dump-outputs", str(tmp_path / "out"), "--full"], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]               # stdout carries the one JSON line only
@@ -74,3 +74,36 @@ def test_bench_prints_one_complete_json_line(tmp_path):
     assert np.array_equal(gh.decode(model, data)[0].astype(np.float64), pts)
     ref = cloud.astype(np.float64)
     assert np.array_equal(pts[np.lexsort(pts.T[::-1])], ref[np.lexsort(ref.T[::-1])])
+
+
+def test_plain_bench_runs_only_the_timed_steps(tmp_path):
+    """Without --full: the same contract keys and the timed steps' own roofline, none of the untimed passes, and --dump-outputs still
+    writes the last timed step's containers and points."""
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need an MI355X")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--points", "100000", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["unit"] == "Mpoints/s" and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 100000 * 3 / (d["ms_per_step"] * 3e-3) / 1e6) < 0.02 * d["value"]
+    assert d["roundtrip_bit_identical"] is True
+    rf = d["roofline"]
+    assert rf["launches"] > 0 and 0 < rf["frac"] < 1 and rf["stages"] == []
+    for key in ("bytes_v0", "scenes_in_flight", "sizes", "batched", "reference_layout", "low_rate", "chunk_sweep"):
+        assert d[key] is None, key
+    assert "side_paths" not in d and "cpu_baseline" not in d
+    assert "Start encoding" not in r.stderr                 # the side-path callers never ran
+    assert sorted(os.listdir(tmp_path / "out")) == ["scene0_container_bytes.npy", "scene0_decoded_points.npy"]
+    import numpy as np
+
+    assert len(np.load(tmp_path / "out" / "scene0_container_bytes.npy")) == d["container_bytes"]
+    assert np.load(tmp_path / "out" / "scene0_decoded_points.npy").shape == (100000, 3)

@@ -18,8 +18,8 @@ cp "$OUT/pmc2/summary.txt" "$OUT/${R}_pmc_conv_counters.txt"; rm -rf "$OUT/pmc2"
 timeout -k 10 600 python3 bench.py $QUIET > "$OUT/bench_quiet.json" 2> /dev/null
 python3 tools/make_pmc_json.py "$OUT/${R}_pmc_conv_fetch_write.txt" "$OUT/${R}_pmc_conv.json" "$OUT/${R}_pmc_conv_counters.txt" "$OUT/bench_quiet.json" > /dev/null
 cp "$OUT/${R}_pmc_conv.json" profiles/${R}_pmc_conv.json
-# 2. the bench line (default flags) and the same command under the kernel tracer
-timeout -k 10 600 python3 bench.py > "$OUT/${R}_bench.json" 2> "$OUT/bench.err"
+# 2. the bench line with every untimed pass (--full) and the timed steps alone under the kernel tracer
+timeout -k 10 600 python3 bench.py --full > "$OUT/${R}_bench.json" 2> "$OUT/bench.err"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/t" -o tr -- python3 bench.py --steps 5 --warmup 1 $QUIET > "$OUT/bench_traced.log" 2>&1
 cp $(find "$OUT/t" -name "*kernel_stats.csv" | head -1) "$OUT/${R}_kernel_stats.csv"
 f=$(find "$OUT/t" -name "*kernel_trace.csv" | head -1)
