@@ -569,6 +569,28 @@ GPCC_API int gpcc_grow_voxels(gpcc_ctx *ctx, const float *xyz_dev, int64_t m, co
                               int64_t c, const float *anchors_dev, int64_t n, float inv, float size, int64_t *count_out, gsr_alloc_fn alloc,
                               void *alloc_user, void *stream);
 
+/* ================= Photometric loss (training step, HAC/utils/loss_utils.py: ssim, l1_loss; train.py's loss) =================
+ * img1, img2 (batch, channels, height, width) float32 device, contiguous.  SSIM of every plane with the reference's window: the outer
+ * product of taps (window_size float32 HOST values: the caller builds them as the reference does, Gaussian taps of sigma 1.5 normalised
+ * by torch's float32 sum -- in flat bright regions sigma^2 = E - mu^2 turns an ulp of that sum into a visible bias), zero padding
+ * window_size / 2; window_size odd in [1, 31] (GPCC_ERR_ARG otherwise: an even window gives the reference an (H+1) x (W+1) map).  Per pixel, in float32 with sigma^2 = E - mu^2:
+ * S = (2 mu1 mu2 + C1)(2 sigma12 + C2) / ((mu1^2 + mu2^2 + C1)(sigma1^2 + sigma2^2 + C2)), C1 = 0.01^2, C2 = 0.03^2.
+ * gsr_ssim_forward: ssim_out[0] = the mean of S (size_average) or ssim_out[b] = the mean over item b (batch values).  With size_average,
+ * l1_out (may be NULL) = mean |img1 - img2| and loss_out (may be NULL; needs l1_out) = (float)(1 - lambda_dssim) l1 + (float)lambda_dssim (1 - ssim) in float32.
+ * Sums are per-tile doubles added in a fixed order (no atomics): bitwise reproducible.  nmaps = 0: nothing else is written; 3 or 4:
+ * maps (nmaps, batch, channels, height, width) receives dS/dmu1, dS/dE[x^2] (= dS/dE[y^2]), dS/dE[xy] and, for nmaps = 4, dS/dmu2, what
+ * gsr_ssim_backward reads.  alloc is called once for 16 bytes per 32 x 32 tile of every plane, not needed once the kernels have run.
+ * gsr_ssim_backward: the same images, window, taps and maps; the upstream gradients are device values: grad_ssim (1 value, or batch values
+ * without size_average) and grad_l1 (1 value, or NULL: no L1 term).  dL/dS(p) = ssim_scale grad_ssim[b] / n, dL/d|x - y|(p) = l1_scale
+ * grad_l1[0] / N (n = the pixels the mean of item b runs over, N = all).  Writes grad_img1 (needs nmaps >= 3) and grad_img2 (needs nmaps = 4),
+ * each may be NULL; sign(0) = 0.  Both calls are enqueued on `stream` without synchronising. */
+GPCC_API int gsr_ssim_forward(gpcc_ctx *ctx, const float *img1, const float *img2, int64_t batch, int64_t channels, int64_t height, int64_t width,
+                              int window_size, const float *taps, int size_average, float *ssim_out, float *l1_out, float *loss_out, double lambda_dssim,
+                              float *maps, int nmaps, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+GPCC_API int gsr_ssim_backward(gpcc_ctx *ctx, const float *img1, const float *img2, int64_t batch, int64_t channels, int64_t height, int64_t width,
+                               int window_size, const float *taps, int size_average, const float *maps, int nmaps, const float *grad_ssim, float ssim_scale,
+                               const float *grad_l1, float l1_scale, float *grad_img1, float *grad_img2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
