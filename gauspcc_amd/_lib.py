@@ -54,6 +54,7 @@ EXPORTS = [
     "gpcc_train_frame", "gpcc_train_frame_nodes", "gpcc_train_weights", "gpcc_train_conv", "gpcc_train_wgrad",
     "gpcc_knn", "gpcc_scatter_max", "gpcc_grow_voxels",
     "gsr_ssim_forward", "gsr_ssim_backward",
+    "gsac_rate_forward", "gsac_rate_backward",
 ]
 
 
@@ -157,6 +158,9 @@ def lib():
     L.gpcc_grow_voxels.argtypes = [vp, vp, i64, vp, vp, i64, i64, vp, i64, f32, f32, C.POINTER(i64), GSR_ALLOC, vp, vp]
     L.gsr_ssim_forward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, fp, i32, vp, vp, vp, C.c_double, vp, i32, GSR_ALLOC, vp, vp]
     L.gsr_ssim_backward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, fp, i32, vp, i32, vp, f32, vp, f32, vp, vp, vp]
+    pp, ip, f64 = C.POINTER(vp), C.POINTER(i32), C.c_double
+    L.gsac_rate_forward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp]
+    L.gsac_rate_backward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp, pp, pp, pp, vp, GSR_ALLOC, vp, vp]
     _lib = L
     return L
 

@@ -591,6 +591,33 @@ GPCC_API int gsr_ssim_backward(gpcc_ctx *ctx, const float *img1, const float *im
                                int window_size, const float *taps, int size_average, const float *maps, int nmaps, const float *grad_ssim, float ssim_scale,
                                const float *grad_l1, float l1_scale, float *grad_img1, float *grad_img2, void *stream);
 
+/* ================= Entropy rate models (training step, HAC-plus/utils/entropy_models.py: Entropy_gaussian, Entropy_gaussian_mix_prob_2 / _3,
+ * Low_bound; the same Gaussian model as gsac_calculate_cdf) =================
+ * x (n, c) float32 device, contiguous; k in {1, 2, 3} mixture components.  mean[i], scale[i] (and prob[i] for k > 1) are device pointers,
+ * kinds[3k] their shapes in the order mean_0..k-1, scale_0..k-1, prob_0..k-1 (kinds[2k..] unused for k = 1): 0 = full (n, c) contiguous,
+ * 1 = per row (n), 2 = one value.  Q likewise (q_kind 0, 1, 2, q a device pointer) or 3 = the host value q_host (q unused).  x_mean is one
+ * float32 device value (read on the device, never copied back).  Per element, in float32 and in the reference's expression order:
+ *   Q = max(Q, q_floor) when q_floor > 0 (CAT-3DGS: 1e-9); lo = x_mean - 15000 Q, hi = x_mean + 15000 Q; x' = clamp(x, lo, hi)
+ *   s_i = max(scale_i, 1e-9); Phi_i(v) = 0.5 (1 + erf((v - mean_i) (1 / s_i) / sqrt 2)) (torch's Normal.cdf, the 1 + erf form)
+ *   L = |Phi_0(x' + Q/2) - Phi_0(x' - Q/2)| (k = 1) or sum_i prob_i |Phi_i(x' + Q/2) - Phi_i(x' - Q/2)| (list order)
+ *   L' = max(L, 1e-6); out = L' (return_lkl) or -log2(L')
+ * gsac_rate_forward writes out (n, c).  gsac_rate_backward takes the upstream gradient grad_out (n, c) and writes any of grad_x (n, c),
+ * grad_mean[i], grad_scale[i], grad_prob[i], grad_q, each shaped as its operand (n, c) / (n) / (1), NULL = not wanted (the arrays
+ * themselves may be NULL); a host Q has no gradient.  Analytic gradients with autograd's choices at the kinks: clamp passes where
+ * lo <= x <= hi, where scale_i >= 1e-9 and where Q >= q_floor; |.| has gradient 0 at 0; Low_bound passes iff L >= 1e-6; the clamp
+ * bounds are detached (x_mean gets no gradient, Q enters through x' +- Q/2 only).  Per-row and one-value gradients are summed in a fixed
+ * order (per row: columns in order; one value: rows in order per workgroup in double, then the workgroup partials in a fixed tree), no
+ * atomics: bitwise reproducible.  alloc is called once, only when a one-value gradient is wanted, for 8 bytes per workgroup of
+ * ceil(n / floor(256 / c)) per such gradient, not needed once the kernels have run.  n = 0 launches nothing (one-value gradients are set
+ * to 0).  Both calls are enqueued on `stream` without synchronising.  Non-finite mean or scale is not rejected. */
+GPCC_API int gsac_rate_forward(gpcc_ctx *ctx, int k, int64_t n, int64_t c, const float *x, const float *x_mean, const float *const *mean,
+                               const float *const *scale, const float *const *prob, const int *kinds, const float *q, int q_kind, double q_host,
+                               double q_floor, int return_lkl, float *out, void *stream);
+GPCC_API int gsac_rate_backward(gpcc_ctx *ctx, int k, int64_t n, int64_t c, const float *x, const float *x_mean, const float *const *mean,
+                                const float *const *scale, const float *const *prob, const int *kinds, const float *q, int q_kind, double q_host,
+                                double q_floor, int return_lkl, const float *grad_out, float *grad_x, float *const *grad_mean,
+                                float *const *grad_scale, float *const *grad_prob, float *grad_q, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
