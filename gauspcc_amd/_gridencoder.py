@@ -11,6 +11,7 @@ that wrote `dy_dx`.  `PV` and `max_level` are accepted and ignored, as in the re
 import torch
 
 from . import _lib, runtime
+from .runtime import ptr
 
 
 def _need(t, name, dtype):
@@ -61,16 +62,12 @@ def _tables(inputs, embeddings, offsets_list, resolutions_list, N, num_dim, n_fe
     return bv, min_level_id
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def forward_into(inputs, embeddings, offsets, resolutions, outputs, n_features, n_levels, Rb, bv, ml, dy_dx=None):
     """gsge_forward (dy_dx None) or gsge_forward_train into `outputs` (L, N, F) and `dy_dx` (N, L, D, F); tensors already checked."""
     N, num_dim = inputs.shape
     dev = inputs.device
     args = (runtime.context(dev), inputs.data_ptr(), embeddings.data_ptr(), offsets.data_ptr(), resolutions.data_ptr(), outputs.data_ptr(),
-            N, num_dim, n_features, n_levels, Rb, _ptr(bv), _ptr(ml))
+            N, num_dim, n_features, n_levels, Rb, ptr(bv), ptr(ml))
     if dy_dx is None:
         _lib.check(_lib.lib().gsge_forward(*args, runtime.stream_ptr(dev)))
     else:
@@ -81,21 +78,9 @@ def backward_into(grad, inputs, embeddings, offsets, resolutions, grad_embedding
     """gsge_backward: adds into grad_embeddings (rows, F), overwrites grad_inputs (N, D) unless None; tensors already checked."""
     N, num_dim = inputs.shape
     dev = inputs.device
-    bufs = []
-
-    def alloc(user, nbytes):
-        try:
-            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        except RuntimeError:
-            return None
-        bufs.append(t)
-        return t.data_ptr()
-
-    cb = _lib.GSR_ALLOC(alloc)
     _lib.check(_lib.lib().gsge_backward(runtime.context(dev), grad.data_ptr(), inputs.data_ptr(), embeddings.data_ptr(), offsets.data_ptr(),
-                                        resolutions.data_ptr(), embeddings.shape[0], grad_embeddings.data_ptr(), _ptr(grad_inputs), N, num_dim,
-                                        n_features, n_levels, Rb, _ptr(bv), _ptr(ml), cb, None, runtime.stream_ptr(dev)))
-    del bufs   # (stream-ordered: the caching allocator hands this memory out again only behind the kernels just enqueued)
+                                        resolutions.data_ptr(), embeddings.shape[0], grad_embeddings.data_ptr(), ptr(grad_inputs), N, num_dim,
+                                        n_features, n_levels, Rb, ptr(bv), ptr(ml), runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
 
 
 def grid_encode_forward(inputs, embeddings, offsets_list, resolutions_list, outputs, N, num_dim, n_features, n_levels, max_level, Rb, PV,

@@ -191,10 +191,6 @@ def decode_gaussian_slices(mean, scale, Q, slice_start, mins, maxs, data, cnt, c
     return out
 
 
-def _ptr_array(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 def _mix_args(mean_list, scale_list, prob_list, Q):
     k = len(mean_list)
     if not (1 <= k <= 4) or len(scale_list) != k or len(prob_list) != k:
@@ -204,7 +200,7 @@ def _mix_args(mean_list, scale_list, prob_list, Q):
             _chk(t, nm)
     _chk(Q, "Q")
     keep = _f32(*mean_list, *scale_list, *prob_list, Q)      # alive until the library call has returned
-    return k, keep, _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), keep[3 * k]
+    return k, keep, runtime.ptrs(keep[:k]), runtime.ptrs(keep[k:2 * k]), runtime.ptrs(keep[2 * k:3 * k]), keep[3 * k]
 
 
 def calculate_cdf_mixed(mean_list, scale_list, prob_list, Q, min_value, max_value):

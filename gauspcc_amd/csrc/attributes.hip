@@ -1549,17 +1549,15 @@ extern "C" int gsge_backward(gpcc_ctx *ctx, const float *grad, const float *inpu
     hipStream_t st = (hipStream_t)stream;
     const int F = n_features;
     const int64_t nchunks = cdiv(E, GB_CHUNK);
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_kb = al(8 * (size_t)E), o_va = o_kb + al(8 * (size_t)E), o_vb = o_va + al(4 * (size_t)E), o_w = o_vb + al(4 * (size_t)E);
-    const size_t o_h = o_w + al(4 * (size_t)E), o_hd = o_h + al(4 * (size_t)radix_sort_hist_words(E)), o_tl = o_hd + al(4 * (size_t)nchunks * F);
-    const size_t o_own = o_tl + al(4 * (size_t)nchunks * F), bytes = o_own + al((size_t)nchunks);
-    char *blk = static_cast<char *>(alloc(alloc_user, bytes));
-    if (!blk) return fail(GPCC_ERR_NOMEM, "grid encoder backward workspace (%zu bytes)", bytes);
-    uint64_t *ka = reinterpret_cast<uint64_t *>(blk), *kb = reinterpret_cast<uint64_t *>(blk + o_kb);
-    uint32_t *va = reinterpret_cast<uint32_t *>(blk + o_va), *vb = reinterpret_cast<uint32_t *>(blk + o_vb);
-    float *wts = reinterpret_cast<float *>(blk + o_w), *head = reinterpret_cast<float *>(blk + o_hd), *tail = reinterpret_cast<float *>(blk + o_tl);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(blk + o_h);
-    uint8_t *own = reinterpret_cast<uint8_t *>(blk + o_own);
+    uint64_t *ka, *kb;
+    uint32_t *va, *vb, *hist;
+    float *wts, *head, *tail;
+    uint8_t *own;
+    GP_TRY(caller_block(alloc, alloc_user, "gsge_backward", [&](Carver &c) {
+        ka = c.take<uint64_t>(E); kb = c.take<uint64_t>(E); va = c.take<uint32_t>(E); vb = c.take<uint32_t>(E); wts = c.take<float>(E);
+        hist = c.take<uint32_t>(radix_sort_hist_words(E)); head = c.take<float>(nchunks * F); tail = c.take<float>(nchunks * F);
+        own = c.take<uint8_t>(nchunks);
+    }));
     const uint32_t n = (uint32_t)N, L = (uint32_t)n_levels, nr = (uint32_t)n_rows;
     dim3 g((unsigned)cdiv(N, TB), L);
     switch (num_dim) {

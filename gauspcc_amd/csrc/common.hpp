@@ -92,6 +92,35 @@ struct Arena {
     void rewind(size_t m) { if (flip) top = m; else off = m; }
 };
 
+// Device memory from the caller (gsr_alloc_fn, the training paths).  Segments of a caller block are 256-byte aligned.
+inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+template <class T> int caller_alloc(gsr_alloc_fn alloc, void *user, size_t bytes, T **out, const char *who)
+{
+    *out = static_cast<T *>(alloc(user, bytes));
+    return *out ? GPCC_OK : fail(GPCC_ERR_NOMEM, "%s: workspace (%zu bytes)", who, bytes);
+}
+// A block's layout is written once, as a lambda that names each buffer and its element count through take(); caller_block runs it
+// twice: on a Carver without a base (take() only sums the segments), then, once the caller has handed out that many bytes, over the block.
+struct Carver {
+    char *base = nullptr;
+    size_t bytes = 0;
+    template <class T> T *take(size_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
+        bytes += align256(count * sizeof(T));
+        return p;
+    }
+};
+template <class Layout> int caller_block(gsr_alloc_fn alloc, void *user, const char *who, Layout &&layout)
+{
+    Carver c;
+    layout(c);
+    GP_TRY(caller_alloc(alloc, user, c.bytes, &c.base, who));
+    c.bytes = 0;
+    layout(c);
+    return GPCC_OK;
+}
+
 // Environment knobs and per-device one-time set-up, safe when several host threads (one context each) enter for the first
 // time together: function-local statics initialised from a lambda are initialised once (C++11), and what has to happen once
 // PER DEVICE (hipFuncSetAttribute is a per-device setting) runs under a mutex with a bit per device.

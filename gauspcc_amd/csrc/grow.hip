@@ -35,8 +35,6 @@ constexpr int GR = 256;                 // sorted rows one lane group walks in k
 constexpr uint64_t SKIP = ~0ull;        // segment id of a row that feeds no output
 constexpr int H_LO = 0, H_HI = 3, H_BAD = 6, H_NVALID = 7, H_COUNT = 8, H_WORDS = 16;
 
-int64_t al256(int64_t b) { return (b + 255) & ~int64_t(255); }
-
 __device__ __forceinline__ uint32_t ord_word(float v)
 {
     if (v != v) return 0xFFFFFFFFu;
@@ -321,15 +319,16 @@ extern "C" int gpcc_scatter_max(gpcc_ctx *ctx, const float *src, const int64_t *
         LAUNCH_CHECK();
         return GPCC_OK;
     }
-    const int64_t o_keys = 256, o_vals = o_keys + al256(16 * m), o_hist = o_vals + al256(8 * m), o_buf = o_hist + al256(4 * radix_sort_hist_words(m)),
-                  bytes = o_buf + al256(8 * total);
-    char *blk = static_cast<char *>(alloc(alloc_user, (size_t)bytes));
-    if (!blk) return fail(GPCC_ERR_NOMEM, "gpcc_scatter_max: workspace (%lld bytes)", (long long)bytes);
-    int *hdr = reinterpret_cast<int *>(blk);
-    uint64_t *ka = reinterpret_cast<uint64_t *>(blk + o_keys), *kb = ka + m;
-    uint32_t *va = reinterpret_cast<uint32_t *>(blk + o_vals), *vb = va + m;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(blk + o_hist);
-    unsigned long long *buf = reinterpret_cast<unsigned long long *>(blk + o_buf);
+    int *hdr;
+    uint64_t *ka;
+    uint32_t *va, *hist;
+    unsigned long long *buf;
+    GP_TRY(caller_block(alloc, alloc_user, "gpcc_scatter_max", [&](Carver &c) {
+        hdr = c.take<int>(H_WORDS); ka = c.take<uint64_t>(2 * m); va = c.take<uint32_t>(2 * m); hist = c.take<uint32_t>(radix_sort_hist_words(m));
+        buf = c.take<unsigned long long>(total);
+    }));
+    uint64_t *kb = ka + m;
+    uint32_t *vb = va + m;
 
     k_hdr_init<<<1, 64, 0, st>>>(hdr);
     LAUNCH_CHECK();
@@ -349,7 +348,7 @@ extern "C" int gpcc_scatter_max(gpcc_ctx *ctx, const float *src, const int64_t *
 }
 
 // Allocations, in this order: (1) the workspace, at most 84 m + 56 n bytes plus the sort's digit table and 1 KiB; after the second
-// read-back and only when U > 0, (2) the outputs, anchors (U, 3) at offset 0 and features (U, c) at al256(12 U), and (3) 8 U c bytes of
+// read-back and only when U > 0, (2) the outputs, anchors (U, 3) at offset 0 and features (U, c) at align256(12 U), and (3) 8 U c bytes of
 // per-column maxima.
 extern "C" int gpcc_grow_voxels(gpcc_ctx *ctx, const float *xyz, int64_t m, const int64_t *rows, const float *feats, int64_t nrows, int64_t c,
                                 const float *anchors, int64_t n, float inv, float size, int64_t *count_out, gsr_alloc_fn alloc, void *alloc_user,
@@ -366,21 +365,18 @@ extern "C" int gpcc_grow_voxels(gpcc_ctx *ctx, const float *xyz, int64_t m, cons
     hipStream_t st = (hipStream_t)stream;
 
     const int64_t mx = m > n ? m : n;
-    const int64_t o_gq = 256, o_aq = o_gq + al256(16 * m), o_cs = o_aq + al256(16 * n), o_as = o_cs + al256(16 * m), o_k = o_as + al256(16 * n),
-                  o_v = o_k + al256(16 * mx), o_hist = o_v + al256(8 * mx), o_u = o_hist + al256(4 * radix_sort_hist_words(mx)),
-                  o_uk = o_u + 4 * al256(4 * m), o_seg = o_uk + al256(4 * m), bytes = o_seg + al256(8 * m);
-    char *blk = static_cast<char *>(alloc(alloc_user, (size_t)bytes));
-    if (!blk) return fail(GPCC_ERR_NOMEM, "gpcc_grow_voxels: workspace (%lld bytes)", (long long)bytes);
-    int *hdr = reinterpret_cast<int *>(blk);
-    int4 *gq = reinterpret_cast<int4 *>(blk + o_gq), *aq = reinterpret_cast<int4 *>(blk + o_aq);
-    int4 *cs = reinterpret_cast<int4 *>(blk + o_cs), *as = reinterpret_cast<int4 *>(blk + o_as);
-    uint64_t *ka = reinterpret_cast<uint64_t *>(blk + o_k), *kb = ka + mx;
-    uint32_t *va = reinterpret_cast<uint32_t *>(blk + o_v), *vb = va + mx;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(blk + o_hist);
-    uint32_t *u = reinterpret_cast<uint32_t *>(blk + o_u), *keep = reinterpret_cast<uint32_t *>(blk + o_u + al256(4 * m)),
-             *ru = reinterpret_cast<uint32_t *>(blk + o_u + 2 * al256(4 * m)), *rk = reinterpret_cast<uint32_t *>(blk + o_u + 3 * al256(4 * m));
-    int *uk = reinterpret_cast<int *>(blk + o_uk);
-    uint64_t *seg = reinterpret_cast<uint64_t *>(blk + o_seg);
+    int *hdr, *uk;
+    int4 *gq, *aq, *cs, *as;
+    uint64_t *ka, *seg;
+    uint32_t *va, *hist, *u, *keep, *ru, *rk;
+    GP_TRY(caller_block(alloc, alloc_user, "gpcc_grow_voxels", [&](Carver &c) {
+        hdr = c.take<int>(H_WORDS); gq = c.take<int4>(m); aq = c.take<int4>(n); cs = c.take<int4>(m); as = c.take<int4>(n);
+        ka = c.take<uint64_t>(2 * mx); va = c.take<uint32_t>(2 * mx); hist = c.take<uint32_t>(radix_sort_hist_words(mx));
+        u = c.take<uint32_t>(m); keep = c.take<uint32_t>(m); ru = c.take<uint32_t>(m); rk = c.take<uint32_t>(m);
+        uk = c.take<int>(m); seg = c.take<uint64_t>(m);
+    }));
+    uint64_t *kb = ka + mx;
+    uint32_t *vb = va + mx;
 
     k_hdr_init<<<1, 64, 0, st>>>(hdr);
     LAUNCH_CHECK();
@@ -455,12 +451,12 @@ extern "C" int gpcc_grow_voxels(gpcc_ctx *ctx, const float *xyz, int64_t m, cons
     GP_TRY(device_error_check(ctx));
     *count_out = U;
     if (U == 0) return GPCC_OK;
-    const int64_t o_feat = al256(12 * U);
-    char *ob = static_cast<char *>(alloc(alloc_user, (size_t)(o_feat + 4 * U * c)));
-    if (!ob) return fail(GPCC_ERR_NOMEM, "gpcc_grow_voxels: outputs for %lld anchors", (long long)U);
-    unsigned long long *buf = static_cast<unsigned long long *>(alloc(alloc_user, (size_t)(8 * U * c)));
-    if (!buf) return fail(GPCC_ERR_NOMEM, "gpcc_grow_voxels: maxima for %lld anchors", (long long)U);
-    float *anchor_out = reinterpret_cast<float *>(ob), *feat_out = reinterpret_cast<float *>(ob + o_feat);
+    const size_t feat_at = align256(12 * U) / sizeof(float);   // the features' segment ends the block unpadded
+    float *anchor_out;
+    unsigned long long *buf;
+    GP_TRY(caller_alloc(alloc, alloc_user, sizeof(float) * (feat_at + U * c), &anchor_out, "gpcc_grow_voxels: outputs"));
+    GP_TRY(caller_alloc(alloc, alloc_user, sizeof(unsigned long long) * U * c, &buf, "gpcc_grow_voxels: maxima"));
+    float *feat_out = anchor_out + feat_at;
     HIP_TRY(hipMemsetAsync(buf, 0, 8 * (size_t)(U * c), st));
     k_emit_anchor<<<(unsigned)cdiv(m, TB), TB, 0, st>>>(cs, keep, rk, m, size, anchor_out);
     LAUNCH_CHECK();

@@ -340,8 +340,6 @@ int launch_search(hipStream_t st, int nleaves, const float4 *pts, const float4 *
     return GPCC_OK;
 }
 
-int64_t al256(int64_t b) { return (b + 255) & ~int64_t(255); }
-
 }  // namespace
 
 // Workspace layout (one alloc call): the bytes are at most 26 n + 64 KiB (header).  The sorted points (16 n) reuse the two key buffers.
@@ -368,16 +366,17 @@ extern "C" int gpcc_knn(gpcc_ctx *ctx, const float *xyz, int64_t n, int k, int64
     const int nleaves = T.cnt[0];
     static const bool stats = dev_env_int("GAUSPCC_KNN_STATS", 0) != 0;   // developer: visited leaves and popped nodes per wave on stderr (synchronises)
     const int nb = (int)std::min<int64_t>(BB_MAX_BLOCKS, cdiv(n, (int64_t)TB * 8));
-    const int64_t o_part = al256(32), o_keys = o_part + al256(32 * (int64_t)nb), o_vals = o_keys + al256(16 * n), o_hist = o_vals + al256(8 * n),
-                  o_box = o_hist + al256(4 * radix_sort_hist_words(n)), o_vis = o_box + al256(32 * nodes), bytes = o_vis + (stats ? al256(8 * (int64_t)nleaves) : 0);
-    char *blk = static_cast<char *>(alloc(alloc_user, (size_t)bytes));
-    if (!blk) return fail(GPCC_ERR_NOMEM, "gpcc_knn: workspace (%lld bytes)", (long long)bytes);
-    float *box = reinterpret_cast<float *>(blk), *part = reinterpret_cast<float *>(blk + o_part);
-    uint64_t *ka = reinterpret_cast<uint64_t *>(blk + o_keys), *kb = ka + n;
-    uint32_t *va = reinterpret_cast<uint32_t *>(blk + o_vals), *vb = va + n;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(blk + o_hist);
-    float4 *boxes = reinterpret_cast<float4 *>(blk + o_box), *pts = reinterpret_cast<float4 *>(blk + o_keys);
-    uint32_t *visits = stats ? reinterpret_cast<uint32_t *>(blk + o_vis) : nullptr;
+    float *box, *part;
+    uint64_t *ka;
+    uint32_t *va, *hist, *visits;
+    float4 *boxes;
+    GP_TRY(caller_block(alloc, alloc_user, "gpcc_knn", [&](Carver &c) {
+        box = c.take<float>(8); part = c.take<float>(8 * nb); ka = c.take<uint64_t>(2 * n); va = c.take<uint32_t>(2 * n);
+        hist = c.take<uint32_t>(radix_sort_hist_words(n)); boxes = c.take<float4>(2 * nodes); visits = stats ? c.take<uint32_t>(2 * nleaves) : nullptr;
+    }));
+    uint64_t *kb = ka + n;
+    uint32_t *vb = va + n;
+    float4 *pts = reinterpret_cast<float4 *>(ka);   // the sorted points, over the keys once the sort is done with them
 
     k_bbox<<<nb, TB, 0, st>>>(xyz, n, part);
     LAUNCH_CHECK();

@@ -315,8 +315,8 @@ extern "C" int gsr_ssim_forward(gpcc_ctx *ctx, const float *img1, const float *i
     if (loss_out && !l1_out) return fail(GPCC_ERR_ARG, "gsr_ssim_forward: loss needs l1_out");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    double2 *part = static_cast<double2 *>(alloc(alloc_user, (size_t)blocks * sizeof(double2)));
-    if (!part) return fail(GPCC_ERR_NOMEM, "gsr_ssim_forward: workspace (%lld bytes)", (long long)(blocks * sizeof(double2)));
+    double2 *part;
+    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)blocks * sizeof(double2), &part, "gsr_ssim_forward"));
 
     Taps T;
     load_taps(taps, window_size, T);

@@ -1021,8 +1021,8 @@ extern "C" int gsnn_forward_train(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int64_t nk = n * n_offsets;
-    uint32_t *pos = static_cast<uint32_t *>(alloc(alloc_user, (size_t)(nk + 1) * 4));
-    if (!pos) return fail(GPCC_ERR_NOMEM, "neural_gaussians_train: allocator returned NULL");
+    uint32_t *pos;
+    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)(nk + 1) * 4, &pos, "gsnn_forward_train"));
     *pos_out = pos;
     if (n == 0) { HIP_TRY(hipMemsetAsync(pos, 0, 4, st)); return GPCC_OK; }
     if (!anchor || !feat || !offsets || !scaling || !mask || !cam_center || !xyz_out || !color_out || !opacity_out || !scale_out || !rot_out || !nopa_out ||
@@ -1100,8 +1100,8 @@ extern "C" int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offse
     const int64_t chunk = cdiv(cdiv(np, ranges), 16) * 16;
     NGWArgs w = {};
     w.np = np; w.chunk = chunk; w.ranges = ranges;
-    float *ws = static_cast<float *>(alloc(alloc_user, (size_t)ncol * np * 4 + (size_t)NG_MAX_STRIPS * ranges * 4096 * 4));
-    if (!ws) return fail(GPCC_ERR_NOMEM, "neural_gaussians_train: allocator returned NULL");
+    float *ws;
+    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)ncol * np * 4 + (size_t)NG_MAX_STRIPS * ranges * 4096 * 4, &ws, "gsnn_backward"));
     NGBArgs b = {};
     b.anchor = anchor; b.feat = feat; b.offsets = offsets; b.scaling = scaling; b.mask = mask; b.cam = cam_center; b.pos = pos;
     b.n = n; b.np = np; b.K = K; b.mafter = mask_after_opacity != 0;

@@ -865,20 +865,17 @@ extern "C" int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, 
     const int ntiles = cam.gx * cam.gy;
     const size_t P1 = (size_t)std::max(P, 1), npix = (size_t)W * H;
     // frame state sized by P, the tiles and the pixels: one block from the caller
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_xy = 0, o_co = o_xy + al(8 * P1), o_pa = o_co + al(16 * P1), o_pb = o_pa + al(4 * P1), o_offs = o_pb + al(4 * P1);
-    const size_t o_rng = o_offs + al(4 * (P1 + 1)), o_ta = o_rng + al(8 * (size_t)ntiles), o_tb = o_ta + al(4 * (size_t)ntiles);
-    const size_t o_T = o_tb + al(4 * (size_t)ntiles), o_end = o_T + al(4 * npix), bytes_a = o_end + al(4 * npix);
-    char *blk = static_cast<char *>(alloc(alloc_user, bytes_a));
-    if (!blk) return fail(GPCC_ERR_NOMEM, "rasteriser frame state (%zu bytes)", bytes_a);
-    float2 *xy = reinterpret_cast<float2 *>(blk + o_xy);
-    float4 *conic_op = reinterpret_cast<float4 *>(blk + o_co);
-    uint32_t *perm_a = reinterpret_cast<uint32_t *>(blk + o_pa), *perm_b = reinterpret_cast<uint32_t *>(blk + o_pb), *offs = reinterpret_cast<uint32_t *>(blk + o_offs);
-    uint2 *ranges = reinterpret_cast<uint2 *>(blk + o_rng);
-    uint32_t *ord_a = reinterpret_cast<uint32_t *>(blk + o_ta), *ord_b = reinterpret_cast<uint32_t *>(blk + o_tb);
-    float *final_T = reinterpret_cast<float *>(blk + o_T);
-    uint32_t *n_end = reinterpret_cast<uint32_t *>(blk + o_end);
-    char *blk_l = nullptr;           // sized by the pair count: slot -> Gaussian, and the sorted slots (two buffers: the sort ping-pongs)
+    float2 *xy;
+    float4 *conic_op;
+    uint32_t *perm_a, *perm_b, *offs, *ord_a, *ord_b, *n_end;
+    uint2 *ranges;
+    float *final_T;
+    GP_TRY(caller_block(alloc, alloc_user, "gsr_forward_train: frame state", [&](Carver &c) {
+        xy = c.take<float2>(P1); conic_op = c.take<float4>(P1); perm_a = c.take<uint32_t>(P1); perm_b = c.take<uint32_t>(P1);
+        offs = c.take<uint32_t>(P1 + 1); ranges = c.take<uint2>(ntiles); ord_a = c.take<uint32_t>(ntiles); ord_b = c.take<uint32_t>(ntiles);
+        final_T = c.take<float>(npix); n_end = c.take<uint32_t>(npix);
+    }));
+    uint32_t *slot_ids = nullptr, *sa, *sb;   // sized by the pair count: slot -> Gaussian, and the sorted slots (two buffers: the sort ping-pongs)
     size_t want = P1 * 112 + (size_t)ntiles * 32 + ((size_t)8 << 20);
     uint32_t L = 0;
     GP_TRY(ctx->hstage.reserve(64));
@@ -913,15 +910,12 @@ extern "C" int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, 
             perm = v0;
         }
         if (num_rendered_out) *num_rendered_out = cull ? (int64_t)rect_host : (int64_t)L;
-        const size_t o_sa = al(4 * (size_t)L), o_sb = o_sa + al(4 * (size_t)L), bytes_l = o_sb + al(4 * (size_t)L);
-        uint32_t *slot_ids = nullptr, *slots = nullptr;
+        uint32_t *slots = nullptr;
         if (L > 0) {
-            if (!blk_l) {
-                blk_l = static_cast<char *>(alloc(alloc_user, bytes_l));
-                if (!blk_l) return fail(GPCC_ERR_NOMEM, "rasteriser pair state (%zu bytes)", bytes_l);
-            }
-            slot_ids = reinterpret_cast<uint32_t *>(blk_l);
-            uint32_t *sa = reinterpret_cast<uint32_t *>(blk_l + o_sa), *sb = reinterpret_cast<uint32_t *>(blk_l + o_sb);
+            if (!slot_ids)
+                GP_TRY(caller_block(alloc, alloc_user, "gsr_forward_train: pair state", [&](Carver &c) {
+                    slot_ids = c.take<uint32_t>(L); sa = c.take<uint32_t>(L); sb = c.take<uint32_t>(L);
+                }));
             uint64_t *ka = ctx->arena.take<uint64_t>(L), *kb = ctx->arena.take<uint64_t>(L);
             if (!ka || !kb || ctx->arena.cap - ctx->arena.off < (size_t)L * 2 + ((size_t)2 << 20)) { want += (size_t)L * 4; continue; }  // grow and redo
             int tbits = 1;
@@ -988,8 +982,7 @@ extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const f
     const uint32_t *n_end = reinterpret_cast<const uint32_t *>(state[13]);
     float *rec = nullptr;
     if (L > 0) {
-        rec = static_cast<float *>(alloc(alloc_user, (size_t)L * NREC * sizeof(float)));
-        if (!rec) return fail(GPCC_ERR_NOMEM, "rasteriser backward records (%llu pairs)", (unsigned long long)L);
+        GP_TRY(caller_alloc(alloc, alloc_user, (size_t)L * NREC * sizeof(float), &rec, "gsr_backward: records"));
         k_render_backward<<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, slots, slot_ids, W, H, cam.gx, xy, colors_precomp, conic_op, background,
                                                            final_T, n_end, dL_dout, rec);
         LAUNCH_CHECK();

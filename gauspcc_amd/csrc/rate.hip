@@ -364,9 +364,8 @@ extern "C" int gsac_rate_backward(gpcc_ctx *ctx, int k, int64_t n, int64_t c, co
     memset(&P, 0, sizeof(P));
     if (nones) {
         if (!alloc) return fail(GPCC_ERR_ARG, "gsac_rate_backward: a one-value gradient needs the workspace allocator");
-        const size_t bytes = (size_t)nones * (size_t)blocks * sizeof(double);
-        double *ws = static_cast<double *>(alloc(alloc_user, bytes));
-        if (!ws) return fail(GPCC_ERR_NOMEM, "gsac_rate_backward: workspace (%lld bytes)", (long long)bytes);
+        double *ws;
+        GP_TRY(caller_alloc(alloc, alloc_user, (size_t)nones * (size_t)blocks * sizeof(double), &ws, "gsac_rate_backward"));
         int j = 0;
         for (int o = 0; o < NOPS; ++o)
             if (G.op[o] && G.kind[o] == ONE) {

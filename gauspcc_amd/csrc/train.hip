@@ -225,40 +225,35 @@ int frame_body(gpcc_ctx *ctx, hipStream_t st, const int32_t *xyz, int64_t n, int
     // caller memory: the pool (tiles + CONV_HDR_PAD zeroed ones the conv kernel may read past a list), block ranges, pair flags,
     // the two dispatch orders and run indexes, the per-node arrays
     const int64_t ntile = L > 1 ? (int64_t)total + CONV_HDR_PAD : 0;
-    const int64_t nb0 = F->set[0].nblk, nb1 = F->set[1].nblk;
-    const size_t sz[] = {(size_t)ntile * 64, (size_t)ntile * 16, (size_t)ntile * 4, (size_t)(pool.nblk + 1) * 4, pool.pflag ? (size_t)pool.nblk : 0,
-                         (size_t)nb0 * 4, (size_t)nb1 * 4, (size_t)nb0 * (F->K + 1) * 4, (size_t)nb1 * (F->K + 1) * 4,
-                         (size_t)nodes, (size_t)nodes * 12, (size_t)F->nC * 4, (size_t)F->nC};
-    constexpr int NSEG = sizeof(sz) / sizeof(sz[0]);
-    size_t off[NSEG + 1] = {0};
-    for (int i = 0; i < NSEG; ++i) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    char *mem = static_cast<char *>(alloc(user, std::max<size_t>(off[NSEG], 256)));
-    if (!mem) { *alloc_failed = true; return fail(GPCC_ERR_NOMEM, "the frame allocator returned NULL for %zu bytes", off[NSEG]); }
-    auto seg = [&](int i) { return mem + off[i]; };
+    const int64_t npflag = pool.pflag ? pool.nblk : 0;
+    int32_t *tj;
+    uint8_t *tr, *pflag;
+    uint32_t *toc, *first, *order[2], *runs[2];
+    const int rc = caller_block(alloc, user, "gpcc_train_frame", [&](Carver &c) {
+        tj = c.take<int32_t>(16 * ntile); tr = c.take<uint8_t>(16 * ntile); toc = c.take<uint32_t>(ntile); first = c.take<uint32_t>(pool.nblk + 1);
+        pflag = c.take<uint8_t>(npflag);
+        for (int s = 0; s < 2; ++s) order[s] = c.take<uint32_t>(F->set[s].nblk);
+        for (int s = 0; s < 2; ++s) runs[s] = c.take<uint32_t>(F->set[s].nblk * (F->K + 1));
+        F->occ = c.take<uint8_t>(nodes); F->coords = c.take<int32_t>(3 * nodes); F->parent = c.take<int32_t>(F->nC); F->octant = c.take<uint8_t>(F->nC);
+    });
+    if (rc != GPCC_OK) { *alloc_failed = true; return rc; }
     if (L > 1) {
-        HIP_TRY(hipMemcpyAsync(seg(0), pool.tj, sz[0], hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(seg(1), pool.tr, sz[1], hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(seg(2), pool.toc, sz[2], hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(seg(3), pool.first, sz[3], hipMemcpyDeviceToDevice, st));
-        if (sz[4]) HIP_TRY(hipMemcpyAsync(seg(4), pool.pflag, sz[4], hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(tj, pool.tj, 64 * (size_t)ntile, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(tr, pool.tr, 16 * (size_t)ntile, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(toc, pool.toc, 4 * (size_t)ntile, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(first, pool.first, 4 * (size_t)(pool.nblk + 1), hipMemcpyDeviceToDevice, st));
+        if (npflag) HIP_TRY(hipMemcpyAsync(pflag, pool.pflag, (size_t)npflag, hipMemcpyDeviceToDevice, st));
         for (int s = 0; s < 2; ++s) {
             ConvTiles &V = F->set[s];
-            HIP_TRY(hipMemcpyAsync(seg(5 + s), V.order, sz[5 + s], hipMemcpyDeviceToDevice, st));
-            V.tj = reinterpret_cast<int32_t *>(seg(0)); V.tr = reinterpret_cast<uint8_t *>(seg(1)); V.toc = reinterpret_cast<uint32_t *>(seg(2));
-            V.first = reinterpret_cast<uint32_t *>(seg(3)); V.pflag = sz[4] ? reinterpret_cast<uint8_t *>(seg(4)) : nullptr;
-            V.order = reinterpret_cast<uint32_t *>(seg(5 + s));
-            uint32_t *runs = reinterpret_cast<uint32_t *>(seg(7 + s));
-            F->runs[s] = runs;
-            k_run_index<<<(unsigned)cdiv(V.nblk * (F->K + 1), 256), 256, 0, st>>>(V, runs);
+            HIP_TRY(hipMemcpyAsync(order[s], V.order, 4 * (size_t)V.nblk, hipMemcpyDeviceToDevice, st));
+            V.tj = tj; V.tr = tr; V.toc = toc; V.first = first; V.pflag = npflag ? pflag : nullptr; V.order = order[s];
+            F->runs[s] = runs[s];
+            k_run_index<<<(unsigned)cdiv(V.nblk * (F->K + 1), 256), 256, 0, st>>>(V, runs[s]);
             LAUNCH_CHECK();
             const int64_t ng = std::max<int64_t>(1, std::min<int64_t>(V.nblk, cdiv(WGRAD_WAVES_TARGET, F->K)));
             F->group[s] = std::max<int64_t>(1, cdiv(V.nblk, ng));
         }
     }
-    F->occ = reinterpret_cast<uint8_t *>(seg(9));
-    F->coords = reinterpret_cast<int32_t *>(seg(10));
-    F->parent = reinterpret_cast<int32_t *>(seg(11));
-    F->octant = reinterpret_cast<uint8_t *>(seg(12));
     FrameNodes S = {};
     S.L = L;
     for (int d = 0; d <= L; ++d) S.base[d] = F->level_base[d];
@@ -364,8 +359,8 @@ extern "C" int gpcc_train_wgrad(gpcc_ctx *ctx, const uint64_t *state, int set, c
     const ConvTiles &T = F.set[set];
     const int64_t G = F.group[set];
     const int ng = (int)cdiv(T.nblk, G);
-    float *part = static_cast<float *>(alloc(alloc_user, (size_t)F.K * ng * 4096));
-    if (!part) return fail(GPCC_ERR_NOMEM, "the workspace allocator returned NULL");
+    float *part;
+    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)F.K * ng * 4096, &part, "gpcc_train_wgrad"));
     WgradArgs a = {T, F.runs[set], x_dev, dy_dev, part, G, ng};
     k_wgrad_part<<<(unsigned)cdiv((int64_t)F.K * ng, 4), 256, 0, st>>>(a);
     LAUNCH_CHECK();

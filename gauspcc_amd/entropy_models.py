@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, runtime
+from .runtime import ptr, ptrs
 
 FULL, ROW, ONE, HOST = 0, 1, 2, 3
 
@@ -75,10 +76,6 @@ class _Operand:
         return g.view(self.shape)
 
 
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
-
-
 class _Plan:
     """What one call of the fused rate term reads: k components, x as (n, c), its operands, Q and the options."""
     def __init__(self, k, x, n, c, ops, q, q_floor, lkl):
@@ -89,8 +86,8 @@ class _Plan:
         k, ops, q = self.k, self.ops, self.q
         means, scales, probs = ops[:k], ops[k:2 * k], ops[2 * k:]
         kinds = [o.kind for o in means] + [o.kind for o in scales] + ([o.kind for o in probs] if k > 1 else [ONE] * k)
-        return (k, self.n, self.c, x2.data_ptr(), xm.data_ptr(), _ptrs([o.data for o in means]), _ptrs([o.data for o in scales]),
-                _ptrs([o.data for o in probs]) if k > 1 else None, (ctypes.c_int * (3 * k))(*kinds),
+        return (k, self.n, self.c, x2.data_ptr(), xm.data_ptr(), ptrs([o.data for o in means]), ptrs([o.data for o in scales]),
+                ptrs([o.data for o in probs]) if k > 1 else None, (ctypes.c_int * (3 * k))(*kinds),
                 None if q.kind == HOST else q.data.data_ptr(), q.kind, 0.0 if q.host is None else q.host,
                 0.0 if self.q_floor is None else float(self.q_floor), int(self.lkl))
 
@@ -126,21 +123,9 @@ class _Rate(torch.autograd.Function):
             gops = [None if g is None else g.zero_() for g in gops]
         elif gx is not None or gq is not None or any(g is not None for g in gops):
             g = grad.detach().reshape(n, c).contiguous()
-            bufs = []
-
-            def alloc(user, nbytes):
-                try:
-                    t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-                except RuntimeError:
-                    return None
-                bufs.append(t)
-                return t.data_ptr()
-
-            ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-            _lib.check(_lib.lib().gsac_rate_backward(runtime.context(dev), *plan.args(x2, xm), g.data_ptr(), ptr(gx), _ptrs(gops[:k]),
-                                                     _ptrs(gops[k:2 * k]), _ptrs(gops[2 * k:]) if k > 1 else None, ptr(gq),
-                                                     _lib.GSR_ALLOC(alloc), None, runtime.stream_ptr(dev)))
-            del bufs   # stream-ordered: the caching allocator hands this memory out again only behind the kernels just enqueued
+            _lib.check(_lib.lib().gsac_rate_backward(runtime.context(dev), *plan.args(x2, xm), g.data_ptr(), ptr(gx), ptrs(gops[:k]),
+                                                     ptrs(gops[k:2 * k]), ptrs(gops[2 * k:]) if k > 1 else None, ptr(gq),
+                                                     runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
         back = lambda g, o: None if g is None else o.to_caller(g, plan.xshape)   # noqa: E731
         return (None, None if gx is None else gx.view(plan.xshape), None, back(gq, q)) + tuple(back(g, o) for g, o in zip(gops, ops))
 

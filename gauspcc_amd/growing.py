@@ -13,7 +13,6 @@ import numpy as np
 import torch
 
 from . import _lib, runtime
-from .scatter import _alloc_cb
 
 
 def _tensor(t, name, dtype, ndim, cols=None):
@@ -59,19 +58,19 @@ def grow_voxels(xyz, anchors, cur_size, feats, rows=None):
     xyz, anchors, feats = (t.detach().contiguous() for t in (xyz, anchors, feats))
     rows = rows.detach().contiguous() if rows is not None else None
     M, N, (R, C) = xyz.shape[0], anchors.shape[0], feats.shape
-    bufs = []
-    cb = _alloc_cb(dev, bufs)
+    work = runtime.Workspace(dev)
     count = ctypes.c_int64(0)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()   # noqa: E731
+
+    def ptr(t):   # NULL for an empty tensor too
+        return None if t is None or t.numel() == 0 else t.data_ptr()
+
     _lib.check(_lib.lib().gpcc_grow_voxels(runtime.context(dev), ptr(xyz), M, ptr(rows), ptr(feats), R, C, ptr(anchors), N, float(inv), float(size),
-                                           ctypes.byref(count), cb, None, runtime.stream_ptr(dev)))
+                                           ctypes.byref(count), work.fn(), None, runtime.stream_ptr(dev)))
     U = count.value
     if U == 0:
-        del bufs
         return torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, C), dtype=torch.float32, device=dev)
-    blk = bufs[1]   # allocation (2): anchors at 0, features at (12 U + 255) & ~255
+    blk = work.buffers[1]   # allocation (2): anchors at 0, features at (12 U + 255) & ~255
     off = (12 * U + 255) & ~255
     new_anchor = blk[:12 * U].view(torch.float32).view(U, 3)
     new_feat = blk[off:off + 4 * U * C].view(torch.float32).view(U, C)
-    del bufs
     return new_anchor, new_feat

@@ -16,6 +16,7 @@ import operator
 import torch
 
 from . import _lib, runtime
+from .runtime import ptr
 
 MAX_K = 16   # gpcc_knn: neighbours per point, the point itself not counted
 
@@ -46,20 +47,8 @@ def knn(points, k, indices=True, distances=True, mean=False):
     mn = torch.empty(P, dtype=torch.float32, device=dev) if mean else None
     if P == 0:
         return idx, d2, mn
-    bufs = []
-
-    def alloc(user, nbytes):
-        try:
-            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        except RuntimeError:
-            return None
-        bufs.append(t)
-        return t.data_ptr()
-
-    cb = _lib.GSR_ALLOC(alloc)
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    _lib.check(_lib.lib().gpcc_knn(runtime.context(dev), points.data_ptr(), P, int(k), ptr(idx), ptr(d2), ptr(mn), cb, None, runtime.stream_ptr(dev)))
-    del bufs   # (stream-ordered: the caching allocator hands this memory out again only behind the kernels just enqueued)
+    _lib.check(_lib.lib().gpcc_knn(runtime.context(dev), points.data_ptr(), P, int(k), ptr(idx), ptr(d2), ptr(mn),
+                                    runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
     return idx, d2, mn
 
 

@@ -17,6 +17,7 @@ import math
 import torch
 
 from . import _lib, runtime
+from .runtime import ptr
 
 MAX_WINDOW = 31
 
@@ -72,21 +73,9 @@ def _forward(x, y, window_size, size_average, nmaps, lam=None):
     l1 = torch.empty(1, dtype=torch.float32, device=dev) if lam is not None else None
     loss = torch.empty(1, dtype=torch.float32, device=dev) if lam is not None else None
     maps = torch.empty((nmaps,) + tuple(x.shape), dtype=torch.float32, device=dev) if nmaps else None
-    bufs = []
-
-    def alloc(user, nbytes):
-        try:
-            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        except RuntimeError:
-            return None
-        bufs.append(t)
-        return t.data_ptr()
-
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     _lib.check(_lib.lib().gsr_ssim_forward(runtime.context(dev), x.data_ptr(), y.data_ptr(), B, C, H, W, window_size, _taps(window_size),
                                            int(size_average), out.data_ptr(), ptr(l1), ptr(loss), 0.0 if lam is None else float(lam), ptr(maps), nmaps,
-                                           _lib.GSR_ALLOC(alloc), None, runtime.stream_ptr(dev)))
-    del bufs   # stream-ordered: the caching allocator hands this memory out again only behind the kernels just enqueued
+                                           runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
     return out, l1, loss, maps
 
 
@@ -95,7 +84,6 @@ def _backward(x, y, window_size, size_average, maps, g_ssim, ssim_scale, g_l1, l
     dev = x.device
     d1 = torch.empty_like(x) if need1 else None
     d2 = torch.empty_like(x) if need2 else None
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     _lib.check(_lib.lib().gsr_ssim_backward(runtime.context(dev), x.data_ptr(), y.data_ptr(), B, C, H, W, window_size, _taps(window_size),
                                             int(size_average), maps.data_ptr(), maps.shape[0], g_ssim.data_ptr(), float(ssim_scale), ptr(g_l1), float(l1_scale),
                                             ptr(d1), ptr(d2), runtime.stream_ptr(dev)))

@@ -24,6 +24,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
+from .runtime import ptrs
 from .hac_codec import Q_FEAT, Q_OFFSETS, Q_SCALING, grid_mlp, ste_multistep
 
 
@@ -118,21 +119,6 @@ def _mlp_params(pc):
     return bank + lin(pc.get_opacity_mlp) + lin(pc.get_cov_mlp) + lin(pc.get_color_mlp)
 
 
-def _alloc_cb(dev, keep):
-    def alloc(user, nbytes):
-        try:
-            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        except RuntimeError:
-            return None
-        keep.append(t)
-        return t.data_ptr()
-    return _lib.GSR_ALLOC(alloc)
-
-
-def _ptrs(ts):
-    return (C.c_void_p * 16)(*[None if t is None else t.data_ptr() for t in ts])
-
-
 class _NeuralGaussians(torch.autograd.Function):
     """gsnn_forward_train / gsnn_backward.  The backward's state is the scan of the keep flags, (n K + 1) uint32 in a tensor on the autograd
     context (through the library's allocator callback): the hidden layers are recomputed, so other library calls may run in between."""
@@ -150,15 +136,13 @@ class _NeuralGaussians(torch.autograd.Function):
         opacity, rot = torch.empty(nk, 1, device=dev), torch.empty(nk, 4, device=dev)
         nopa = torch.empty(nk, 1, device=dev)
         keep = torch.empty(nk, dtype=torch.bool, device=dev)
-        bufs = []
-        cb = _alloc_cb(dev, bufs)
+        work = runtime.Workspace(dev)
         pos, m = C.c_void_p(), C.c_int64()
-        wp = _ptrs(ws)
-        _lib.check(_lib.lib().gsnn_forward_train(runtime.context(dev), n, F, K, *[t.data_ptr() for t in ins], wp, int(bool(mask_after)), xyz.data_ptr(),
+        _lib.check(_lib.lib().gsnn_forward_train(runtime.context(dev), n, F, K, *[t.data_ptr() for t in ins], ptrs(ws, 16), int(bool(mask_after)), xyz.data_ptr(),
                                                  color.data_ptr(), opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), nopa.data_ptr(), keep.data_ptr(),
-                                                 cb, None, C.byref(pos), C.byref(m), runtime.stream_ptr(dev)))
+                                                 work.fn(), None, C.byref(pos), C.byref(m), runtime.stream_ptr(dev)))
         m = m.value
-        ctx.state = (bufs, pos.value, bool(mask_after), n, F, K, masks.shape, grid_offsets.shape)
+        ctx.state = (work, pos.value, bool(mask_after), n, F, K, masks.shape, grid_offsets.shape)
         ctx.save_for_backward(*ins, *ws)
         ctx.mark_non_differentiable(keep)
         return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m], nopa, keep
@@ -166,7 +150,7 @@ class _NeuralGaussians(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_xyz, g_color, g_opacity, g_scaling, g_rot, g_nopa, g_keep):
-        bufs, pos, mask_after, n, F, K, mshape, oshape = ctx.state
+        _, pos, mask_after, n, F, K, mshape, oshape = ctx.state
         saved = ctx.saved_tensors
         ins, ws = saved[:6], list(saved[6:])
         dev = ins[0].device
@@ -175,11 +159,9 @@ class _NeuralGaussians(torch.autograd.Function):
         d_anchor, d_feat = torch.empty(n, 3, device=dev), torch.empty(n, F, device=dev)
         d_off, d_sc, d_mask = torch.empty(n, K, 3, device=dev), torch.empty(n, 6, device=dev), torch.empty(n, K, device=dev)
         d_ws = [None if w is None else torch.empty_like(w) for w in ws]
-        work = []
-        cb = _alloc_cb(dev, work)
-        _lib.check(_lib.lib().gsnn_backward(runtime.context(dev), n, F, K, *[t.data_ptr() for t in ins], _ptrs(ws), int(mask_after), pos,
+        _lib.check(_lib.lib().gsnn_backward(runtime.context(dev), n, F, K, *[t.data_ptr() for t in ins], ptrs(ws, 16), int(mask_after), pos,
                                             *[g.data_ptr() for g in gs], d_anchor.data_ptr(), d_feat.data_ptr(), d_off.data_ptr(), d_sc.data_ptr(),
-                                            d_mask.data_ptr(), _ptrs(d_ws), cb, None, runtime.stream_ptr(dev)))
+                                            d_mask.data_ptr(), ptrs(d_ws, 16), runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
         return (None, d_anchor, d_feat, d_off.view(oshape), d_sc, d_mask.view(mshape), None, *d_ws)
 
 

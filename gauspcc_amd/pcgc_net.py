@@ -34,22 +34,12 @@ class _Frame:
     def __init__(self, xyz: torch.Tensor, kernel_size: int):
         dev = xyz.device
         self.device = dev
-        self.bufs = []
-
-        def alloc(user, nbytes):
-            try:
-                t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            except RuntimeError:
-                return None
-            self.bufs.append(t)
-            return t.data_ptr()
-
-        cb = _lib.GSR_ALLOC(alloc)
+        self.work = runtime.Workspace(dev)
         self.state = (C.c_uint64 * _lib.GPCC_TRAIN_STATE_WORDS)()
         L = C.c_int32()
         nodes = (C.c_int64 * 24)()
         xyz = xyz.to(torch.int32).contiguous()
-        _lib.check(_lib.lib().gpcc_train_frame(runtime.context(dev), xyz.data_ptr(), xyz.shape[0], int(kernel_size), cb, None, self.state,
+        _lib.check(_lib.lib().gpcc_train_frame(runtime.context(dev), xyz.data_ptr(), xyz.shape[0], int(kernel_size), self.work.fn(), None, self.state,
                                                C.byref(L), nodes, runtime.stream_ptr(dev)))
         self.L = L.value
         self.level_nodes = [int(nodes[d]) for d in range(self.L)]
@@ -108,20 +98,8 @@ class _SparseConvFn(torch.autograd.Function):
                                                   dx.data_ptr(), runtime.stream_ptr(dev)))
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)
-            keep = []
-
-            def alloc(user, nbytes):
-                try:
-                    t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-                except RuntimeError:
-                    return None
-                keep.append(t)
-                return t.data_ptr()
-
-            cb = _lib.GSR_ALLOC(alloc)
-            _lib.check(_lib.lib().gpcc_train_wgrad(runtime.context(dev), frame.state, s, x.data_ptr(), g.data_ptr(), cb, None, dw.data_ptr(),
-                                                   runtime.stream_ptr(dev)))
-            del keep   # (stream-ordered: the caching allocator reuses it only behind the kernels just enqueued)
+            _lib.check(_lib.lib().gpcc_train_wgrad(runtime.context(dev), frame.state, s, x.data_ptr(), g.data_ptr(), runtime.Workspace(dev).fn(), None,
+                                                   dw.data_ptr(), runtime.stream_ptr(dev)))
         return dx, dw, (g if ctx.has_res else None), None, None, None
 
 

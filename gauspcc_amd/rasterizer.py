@@ -18,6 +18,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
+from .runtime import ptr
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -48,10 +49,6 @@ def _check_args(shs, colors_precomp, scales, rotations, cov3D_precomp):
         raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class _RasterizeGaussians(torch.autograd.Function):
     """Training path.  The frame state the backward needs lives in uint8 tensors handed to the library through its allocator callback and
     kept on the autograd context: it dies with the graph, and other rasteriser calls may run between forward and backward."""
@@ -67,26 +64,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty(P, dtype=torch.int32, device=dev)
         view, proj, bg = _f32(rs.viewmatrix), _f32(rs.projmatrix), _f32(rs.bg)
-        bufs = []
-
-        def alloc(user, nbytes):
-            try:
-                t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            except RuntimeError:
-                return None
-            bufs.append(t)
-            return t.data_ptr()
-
-        cb = _lib.GSR_ALLOC(alloc)
+        work = runtime.Workspace(dev)
         state = (C.c_uint64 * _lib.GSR_STATE_WORDS)()
         n = C.c_int64()
         _lib.check(_lib.lib().gsr_forward_train(
-            runtime.context(dev), P, bg.data_ptr(), W, H, m.data_ptr(), col.data_ptr(), op.data_ptr(), _ptr(sc), float(rs.scale_modifier), _ptr(rot),
-            _ptr(cov), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)), color.data_ptr(), radii.data_ptr(),
-            cb, None, state, C.byref(n), runtime.stream_ptr(dev)))
+            runtime.context(dev), P, bg.data_ptr(), W, H, m.data_ptr(), col.data_ptr(), op.data_ptr(), ptr(sc), float(rs.scale_modifier), ptr(rot),
+            ptr(cov), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)), color.data_ptr(), radii.data_ptr(),
+            work.fn(), None, state, C.byref(n), runtime.stream_ptr(dev)))
         info["num_rendered"] = n.value
         ctx.rs = rs
-        ctx.frame = (bufs, state)
+        ctx.frame = (work, state)
         ctx.save_for_backward(means3D, means2D, opacities, colors_precomp, scales, rotations, cov3D_precomp, radii)
         ctx.mark_non_differentiable(radii)
         return color, radii
@@ -96,7 +83,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_color, grad_radii):
         means3D, means2D, opacities, colors_precomp, scales, rotations, cov3D_precomp, radii = ctx.saved_tensors
         rs = ctx.rs
-        bufs, state = ctx.frame
+        state = ctx.frame[1]
         m, col, op = _f32(means3D), _f32(colors_precomp), _f32(opacities)
         sc, rot, cov = _f32(scales), _f32(rotations), _f32(cov3D_precomp)
         P = m.shape[0]
@@ -110,24 +97,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             g["sc"], g["rot"] = torch.empty((P, 3), dtype=torch.float32, device=dev), torch.empty((P, 4), dtype=torch.float32, device=dev)
         else:
             g["cov"] = torch.empty((P, 6), dtype=torch.float32, device=dev)
-        recs = []
-
-        def alloc(user, nbytes):
-            try:
-                t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            except RuntimeError:
-                return None
-            recs.append(t)
-            return t.data_ptr()
-
-        cb = _lib.GSR_ALLOC(alloc)
         _lib.check(_lib.lib().gsr_backward(
-            runtime.context(dev), state, P, bg.data_ptr(), W, H, m.data_ptr(), col.data_ptr(), op.data_ptr(), _ptr(sc), float(rs.scale_modifier), _ptr(rot),
-            _ptr(cov), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy), radii.data_ptr(), dout.data_ptr(), cb, None,
-            g["m3"].data_ptr(), g["m2"].data_ptr(), g["col"].data_ptr(), g["op"].data_ptr(), _ptr(g.get("sc")), _ptr(g.get("rot")), _ptr(g.get("cov")),
-            runtime.stream_ptr(dev)))
-        del recs, bufs   # (stream-ordered: the caching allocator hands this memory out again only behind the kernels just enqueued)
-        ctx.frame = None
+            runtime.context(dev), state, P, bg.data_ptr(), W, H, m.data_ptr(), col.data_ptr(), op.data_ptr(), ptr(sc), float(rs.scale_modifier), ptr(rot),
+            ptr(cov), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy), radii.data_ptr(), dout.data_ptr(),
+            runtime.Workspace(dev).fn(), None, g["m3"].data_ptr(), g["m2"].data_ptr(), g["col"].data_ptr(), g["op"].data_ptr(), ptr(g.get("sc")),
+            ptr(g.get("rot")), ptr(g.get("cov")), runtime.stream_ptr(dev)))
+        ctx.frame = None   # the frame state goes with its workspace
 
         def out(key, t):
             if t is None or not ctx.needs_input_grad[["m3", "m2", "op", "col", "sc", "rot", "cov"].index(key)]:

@@ -83,6 +83,41 @@ def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(_device_index(device)).cuda_stream)
 
 
+def ptr(t):
+    """A tensor's device pointer, None (NULL) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def ptrs(ts, n=None):
+    """A c_void_p array of ptr(t) for each t, padded with NULL to n slots when n is given."""
+    return (C.c_void_p * (len(ts) if n is None else n))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+class Workspace:
+    """Device memory the library asks for through gsr_alloc_fn: uint8 tensors on `device`, in request order (`buffers`).  fn() is the
+    callback for one call; it returns NULL when torch cannot allocate, and the call then fails with GPCC_ERR_NOMEM.  The buffers live
+    as long as the Workspace.  Dropping it right after the call is safe: the caching allocator hands the memory out again only behind
+    the kernels already enqueued on the stream."""
+
+    def __init__(self, device):
+        self.device = device
+        self.buffers = []
+
+    def fn(self):
+        # a fresh callback over the list, not stored on self: self -> callback -> self would keep the buffers until the cycle collector runs
+        dev, bufs = self.device, self.buffers
+
+        def request(user, nbytes):
+            try:
+                t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+            except RuntimeError:
+                return None
+            bufs.append(t)
+            return t.data_ptr()
+
+        return _lib.GSR_ALLOC(request)
+
+
 class Model:
     """Weights resident on one device (gpcc_model)."""
 

@@ -13,18 +13,6 @@ import torch
 from . import _lib, runtime
 
 
-def _alloc_cb(dev, bufs):
-    def alloc(user, nbytes):
-        try:
-            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        except RuntimeError:
-            return None
-        bufs.append(t)
-        return t.data_ptr()
-
-    return _lib.GSR_ALLOC(alloc)
-
-
 def scatter_max_rows(src, index, dim_size, out=None):
     """gpcc_scatter_max on checked tensors: src (M, C) float32, index (M,) int64, both contiguous on one device.  out (S, C) float32
     contiguous gives include-self semantics and is written in place.  Returns (out, arg (S, C) int64)."""
@@ -36,11 +24,9 @@ def scatter_max_rows(src, index, dim_size, out=None):
     arg = torch.empty((dim_size, C), dtype=torch.int64, device=dev)
     if dim_size == 0 and M == 0:
         return out, arg
-    bufs = []
-    cb = _alloc_cb(dev, bufs)
     _lib.check(_lib.lib().gpcc_scatter_max(runtime.context(dev), src.data_ptr() if M else None, index.data_ptr() if M else None, M, C, dim_size,
-                                           int(include_self), out.data_ptr(), arg.data_ptr(), cb, None, runtime.stream_ptr(dev)))
-    del bufs   # (stream-ordered: the caching allocator hands this memory out again only behind the kernels just enqueued)
+                                           int(include_self), out.data_ptr(), arg.data_ptr(), runtime.Workspace(dev).fn(), None,
+                                           runtime.stream_ptr(dev)))
     return out, arg
 
 
