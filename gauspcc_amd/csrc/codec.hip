@@ -13,7 +13,6 @@
 #include <algorithm>
 #include <chrono>
 
-#include <functional>
 #include "hostcoder.hpp"
 #include "codec_shared.hpp"
 #include "container.hpp"
@@ -30,8 +29,17 @@ constexpr int ENC_RETRY_SMALLER_CHUNKS = -1000;
 // launch-per-layer path (ctx->fused_off is set)
 constexpr int DEC_RETRY_UNFUSED = -1001;
 
-// lohi slot of stage 0 and stage stride of every row of C: where the heads put a node's coder input (needs the raster ranks)
-__global__ __launch_bounds__(256) void k_set_pos(SetLevels S, int64_t nC, uint32_t *__restrict__ pos_out, uint32_t *__restrict__ slots_out)
+// Where the heads put a node's coder input (needs the raster ranks).  Level d >= 1 lives in the target set C at rows cbase[d]..; its four
+// streams start at word lohi_base[d], slots[d] words each, cut into nch[d] lanes of 2^clog[d] symbols.
+struct PosLevels {
+    int L;
+    uint32_t cbase[MAXLV], lohi_base[MAXLV], slots[MAXLV], nch[MAXLV];
+    int clog[MAXLV];
+    const uint32_t *m2r[MAXLV];
+};
+
+// lohi slot of stage 0 and stage stride of every row of C
+__global__ __launch_bounds__(256) void k_set_pos(PosLevels S, int64_t nC, uint32_t *__restrict__ pos_out, uint32_t *__restrict__ slots_out)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nC) return;
@@ -39,6 +47,17 @@ __global__ __launch_bounds__(256) void k_set_pos(SetLevels S, int64_t nC, uint32
     for (int q = 2; q < S.L; ++q) d = i >= (int64_t)S.cbase[q] ? q : d;
     pos_out[i] = S.lohi_base[d] + rc_interleaved(S.m2r[d][i - S.cbase[d]], S.clog[d], S.nch[d]);
     slots_out[i] = S.slots[d];
+}
+
+// what every successful encode reports (hp: the pair counters, then the 16 accumulators of the ideal code length)
+void fill_stats(gpcc_stats *stats, int64_t n, size_t nbytes, const Tree &T, int64_t coded, const unsigned long long set_pairs[2], const unsigned long long *hp)
+{
+    memset(stats, 0, sizeof *stats);
+    stats->num_points = n; stats->num_bytes = (int64_t)nbytes; stats->num_levels = T.L; stats->coded_nodes = coded;
+    for (int d = 0; d < T.L; ++d) stats->level_nodes[d] = T.lv[d].n;
+    stats->conv_pairs = (int64_t)set_pairs[0] * 5 + (int64_t)set_pairs[1] * 13;   // prior set: 5 convs, target set: 5 + 8
+    const double *hb = reinterpret_cast<const double *>(hp + MAXLV);
+    for (int i = 0; i < 16; ++i) stats->ideal_bits += hb[i];
 }
 
 int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t n, int chunk_log2, uint16_t posq,
@@ -49,7 +68,7 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
     const bool want_bits = stats && (stats->flags & GPCC_STATS_IDEAL_BITS);   // the reference's bpp estimator (a14): on request only
     GP_TRY(ctx->side_init());
     hipStream_t sd = ctx->side;
-    struct SideGuard { hipStream_t s; ~SideGuard() { (void)hipStreamSynchronize(s); } } side_guard{sd};   // error returns leave nothing in flight
+    SideGuard side_guard{sd, nullptr};
     Tree T;
     {
         StageTimer tm(ctx, st, ST_OCTREE, 0.0);
@@ -77,122 +96,25 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
     constexpr int NCOUNTERS = MAXLV + 16;   // pairs per level, then 16 accumulators of the ideal code length
     TAKE(pairs_dev, unsigned long long, NCOUNTERS);
     HIP_TRY(hipMemsetAsync(pairs_dev, 0, sizeof(unsigned long long) * NCOUNTERS, st));
-    // Encoding is teacher-forced, so every level is independent of the others: all parent levels are
-    // concatenated into one "prior set" P (levels 0..L-2) and all coded levels into one "target set" C
-    // (levels 1..L-1).  Each of the 18 network layers is then ONE launch over a set instead of one per level.
-    int64_t nP = 0;
-    for (int d = 0; d + 1 < L; ++d) nP += T.lv[d].n;
-    const int64_t nC = coded;
     if (L > 1) {
-        int64_t pb[MAXLV] = {0}, cbase[MAXLV] = {0};
-        for (int d = 1; d < L; ++d) { pb[d] = pb[d - 1] + T.lv[d - 1].n; }
-        for (int d = 2; d < L; ++d) { cbase[d] = cbase[d - 1] + T.lv[d - 1].n; }
-        TAKE(occP, uint8_t, nP); TAKE(occC, uint8_t, nC); TAKE(rkeyC, uint64_t, nC);
-        TAKE(parentC, uint32_t, nC); TAKE(posC, uint32_t, nC); TAKE(slotsC, uint32_t, nC);
-        SetLevels S = {};
-        {
-            S.L = L;
-            int64_t lohi_base = 0;
-            for (int d = 0; d < L; ++d) {
-                const Level *lv = &T.lv[d];
-                S.n[d] = (uint32_t)lv->n; S.pb[d] = (uint32_t)pb[d]; S.cbase[d] = (uint32_t)cbase[d];
-                S.occ[d] = lv->occ; S.rkey[d] = lv->rkey; S.parent[d] = lv->parent; S.m2r[d] = lv->m2r;
-                if (d) {
-                    S.lohi_base[d] = (uint32_t)lohi_base; S.slots[d] = (uint32_t)slots(lv->n); S.clog[d] = clog(lv->n);
-                    S.nch[d] = plan(lv->n).nlanes;
-                    lohi_base += 4 * slots(lv->n);
-                }
-            }
-            StageTimer tm(ctx, st, ST_ELEM, (double)nP * 2 + (double)nC * (2 + 16 + 8));
-            k_set_rows<<<(unsigned)cdiv(std::max(nP, nC), 256), 256, 0, st>>>(S, nP, nC, occP, occC, rkeyC, parentC);
-            LAUNCH_CHECK();
+        PosLevels PL = {};
+        PL.L = L;
+        int64_t lohi_base = 0, cbase = 0;
+        for (int d = 1; d < L; ++d) {
+            const Level *lv = &T.lv[d];
+            PL.cbase[d] = (uint32_t)cbase; PL.m2r[d] = lv->m2r;
+            PL.lohi_base[d] = (uint32_t)lohi_base; PL.slots[d] = (uint32_t)slots(lv->n); PL.clog[d] = clog(lv->n); PL.nch[d] = plan(lv->n).nlanes;
+            lohi_base += 4 * slots(lv->n); cbase += lv->n;
         }
-        HIP_TRY(hipEventRecord(ctx->ev_main, st));   // the tree is complete on st
-        // Second stream: the raster ranks of every level and what depends on them (the coder slots of the rows of C).
-        // Their first reader is the head of stage 0, eighteen convolutions away; temporaries come from the top of the
-        // arena (Arena::flip), which nothing else in an encode uses.  The ~190 small launches cost the host 0.4 ms to queue:
-        // that happens behind the first trunk's launches, when the device has milliseconds of work in hand.
-        const std::function<int()> queue_ranks = [&]() -> int {
-            HIP_TRY(hipStreamWaitEvent(sd, ctx->ev_main, 0));
-            ctx->arena.flip = true;
-            int rc = GPCC_OK;
-            {
-                StageTimer tm(ctx, sd, ST_OCTREE, 0.0);
-                rc = tree_ranks(ctx, sd, &T);
-            }
-            ctx->arena.flip = false;
-            GP_TRY(rc);
-            {
-                StageTimer tm(ctx, sd, ST_ELEM, (double)nC * (4 + 8));
-                k_set_pos<<<(unsigned)cdiv(nC, 256), 256, 0, sd>>>(S, nC, posC, slotsC);
-                LAUNCH_CHECK();
-            }
-            HIP_TRY(hipEventRecord(ctx->ev_side, sd));
+        EncodeNet net = {&T, nullptr, nullptr, pairs_dev, lohi, want_bits ? reinterpret_cast<double *>(pairs_dev + MAXLV) : nullptr};   // bits: the 16 slots behind the pair counters
+        net.ranks = [&](hipStream_t s) { return tree_ranks(ctx, s, &T); };
+        net.set_pos = [&](hipStream_t s, uint32_t *posC, uint32_t *slotsC) -> int {
+            k_set_pos<<<(unsigned)cdiv(coded, 256), 256, 0, s>>>(PL, coded, posC, slotsC);
+            LAUNCH_CHECK();
             return GPCC_OK;
         };
-        ht.mark("enc meta queued");
-        // Tile lists of every level in one pool, built top-down from the cell maps (tiles.hip; one stream sync for the pool
-        // size).  A level's list is the same in the prior and in the target set -- tile entries are row indices inside the
-        // level -- so the two sets are two views of the pool: levels 0..L-2 and 1..L-1.
-        ConvTiles tilesP, tilesC;
-        {
-            const int NPc = cell_map_entries(m->k);
-            TileLevel tl[MAXLV];
-            const int32_t *cell_prev = nullptr;
-            for (int d = 0; d < L; ++d) {
-                int32_t *own = nullptr;
-                if (d + 1 < L) { TAKE(cm, int32_t, (int64_t)NPc * T.lv[d].n); own = cm; }
-                tl[d] = TileLevel{&T.lv[d], d ? &T.lv[d - 1] : nullptr, cell_prev, own};
-                cell_prev = own;
-            }
-            const int R = conv_pick_rows(nC, m->k), H = conv_pick_height(nC, R);
-            TilePool pool;
-            StageTimer tm(ctx, st, ST_TILES, 0.0);
-            GP_TRY(tiles_build(ctx, st, tl, L, m->k, R, H, &pool, pairs_dev));
-            GP_TRY(tiles_view(ctx, st, pool, 0, L - 1, pb, &tilesP));
-            GP_TRY(tiles_view(ctx, st, pool, 1, L, cbase + 1, &tilesC));
-            tm.add_bytes(pool.alg_bytes);
-        }
-        ht.mark("enc tiles built");
-        TAKE(pF, float, nP * m->C); TAKE(pA, float, nP * m->C); TAKE(pB, float, nP * m->C);
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nP * 129); GP_TRY(embed_occ(st, m->prior_emb, occP, nP, pF, m->C)); }
-        GP_TRY(run_trunk(ctx, 0, st, m, 0, Trunk{pF, pA, pB}, tilesP, nP));           // -> pA
-        GP_TRY(queue_ranks());   // the device now has milliseconds of convolutions queued: the host time of these launches is free
-        TAKE(cX, float, nC * m->C); TAKE(cA, float, nC * m->C); TAKE(cB, float, nC * m->C);
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nC * (128 + 12 + 128)); GP_TRY(child_features(st, pA, parentC, rkeyC, m->temb, nC, cX, m->C)); }
-        GP_TRY(run_trunk(ctx, 1, st, m, 5, Trunk{cX, cA, cB}, tilesC, nC));           // -> cA  (X of pcc_utils.py:109)
-        // stages: cX, cB are free now; inputs u[s], mid v[s], outputs y[s]
-        TAKE(u1, float, nC * m->C); TAKE(u2, float, nC * m->C); TAKE(u3, float, nC * m->C);
-        TAKE(v1, float, nC * m->C); TAKE(v2, float, nC * m->C);
-        float *u[4] = {cA, u1, u2, u3};
-        float *v[4] = {cX, cB, v1, v2};
-        {
-            const float *const embs[3] = {m->semb[0], m->semb[1], m->semb[2]};
-            float *const outs[3] = {u1, u2, u3};
-            StageTimer tm(ctx, st, ST_ELEM, (double)nC * (128 + 1 + 3 * 128));
-            GP_TRY(stage_inputs_gt(st, cA, embs, occC, nC, outs, m->C));
-        }
-        ConvBatch cb = {}; cb.C = m->C;
-        for (int s = 0; s < 4; ++s) cb.job[s] = ConvJob{u[s], m->conv[10 + 2 * s], nullptr, v[s]};
-        GP_TRY(sparse_conv(ctx, 1, st, cb, 4, tilesC, nC, 1));
-        TAKE(y0, float, nC * m->C);
-        float *y[4] = {y0, u1, u2, u3};
-        for (int s = 0; s < 4; ++s) cb.job[s] = ConvJob{v[s], m->conv[10 + 2 * s + 1], nullptr, y[s]};
-        GP_TRY(sparse_conv(ctx, 1, st, cb, 4, tilesC, nC, 0));
-        GP_TRY(dbg_mark(ctx, st, 1, pA, (size_t)nP * 128)); GP_TRY(dbg_mark(ctx, st, 2, cA, (size_t)nC * 128));
-        for (int s = 0; s < 4; ++s) GP_TRY(dbg_mark(ctx, st, 3 + s, y[s], (size_t)nC * 128));
-        HIP_TRY(hipStreamWaitEvent(st, ctx->ev_side, 0));   // ranks -> posC / slotsC
-        GP_TRY(dbg_mark(ctx, st, 7, posC, (size_t)nC * 4)); GP_TRY(dbg_mark(ctx, st, 8, slotsC, (size_t)nC * 4));
-        ctx->arena.release_top_low();                       // what is enqueued on st from here on runs behind the rank pass: its temporaries are free
-        StageTimer tm_heads(ctx, st, ST_HEADS, (double)nC * 4 * (128 + 1 + 8 + 4));
-        for (int s = 0; s < 4; ++s) {
-            HeadArgs ha = {}; ha.C = m->C;
-            ha.x = y[s]; ha.n = nC; ha.stage_m = STAGE_M[s];
-            ha.w1 = m->hw1[s]; ha.b1 = m->hb1[s]; ha.w2 = m->hw2[s]; ha.b2 = m->hb2[s]; ha.frag = m->hfrag[s];
-            ha.occ = occC; ha.stage = s; ha.lohi = lohi; ha.mode = 0; ha.pos = posC; ha.slots = slotsC;
-            ha.bits = want_bits ? reinterpret_cast<double *>(pairs_dev + MAXLV) : nullptr;   // the 16 slots behind the pair counters
-            GP_TRY(head_cdf(st, ha));
-        }
+        net.ht = &ht; net.trace = "enc";
+        GP_TRY(encode_network(ctx, m, st, sd, net));
     }
     // ---- range coder over every lane of every stream
     const int nstreams = 4 * (L - 1);
@@ -201,6 +123,7 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
     // words come down once, the streams (independent in an encode) are coded on a pool of native threads, the container is put together here.
     // GAUSPCC_V0_DEVICE_CODER=1 (developer knob): the one-lane-per-stream device path below, kept as the cross-check.
     static const bool v0_device = dev_env_int("GAUSPCC_V0_DEVICE_CODER", 0) != 0;
+    const int64_t no_origin[3] = {0, 0, 0};   // level_to_raster hands the base level back in the cloud's own coordinates
     if (!chunk_log2 && !v0_device) {
         const Level *base = &T.lv[0];
         TAKE(base_xyz, int32_t, 3 * base->n);
@@ -238,12 +161,8 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
         for (int si = 0; si < nstreams; ++si) fsize += 4 + sb[(size_t)si].size();
         GP_TRY(ctx->hbytes.reserve(fsize + 16));
         uint8_t *out = ctx->hbytes.p;
-        size_t pos = 0;
-        out[0] = (uint8_t)posq; out[1] = (uint8_t)(posq >> 8); pos = 2;
-        put32(out + pos, (uint32_t)base->n); pos += 4;
-        memcpy(out + pos, hc + off_bx, 12 * (size_t)base->n); pos += 12 * (size_t)base->n;
-        memcpy(out + pos, hc + off_bo, (size_t)base->n); pos += (size_t)base->n;
-        out[pos] = (uint8_t)nstreams; out[pos + 1] = (uint8_t)(nstreams >> 8); pos += 2;
+        out[0] = (uint8_t)posq; out[1] = (uint8_t)(posq >> 8);
+        size_t pos = 2 + base_block_put(out + 2, base->n, reinterpret_cast<const int32_t *>(hc + off_bx), no_origin, hc + off_bo, nstreams);
         for (int si = 0; si < nstreams; ++si) {
             const std::vector<uint8_t> &b = sb[(size_t)si];
             put32(out + pos, (uint32_t)b.size()); pos += 4;
@@ -253,26 +172,17 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
         if (pos != fsize) return fail(GPCC_ERR_HIP, "internal: container size mismatch (%zu vs %zu)", pos, fsize);
         if (ctx->prof.on && ctx->prof.stages) ctx->prof.stage_bytes[ST_CODER] += 3.0 * (double)(fsize - (2 + 4 + 13 * (size_t)base->n + 2 + 4 * (size_t)nstreams));
         const unsigned long long *hp = reinterpret_cast<const unsigned long long *>(hc + off_pairs);
-        unsigned long long set_pairs[2] = {0, 0};
-        for (int d = 0; d < L; ++d) { if (d + 1 < L) set_pairs[0] += hp[d]; if (d) set_pairs[1] += hp[d]; }
+        unsigned long long set_pairs[2];
+        sum_set_pairs(hp, L, set_pairs);
         if (ctx->prof.on) GP_TRY(prof_collect(ctx, set_pairs, 2));
         *bytes_out = out; *nbytes_out = (int64_t)pos;
-        if (stats) {
-            memset(stats, 0, sizeof *stats);
-            stats->num_points = n; stats->num_bytes = (int64_t)pos; stats->num_levels = L; stats->coded_nodes = coded;
-            for (int d = 0; d < L; ++d) stats->level_nodes[d] = T.lv[d].n;
-            stats->conv_pairs = (int64_t)set_pairs[0] * 5 + (int64_t)set_pairs[1] * 13;
-            const double *hb = reinterpret_cast<const double *>(hp + MAXLV);
-            for (int i = 0; i < 16; ++i) stats->ideal_bits += hb[i];
-        }
+        if (stats) fill_stats(stats, n, pos, T, coded, set_pairs, hp);
         return GPCC_OK;
     }
-    std::vector<RcChunk> chunks;         // one descriptor per lane
+    LaneList lanes;
     std::vector<uint32_t> gaps;          // reference layout: container bytes in front of a lane's payload that are not payload (the stream lengths);
                                          // chunked: the stream of every lane (the gaps depend on the byte counts: rc_layout_launch)
     std::vector<uint32_t> stream_first(nstreams + 1, 0);
-    uint32_t max_syms = 1;
-    size_t table_bound = 0;              // most bytes the chunk tables can take
     {
         int64_t pre = 0; int si = 0;
         uint32_t gap = 0;
@@ -280,22 +190,18 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
             const int64_t nc = T.lv[d].n;
             const RcPlan pl = plan(nc);
             for (int s = 0; s < 4; ++s, ++si) {
-                stream_first[si] = (uint32_t)chunks.size();
-                const int64_t base = pre + (int64_t)s * slots(nc);
+                stream_first[si] = (uint32_t)lanes.chunks.size();
                 gap += 4u;
-                table_bound += 6 * (size_t)pl.nchunks + 8;   // escape code: 48 bits a chunk; first count + k
-                if (pl.dual && ((base & 1) || pl.llog < 4)) return fail(GPCC_ERR_HIP, "internal: stream %d starts on an odd slot or has lanes below 16 symbols", si);   // k_rc_compact tells a chunk's backwards lane by the parity of RcChunk::first; k_rc_decode_lds stores 16 symbols at a time
-                for (uint32_t c = 0; c < pl.nlanes; ++c) {
-                    const int64_t cn = pl.lane_syms(nc, c);
-                    gaps.push_back(chunk_log2 ? (uint32_t)si : gap);
-                    chunks.push_back(RcChunk{(uint32_t)(base + c), pl.nlanes, (uint32_t)cn, 0, 0, 0});
-                    max_syms = std::max<uint32_t>(max_syms, (uint32_t)cn);
-                }
+                GP_TRY(lanes_append(&lanes, si, pre + (int64_t)s * slots(nc), nc, pl));
+                gaps.insert(gaps.end(), pl.nlanes, chunk_log2 ? (uint32_t)si : gap);
             }
             pre += 4 * slots(nc);
         }
-        stream_first[nstreams] = (uint32_t)chunks.size();
+        stream_first[nstreams] = (uint32_t)lanes.chunks.size();
     }
+    const std::vector<RcChunk> &chunks = lanes.chunks;
+    const uint32_t max_syms = lanes.max_syms;
+    const size_t table_bound = lanes.table_bound;
     const int nchunks = (int)chunks.size();
     const Level *base = &T.lv[0];
     TAKE(base_xyz, int32_t, 3 * base->n);
@@ -367,36 +273,27 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
     const uint32_t *hcnt = reinterpret_cast<const uint32_t *>(hs + off_cnt);
     if (nchunks) total_payload = hcnt[nchunks];
     if (ctx->prof.on && ctx->prof.stages) ctx->prof.stage_bytes[ST_CODER] += 3.0 * total_payload;
-    // pairs of the two sets (the conv launches are tagged 0 = prior set, 1 = target set)
-    unsigned long long set_pairs[2] = {0, 0};
-    {
-        const unsigned long long *hp = reinterpret_cast<const unsigned long long *>(hs + off_pairs);
-        for (int d = 0; d < L; ++d) { if (d + 1 < L) set_pairs[0] += hp[d]; if (d) set_pairs[1] += hp[d]; }
-    }
+    const unsigned long long *hp = reinterpret_cast<const unsigned long long *>(hs + off_pairs);
+    unsigned long long set_pairs[2];
+    sum_set_pairs(hp, L, set_pairs);
     if (ctx->prof.on) GP_TRY(prof_collect(ctx, set_pairs, 2));
     // ---- container
     // per stream: table bytes and payload bytes, from the lane byte counts
-    std::vector<size_t> s_tab((size_t)nstreams, 0), s_pay((size_t)nstreams, 0);
+    std::vector<StreamSize> ssz((size_t)nstreams);
     size_t tables = 0;
     for (int si = 0; si < nstreams; ++si) {
-        const int c0 = (int)stream_first[si], c1 = (int)stream_first[si + 1];
-        for (int c = c0; c < c1; ++c) s_pay[(size_t)si] += hcnt[c];
-        if (chunk_log2) {   // never write a chunk the staged decoder could not hold (rangecoder.hpp: rc_window_fits)
-            const int stage_lp[4] = {STAGE_M[0] + 1, STAGE_M[1] + 1, STAGE_M[2] + 1, STAGE_M[3] + 1};
-            uint32_t mb = 0;
-            for (int c = c0; c < c1; c += 2) mb = std::max(mb, hcnt[c] + (c + 1 < c1 ? hcnt[c + 1] : 0u));
-            // (GAUSPCC_TEST_CHUNK_BYTES: a test's stand-in for the window, so that the re-encode with smaller chunks is seen working
-            // on an ordinary cloud: tests/test_gpu_parity.py)
-            static const uint32_t test_cap = (uint32_t)env_int("GAUSPCC_TEST_CHUNK_BYTES", 0);
-            if (!rc_window_fits(stage_lp[si & 3], mb) || (test_cap && mb > test_cap && chunk_log2 > 7)) {
-                // (possible only at chunk_log2 >= 13 with a model that spends > 8 bits per 16-ary symbol: gpcc_encode codes the cloud again with smaller chunks)
-                (void)fail(GPCC_ERR_ARG, "a chunk of stream %d takes %u bytes, more than the decoder's window holds at chunk_log2 = %d: use a smaller chunk_log2", si, mb, chunk_log2);
-                return ENC_RETRY_SMALLER_CHUNKS;
-            }
+        const StreamSize z = stream_size(hcnt, (int)stream_first[si], (int)stream_first[si + 1], si, chunk_log2 != 0);
+        // (GAUSPCC_TEST_CHUNK_BYTES: a test's stand-in for the window, so that the re-encode with smaller chunks is seen working
+        // on an ordinary cloud: tests/test_gpu_parity.py)
+        static const uint32_t test_cap = (uint32_t)env_int("GAUSPCC_TEST_CHUNK_BYTES", 0);
+        if (!z.fits || (chunk_log2 > 7 && test_cap && z.max_chunk > test_cap)) {
+            // never write a chunk the staged decoder could not hold
+            // (possible only at chunk_log2 >= 13 with a model that spends > 8 bits per 16-ary symbol: gpcc_encode codes the cloud again with smaller chunks)
+            (void)fail(GPCC_ERR_ARG, "a chunk of stream %d takes %u bytes, more than the decoder's window holds at chunk_log2 = %d: use a smaller chunk_log2", si, z.max_chunk, chunk_log2);
+            return ENC_RETRY_SMALLER_CHUNKS;
         }
-        if (chunk_log2)
-            s_tab[(size_t)si] = rc_table_size([&](uint32_t c) { const int l = c0 + 2 * (int)c; return hcnt[l] + (l + 1 < c1 ? hcnt[l + 1] : 0u); }, (uint32_t)((c1 - c0 + 1) / 2));
-        tables += s_tab[(size_t)si];
+        ssz[(size_t)si] = z;
+        tables += z.tab;
     }
     size_t fsize = pos0_hdr + 4 * (size_t)nstreams + total_payload + tables;
     if (direct) { if (fsize + 16 > ctx->hbytes.cap) return fail(GPCC_ERR_HIP, "internal: payload beyond its bound"); }
@@ -404,17 +301,13 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
     uint8_t *out = ctx->hbytes.p;
     size_t pos = 0;
     if (chunk_log2) {
-        out[0] = 0xFF; out[1] = 0xFF; out[2] = (uint8_t)CONTAINER_VERSION; out[3] = (uint8_t)chunk_log2; out[4] = (uint8_t)posq; out[5] = (uint8_t)(posq >> 8); out[6] = (uint8_t)L; out[7] = 0;
-        pos = 8;
-        for (int d = 0; d < L; ++d) { put32(out + pos, (uint32_t)T.lv[d].n); pos += 4; }
-        put32(out + pos, (uint32_t)n); pos += 4;
+        int64_t level_nodes[MAXLV];
+        for (int d = 0; d < L; ++d) level_nodes[d] = T.lv[d].n;
+        pos = chunked_header_put(out, CONTAINER_VERSION, chunk_log2, posq, L, level_nodes, n);
     } else {
         out[0] = (uint8_t)posq; out[1] = (uint8_t)(posq >> 8); pos = 2;
     }
-    put32(out + pos, (uint32_t)base->n); pos += 4;
-    memcpy(out + pos, hs + off_bx, 12 * (size_t)base->n); pos += 12 * (size_t)base->n;
-    memcpy(out + pos, hs + off_bo, (size_t)base->n); pos += (size_t)base->n;
-    out[pos] = (uint8_t)nstreams; out[pos + 1] = (uint8_t)(nstreams >> 8); pos += 2;
+    pos += base_block_put(out + pos, base->n, reinterpret_cast<const int32_t *>(hs + off_bx), no_origin, hs + off_bo, nstreams);
     // the payload comes straight from the device into its final place in one copy; the stream lengths and chunk tables
     // are then written into the gaps it left
     {
@@ -423,26 +316,14 @@ int encode_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz, int64_t 
         if (body && !direct) { HIP_TRY(hipMemcpyAsync(out + pos0, payload_dev, body, hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); }
         size_t p = pos0;
         for (int si = 0; si < nstreams; ++si) {
-            const int c0 = (int)stream_first[si], c1 = (int)stream_first[si + 1];
-            put32(out + p, (uint32_t)(s_tab[(size_t)si] + s_pay[(size_t)si])); p += 4;
-            if (chunk_log2)
-                p += rc_table_put(out + p, [&](uint32_t c) { const int l = c0 + 2 * (int)c; return hcnt[l] + (l + 1 < c1 ? hcnt[l + 1] : 0u); }, (uint32_t)((c1 - c0 + 1) / 2));
-            p += s_pay[(size_t)si];
+            p += stream_head_put(out + p, hcnt, (int)stream_first[si], (int)stream_first[si + 1], ssz[(size_t)si], chunk_log2 != 0) + ssz[(size_t)si].pay;
         }
         pos = p;
     }
     ht.mark("enc payload d2h");
     if (pos != fsize) return fail(GPCC_ERR_HIP, "internal: container size mismatch (%zu vs %zu)", pos, fsize);
     *bytes_out = out; *nbytes_out = (int64_t)pos;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->num_points = n; stats->num_bytes = (int64_t)pos; stats->num_levels = L; stats->coded_nodes = coded;
-        const unsigned long long *hp = reinterpret_cast<const unsigned long long *>(hs + off_pairs);
-        for (int d = 0; d < L; ++d) stats->level_nodes[d] = T.lv[d].n;
-        stats->conv_pairs = (int64_t)set_pairs[0] * 5 + (int64_t)set_pairs[1] * 13;   // prior set: 5 convs, target set: 5 + 8
-        const double *hb = reinterpret_cast<const double *>(hp + MAXLV);
-        for (int i = 0; i < 16; ++i) stats->ideal_bits += hb[i];
-    }
+    if (stats) fill_stats(stats, n, pos, T, coded, set_pairs, hp);
     return GPCC_OK;
 }
 
@@ -482,8 +363,8 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
     // internal frame (octree.hpp: Tree::bias): 2^20 when the whole cloud lies inside (-2^20, 2^20), else the base level's own
     // minimum per axis -- in leaf units a multiple of 2^L, which is all the tree needs
     int64_t bias_base[3] = {CB >> L, CB >> L, CB >> L}, bias_leaf[3] = {CB, CB, CB};
+    int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
     {
-        int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
         for (int64_t i = 0; i < bn; ++i)
             for (int a = 0; a < 3; ++a) { const int64_t c = (int32_t)get32(bxyz + 12 * i + 4 * a); lo[a] = std::min(lo[a], c); hi[a] = std::max(hi[a], c); }
         bool inside = true;
@@ -491,39 +372,18 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
         if (!inside)
             for (int a = 0; a < 3; ++a) { bias_base[a] = -lo[a]; bias_leaf[a] = -lo[a] * ((int64_t)1 << L); }
     }
-    struct BN { uint64_t mk, rk; uint8_t occ; };
-    std::vector<BN> bnodes((size_t)bn);
-    uint32_t mn[3] = {~0u, ~0u, ~0u}, mx[3] = {0, 0, 0};
-    for (int64_t i = 0; i < bn; ++i) {
-        uint32_t b[3];
-        for (int a = 0; a < 3; ++a) {
-            const int64_t c = (int32_t)get32(bxyz + 12 * i + 4 * a) + bias_base[a];
-            if (c < 0 || c >= ((int64_t)1 << (21 - L))) return fail(GPCC_ERR_FORMAT, "base coordinate out of range");
-            b[a] = (uint32_t)c; mn[a] = std::min(mn[a], b[a]); mx[a] = std::max(mx[a], b[a]);
-        }
-        bnodes[(size_t)i] = BN{morton3(b[0], b[1], b[2]), rkey3(b[0], b[1], b[2]), bocc[i]};
-        if (!bocc[i]) return fail(GPCC_ERR_FORMAT, "empty base occupancy");
-    }
-    std::sort(bnodes.begin(), bnodes.end(), [](const BN &a, const BN &b) { return a.mk < b.mk; });
-    for (int64_t i = 1; i < bn; ++i) if (bnodes[(size_t)i].mk == bnodes[(size_t)i - 1].mk) return fail(GPCC_ERR_FORMAT, "duplicate base node");
-    int hb = 1;
-    for (int a = 0; a < 3; ++a) { int b = 0; uint32_t v = mn[a] ^ mx[a]; while (v) { ++b; v >>= 1; } hb = std::max(hb, b); }
+    std::vector<BaseNode> bnodes;
+    GP_TRY(base_nodes_append(bxyz, bocc, bn, bias_base, (int64_t)1 << (21 - L), "", &bnodes));
+    int hb = 1;   // varying low bits per axis of the base level
+    for (int a = 0; a < 3; ++a) { int b = 0; uint64_t v = (uint64_t)(lo[a] + bias_base[a]) ^ (uint64_t)(hi[a] + bias_base[a]); while (v) { ++b; v >>= 1; } hb = std::max(hb, b); }
 
     // ---- device state
-    auto alloc_level = [&](Level *lv, int64_t n, int lvl) -> int {
-        lv->n = n; lv->lvl = lvl;
-        TAKE(rkey, uint64_t, n); TAKE(occ, uint8_t, n); TAKE(cstart, uint32_t, n + 1); TAKE(parent, uint32_t, n); TAKE(m2r, uint32_t, n); TAKE(r2m, uint32_t, n);
-        lv->rkey = rkey; lv->occ = occ; lv->cstart = cstart; lv->parent = parent; lv->m2r = m2r; lv->r2m = r2m;
-        // the arrays are carved back to back: level_expand_rank zeroes them with ONE memset over this recorded span
-        lv->span0 = reinterpret_cast<char *>(rkey); lv->span_bytes = (size_t)(reinterpret_cast<char *>(r2m + n) - reinterpret_cast<char *>(rkey));
-        return GPCC_OK;
-    };
     // the container goes up on a stream of its own: the first reader is the range decoder of the first coded level, behind a
     // parent trunk, the structure of that level and its own trunk (the copy was the first ~0.2 ms of every decode on st)
     TAKE(dbytes, uint8_t, nbytes + 16);
     GP_TRY(ctx->side_init());
     hipStream_t sd = ctx->side;
-    struct SideGuard { hipStream_t s, x; ~SideGuard() { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(x); } } side_guard{sd, ctx->xfer};   // error returns leave nothing in flight
+    SideGuard side_guard{sd, ctx->xfer};
     HIP_TRY(hipMemcpyAsync(dbytes, in, (size_t)nbytes, hipMemcpyHostToDevice, ctx->xfer));
     HIP_TRY(hipEventRecord(ctx->ev_bytes, ctx->xfer));
     // lane descriptors of every level are staged in pinned memory that is written once (no reuse, so no sync before
@@ -568,7 +428,7 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
         return GPCC_OK;
     };
     Level cur;
-    GP_TRY(alloc_level(&cur, bn, L));
+    GP_TRY(alloc_level(ctx, &cur, bn, L));
     {
         uint64_t *hr = reinterpret_cast<uint64_t *>(ctx->hstage.p + 1024);
         uint8_t *ho = ctx->hstage.p + 1024 + 8 * (size_t)bn;
@@ -617,23 +477,8 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
         const size_t top_mk = ctx->arena.top_mark();
         const int64_t np = cur.n;
         // ---- st: parent trunk
-        TAKE_TOP(pF, float, np * m->C); TAKE_TOP(pA, float, np * m->C); TAKE_TOP(pB, float, np * m->C);
-        float *Pp = nullptr;
-        if (planP.valid()) { TAKE_TOP(pp, float, planP.pcap * 32); Pp = pp; }
-        if (planP.valid() && fmode == 1) {
-            // (profiling: a persistent launch counts as the convolutions it contains -- 5 here, 13 for a level's chain -- over its whole
-            // time, heads / coder phases and barriers included: the conv roofline figure stays conservative)
-            ConvRec rec = {0, 0, g, 1, 0, 0, (long long)np, 0, 5, 1};
-            if (ctx->prof.on) GP_TRY(prof_event(ctx, st, &rec.e0));
-            GP_TRY(fused_parent_trunk(ctx, st, m, planP, planP_np, cur.occ, pF, pA, pB, Pp));
-            if (ctx->prof.on) { GP_TRY(prof_event(ctx, st, &rec.e1)); ctx->prof.recs.push_back(rec); }
-            any_fused = true;
-        } else {
-            { StageTimer tm(ctx, st, ST_ELEM, (double)np * 129); GP_TRY(embed_occ(st, m->prior_emb, cur.occ, np, pF, m->C)); }
-            GP_TRY(dbg_mark(ctx, st, g * 100 + 1, pF, (size_t)np * 128));
-            GP_TRY(run_trunk(ctx, g, st, m, 0, Trunk{pF, pA, pB}, tilesP, np, planP.valid() ? &planP : nullptr, Pp));
-        }
-        GP_TRY(dbg_mark(ctx, st, g * 100 + 2, pA, (size_t)np * 128));
+        float *pA = nullptr;
+        GP_TRY(dec_parent_trunk(ctx, st, m, g, cur.occ, np, tilesP, planP, planP_np, fmode, &pA, &any_fused));
         // ---- side: the child level's structure
         HIP_TRY(hipStreamWaitEvent(sd, ctx->ev_main, 0));
         Level chi;
@@ -646,7 +491,7 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
             lvl_n[g + 1] = nc;
         }
         if (nc <= 0 || nc > 8 * cur.n) return fail(GPCC_ERR_FORMAT, "bad node count at level %d", g + 1);
-        GP_TRY(alloc_level(&chi, nc, L - g - 1));
+        GP_TRY(alloc_level(ctx, &chi, nc, L - g - 1));
         {
             const int hbl = std::min(21, std::max(1, hb + g + 1));
             StageTimer tm(ctx, sd, ST_OCTREE, (double)np * 13 + (double)nc * 12 + (double)cdiv(3 * hbl, 8) * (double)nc * 24 + (double)nc * 8);
@@ -663,18 +508,7 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
         ConvTiles tilesC;
         PairPlan planC;
         const bool child_plan = fuse_ctx && fused_level_ok(nc, m->k) && pl.dual == (version >= 3) && fused_windows_fit(nc, cur.n, pl.nlanes, win_bytes[g]);
-        if (child_plan) {
-            StageTimer tm(ctx, sd, ST_TILES, 0.0);
-            GP_TRY(pairplan_build(ctx, sd, &cur, cellP, &chi, cellC, m->k, &planC, pairs_dev + g + 1));
-        } else {
-            const TileLevel tl = {&chi, &cur, cellP, cellC};
-            const int R = conv_pick_rows(nc, m->k);
-            TilePool pool;
-            StageTimer tm(ctx, sd, ST_TILES, 0.0);
-            GP_TRY(tiles_build(ctx, sd, &tl, 1, m->k, R, conv_pick_height(nc, R), &pool, pairs_dev + g + 1));
-            GP_TRY(tiles_view(ctx, sd, pool, 0, 1, zero_base, &tilesC));
-            tm.add_bytes(pool.alg_bytes);
-        }
+        GP_TRY(dec_child_lists(ctx, sd, m, &cur, cellP, &chi, cellC, child_plan, pairs_dev + g + 1, &planC, &tilesC));
         GP_TRY(dbg_mark(ctx, sd, g * 100 + 3, chi.rkey, (size_t)nc * 8)); GP_TRY(dbg_mark(ctx, sd, g * 100 + 4, chi.parent, (size_t)nc * 4));
         GP_TRY(dbg_mark(ctx, sd, g * 100 + 5, chi.m2r, (size_t)nc * 4));
         if (!child_plan) { GP_TRY(dbg_mark(ctx, sd, g * 100 + 6, tilesC.first, (size_t)(tilesC.nblk + 1) * 4)); GP_TRY(dbg_mark(ctx, sd, g * 100 + 7, tilesC.order, (size_t)tilesC.nblk * 4)); }
@@ -694,56 +528,21 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
             dchunks = dch;
         }
         // ---- st: child trunk and the four stages
-        TAKE_TOP(cX, float, nc * m->C); TAKE_TOP(cA, float, nc * m->C); TAKE_TOP(cB, float, nc * m->C); TAKE_TOP(cU, float, nc * m->C);
-        float *Pc = nullptr;
-        if (child_plan) { TAKE_TOP(pc, float, planC.pcap * 32); Pc = pc; }
-        TAKE_TOP(cdf, uint16_t, rc_rows_capacity(nch, S) * 16);  // interleaved rows + the decoder's look-ahead
-        uint8_t *sym[4];
-        for (int s = 0; s < 4; ++s) { TAKE_TOP(sy, uint8_t, nc + 4); sym[s] = sy; }   // + the last group of four of the last lane
+        LevelCoder lc = {nullptr, nullptr, (uint32_t)nch, clog, dchunks, {win_bytes[g][0], win_bytes[g][1], win_bytes[g][2], win_bytes[g][3]}, pl.dual, rc_coder_of_version(version)};
+        ChildBufs cb;
+        GP_TRY(child_bufs_take(ctx, m, nc, child_plan ? planC.pcap : 0, lc.nlanes, S, nc + 4, &cb));   // symbols: + the last group of four of the last lane
+        uint8_t *const *sym = cb.sym;
+        uint16_t *const cdf = cb.cdf;
         if (child_plan && fmode == 1) {
-            // the level's whole chain in one persistent launch (fused.hip)
             if (g == 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_bytes, 0));
             if (g == TAB_EARLY) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_tables, 0));
-            FusedChild fa = {};
-            fa.pA = pA; fa.np = np; fa.parent = chi.parent; fa.rkey = chi.rkey; fa.m2r = chi.m2r; fa.bytes = dbytes; fa.chunks = dchunks; fa.nlanes = (uint32_t)nch; fa.llog = clog;
-            for (int s = 0; s < 4; ++s) { fa.win_bytes[s] = win_bytes[g][s]; fa.sym[s] = sym[s]; }
-            fa.cX = cX; fa.cA = cA; fa.cB = cB; fa.cU = cU; fa.P = Pc; fa.cdf = cdf; fa.occ = chi.occ; fa.coder = rc_coder_of_version(version);
-            ConvRec rec = {0, 0, g + 1, 1, 0, 0, (long long)nc, 0, 13, 1};
-            if (ctx->prof.on) GP_TRY(prof_event(ctx, st, &rec.e0));
-            GP_TRY(fused_child_level(ctx, st, m, planC, fa));
-            if (ctx->prof.on) { GP_TRY(prof_event(ctx, st, &rec.e1)); ctx->prof.recs.push_back(rec); }
+            GP_TRY(dec_child_fused(ctx, st, m, g, planC, pA, np, chi, dbytes, lc, cb));
             any_fused = true;
         } else {
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nc * (128 + 12 + 128)); GP_TRY(child_features(st, pA, chi.parent, chi.rkey, m->temb, nc, cX, m->C)); }
-        GP_TRY(dbg_mark(ctx, st, g * 100 + 8, cX, (size_t)nc * 128));
-        GP_TRY(run_trunk(ctx, g + 1, st, m, 5, Trunk{cX, cA, cB}, tilesC, nc, child_plan ? &planC : nullptr, Pc));  // -> cA
-        GP_TRY(dbg_mark(ctx, st, g * 100 + 9, cA, (size_t)nc * 128));
+        GP_TRY(dec_child_trunk(ctx, st, m, g, pA, chi, tilesC, child_plan ? &planC : nullptr, cb));
         for (int s = 0; s < 4; ++s) {
-            const float *xin = cA;
-            if (s) { StageTimer tm(ctx, st, ST_ELEM, (double)nc * (128 + 4 + s + 128)); GP_TRY(stage_input_dec(st, cA, m->semb[s - 1], sym, chi.m2r, s, nc, cU, m->C)); xin = cU; }
-            ConvBatch cb = {}; cb.C = m->C;
-            if (child_plan) {
-                GP_TRY(plan_conv(st, planC, ConvJob{xin, m->conv[10 + 2 * s], nullptr, cX}, Pc, 1));
-                GP_TRY(plan_conv(st, planC, ConvJob{cX, m->conv[10 + 2 * s + 1], nullptr, cB}, Pc, 0));
-            } else {
-            GP_TRY(conv_chain_begin(ctx, st));
-            cb.job[0] = ConvJob{xin, m->conv[10 + 2 * s], nullptr, cX};
-            GP_TRY(sparse_conv(ctx, g + 1, st, cb, 1, tilesC, nc, 1));
-            cb.job[0] = ConvJob{cX, m->conv[10 + 2 * s + 1], nullptr, cB};
-            GP_TRY(sparse_conv(ctx, g + 1, st, cb, 1, tilesC, nc, 0));
-            GP_TRY(conv_chain_end(ctx, st));
-            }
-            GP_TRY(dbg_mark(ctx, st, g * 100 + 10 + 5 * s, xin, (size_t)nc * 128)); GP_TRY(dbg_mark(ctx, st, g * 100 + 11 + 5 * s, cX, (size_t)nc * 128));
-            GP_TRY(dbg_mark(ctx, st, g * 100 + 12 + 5 * s, cB, (size_t)nc * 128));
-            HeadArgs ha = {}; ha.C = m->C;
-            ha.x = cB; ha.n = nc; ha.stage_m = STAGE_M[s];
-            ha.w1 = m->hw1[s]; ha.b1 = m->hb1[s]; ha.w2 = m->hw2[s]; ha.b2 = m->hb2[s]; ha.frag = m->hfrag[s];
-            ha.m2r = chi.m2r; ha.cdf = cdf; ha.mode = 1; ha.chunk_log2 = clog; ha.nch = (uint32_t)nch;
-            const int row_bytes = STAGE_M[s] == 2 ? 2 : STAGE_M[s] == 4 ? 8 : 32;     // compact CDF row
-            const size_t cdf_bytes = (size_t)rc_rows_capacity(nch, S) * 16 * 2;
-            if (ctx->dbg_on) HIP_TRY(hipMemsetAsync(cdf, 0, cdf_bytes, st));   // developer trace: rows the head does not write read as zeros
-            { StageTimer tm(ctx, st, ST_HEADS, (double)nc * (128 + 4 + row_bytes)); GP_TRY(head_cdf(st, ha)); }
-            GP_TRY(dbg_mark(ctx, st, g * 100 + 13 + 5 * s, cdf, cdf_bytes));
+            GP_TRY(dec_child_stage(ctx, st, m, g, s, chi, tilesC, child_plan ? &planC : nullptr, lc, cb));
+            const int row_bytes = stage_row_bytes(s);
             if (g == 0 && s == 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_bytes, 0));
             if (g == TAB_EARLY && s == 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_tables, 0));
             static const bool v0_device = dev_env_int("GAUSPCC_V0_DEVICE_CODER", 0) != 0;
@@ -845,14 +644,6 @@ int decode_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *in, int64_t n
 
 }  // namespace
 
-// developer / test knob: scales the first workspace estimate of both calls, so that the grow-and-retry path (a level of the
-// tree, the tile pool, the rank pass on the second stream or a feature buffer running out of arena) can be driven on purpose
-static size_t arena_scaled(size_t want)
-{
-    static const double scale = [] { const char *e = getenv("GAUSPCC_ARENA_SCALE"); const double v = e ? atof(e) : 1.0; return v > 0.0 ? v : 1.0; }();
-    return scale == 1.0 ? want : std::max<size_t>((size_t)((double)want * scale), (size_t)1 << 20);
-}
-
 extern "C" int gpcc_encode(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *xyz_dev, int64_t n, int chunk_log2, uint16_t posq_f16,
                            const uint8_t **bytes_out, int64_t *nbytes_out, gpcc_stats *stats, void *stream)
 {
@@ -912,8 +703,7 @@ static int decode_entry(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *bytes
         GP_TRY(ctx->arena.reserve(want));
         rc = decode_body(ctx, m, bytes, nbytes, &xyz, n_out, posq_f16_out, stats, st, out_user, out_cap);
         if (rc == DEC_RETRY_UNFUSED) {
-            static const bool loud = getenv("GAUSPCC_FUSED_QUIET") == nullptr;
-            if (loud) fprintf(stderr, "[gauspcc] a persistent small-level launch timed out on device %d; the launch-per-layer path serves this context's next %d decodes\n", ctx->device, ctx->fused_rearm_after);
+            fused_timeout_notice(ctx);
             attempt -= 1;
             continue;
         }

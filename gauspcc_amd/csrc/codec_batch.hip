@@ -12,7 +12,6 @@
 // container layout, mixed container versions) are coded one by one by the same entry points.
 #include <algorithm>
 #include <chrono>
-#include <functional>
 
 #include "codec_shared.hpp"
 #include "container.hpp"
@@ -69,7 +68,7 @@ int encode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *const *
     HostTrace ht;
     GP_TRY(ctx->side_init());
     hipStream_t sd = ctx->side;
-    struct SideGuard { hipStream_t s; ~SideGuard() { (void)hipStreamSynchronize(s); } } side_guard{sd};
+    SideGuard side_guard{sd, nullptr};
     GP_TRY(ctx->hbatch.reserve(enc_seg_offset(K) + enc_seg_bytes(K) + 64));
     Forest F;
     int bad = -1;
@@ -115,116 +114,30 @@ int encode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *const *
     constexpr int NCOUNTERS = MAXLV + 16;
     TAKE(pairs_dev, unsigned long long, NCOUNTERS);
     HIP_TRY(hipMemsetAsync(pairs_dev, 0, sizeof(unsigned long long) * NCOUNTERS, st));
-    int64_t nP = 0;
-    for (int d = 0; d + 1 < L; ++d) nP += T.lv[d].n;
-    const int64_t nC = coded;
     if (L > 1) {
-        int64_t pb[MAXLV] = {0}, cbase[MAXLV] = {0};
-        for (int d = 1; d < L; ++d) pb[d] = pb[d - 1] + T.lv[d - 1].n;
-        for (int d = 2; d < L; ++d) cbase[d] = cbase[d - 1] + T.lv[d - 1].n;
-        TAKE(occP, uint8_t, nP); TAKE(occC, uint8_t, nC); TAKE(rkeyC, uint64_t, nC);
-        TAKE(parentC, uint32_t, nC); TAKE(posC, uint32_t, nC); TAKE(slotsC, uint32_t, nC);
-        SetLevels S = {};
         FPosArgs PA = {};
-        {
-            S.L = L; PA.L = L;
-            for (int d = 0; d < L; ++d) {
-                const Level *lv = &T.lv[d];
-                S.n[d] = (uint32_t)lv->n; S.pb[d] = (uint32_t)pb[d]; S.cbase[d] = (uint32_t)cbase[d];
-                S.occ[d] = lv->occ; S.rkey[d] = lv->rkey; S.parent[d] = lv->parent; S.m2r[d] = lv->m2r;
-                PA.cbase[d] = (uint32_t)cbase[d]; PA.m2r[d] = lv->m2r; PA.seg[d] = F.seg_dev[d]; PA.nseg[d] = F.Kd[d];
-            }
-            StageTimer tm(ctx, st, ST_ELEM, (double)nP * 2 + (double)nC * (2 + 16 + 8));
-            k_set_rows<<<(unsigned)cdiv(std::max(nP, nC), 256), 256, 0, st>>>(S, nP, nC, occP, occC, rkeyC, parentC);
+        PA.L = L;
+        int64_t cbase = 0;
+        for (int d = 1; d < L; ++d) { PA.cbase[d] = (uint32_t)cbase; PA.m2r[d] = T.lv[d].m2r; PA.seg[d] = F.seg_dev[d]; PA.nseg[d] = F.Kd[d]; cbase += T.lv[d].n; }
+        // the base level hangs under the forest's root level, so it is an ordinary level with a parent (tiles.hip)
+        EncodeNet net = {&T, &F.root, F.cell_root, pairs_dev, lohi, nullptr};
+        net.ranks = [&](hipStream_t s) { return forest_ranks(ctx, s, &F); };
+        net.set_pos = [&](hipStream_t s, uint32_t *posC, uint32_t *slotsC) -> int {
+            k_fset_pos<<<(unsigned)cdiv(coded, 256), 256, 0, s>>>(PA, coded, posC, slotsC);
             LAUNCH_CHECK();
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_main, st));
-        // second stream: the raster ranks of every merged level and the coder slots that depend on them (codec.hip: queue_ranks)
-        const std::function<int()> queue_ranks = [&]() -> int {
-            HIP_TRY(hipStreamWaitEvent(sd, ctx->ev_main, 0));
-            ctx->arena.flip = true;
-            int rc = GPCC_OK;
-            {
-                StageTimer tm(ctx, sd, ST_OCTREE, 0.0);
-                rc = forest_ranks(ctx, sd, &F);
-            }
-            ctx->arena.flip = false;
-            GP_TRY(rc);
-            {
-                StageTimer tm(ctx, sd, ST_ELEM, (double)nC * (4 + 8));
-                k_fset_pos<<<(unsigned)cdiv(nC, 256), 256, 0, sd>>>(PA, nC, posC, slotsC);
-                LAUNCH_CHECK();
-            }
-            HIP_TRY(hipEventRecord(ctx->ev_side, sd));
             return GPCC_OK;
         };
-        // tile lists of every merged level in one pool; the base level hangs under the forest's root level, so it is an
-        // ordinary level with a parent (tiles.hip)
-        ConvTiles tilesP, tilesC;
-        {
-            const int NPc = cell_map_entries(m->k);
-            TileLevel tl[MAXLV];
-            const int32_t *cell_prev = F.cell_root;
-            for (int d = 0; d < L; ++d) {
-                int32_t *own = nullptr;
-                if (d + 1 < L) { TAKE(cm, int32_t, (int64_t)NPc * T.lv[d].n); own = cm; }
-                tl[d] = TileLevel{&T.lv[d], d ? &T.lv[d - 1] : &F.root, cell_prev, own};
-                cell_prev = own;
-            }
-            const int R = conv_pick_rows(nC, m->k), H = conv_pick_height(nC, R);
-            TilePool pool;
-            StageTimer tm(ctx, st, ST_TILES, 0.0);
-            GP_TRY(tiles_build(ctx, st, tl, L, m->k, R, H, &pool, pairs_dev));
-            GP_TRY(tiles_view(ctx, st, pool, 0, L - 1, pb, &tilesP));
-            GP_TRY(tiles_view(ctx, st, pool, 1, L, cbase + 1, &tilesC));
-            tm.add_bytes(pool.alg_bytes);
-        }
-        ht.mark("benc tiles built");
-        TAKE(pF, float, nP * m->C); TAKE(pA, float, nP * m->C); TAKE(pB, float, nP * m->C);
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nP * 129); GP_TRY(embed_occ(st, m->prior_emb, occP, nP, pF, m->C)); }
-        GP_TRY(run_trunk(ctx, 0, st, m, 0, Trunk{pF, pA, pB}, tilesP, nP));
-        GP_TRY(queue_ranks());
-        TAKE(cX, float, nC * m->C); TAKE(cA, float, nC * m->C); TAKE(cB, float, nC * m->C);
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nC * (128 + 12 + 128)); GP_TRY(child_features(st, pA, parentC, rkeyC, m->temb, nC, cX, m->C)); }
-        GP_TRY(run_trunk(ctx, 1, st, m, 5, Trunk{cX, cA, cB}, tilesC, nC));
-        TAKE(u1, float, nC * m->C); TAKE(u2, float, nC * m->C); TAKE(u3, float, nC * m->C);
-        TAKE(v1, float, nC * m->C); TAKE(v2, float, nC * m->C);
-        float *u[4] = {cA, u1, u2, u3};
-        float *v[4] = {cX, cB, v1, v2};
-        {
-            const float *const embs[3] = {m->semb[0], m->semb[1], m->semb[2]};
-            float *const outs[3] = {u1, u2, u3};
-            StageTimer tm(ctx, st, ST_ELEM, (double)nC * (128 + 1 + 3 * 128));
-            GP_TRY(stage_inputs_gt(st, cA, embs, occC, nC, outs, m->C));
-        }
-        ConvBatch cb = {}; cb.C = m->C;
-        for (int s = 0; s < 4; ++s) cb.job[s] = ConvJob{u[s], m->conv[10 + 2 * s], nullptr, v[s]};
-        GP_TRY(sparse_conv(ctx, 1, st, cb, 4, tilesC, nC, 1));
-        TAKE(y0, float, nC * m->C);
-        float *y[4] = {y0, u1, u2, u3};
-        for (int s = 0; s < 4; ++s) cb.job[s] = ConvJob{v[s], m->conv[10 + 2 * s + 1], nullptr, y[s]};
-        GP_TRY(sparse_conv(ctx, 1, st, cb, 4, tilesC, nC, 0));
-        HIP_TRY(hipStreamWaitEvent(st, ctx->ev_side, 0));
-        ctx->arena.release_top_low();
-        StageTimer tm_heads(ctx, st, ST_HEADS, (double)nC * 4 * (128 + 1 + 8 + 4));
-        for (int s = 0; s < 4; ++s) {
-            HeadArgs ha = {}; ha.C = m->C;
-            ha.x = y[s]; ha.n = nC; ha.stage_m = STAGE_M[s];
-            ha.w1 = m->hw1[s]; ha.b1 = m->hb1[s]; ha.w2 = m->hw2[s]; ha.b2 = m->hb2[s]; ha.frag = m->hfrag[s];
-            ha.occ = occC; ha.stage = s; ha.lohi = lohi; ha.mode = 0; ha.pos = posC; ha.slots = slotsC;
-            ha.bits = nullptr;
-            GP_TRY(head_cdf(st, ha));
-        }
+        net.ht = &ht; net.trace = "benc";
+        GP_TRY(encode_network(ctx, m, st, sd, net));
     }
     // ---- range coder over every lane of every stream; streams in container order: scene (the caller's order), level, stage
     int nstreams = 0;
     for (int u = 0; u < K; ++u) nstreams += 4 * (F.sc[(size_t)internal_of[(size_t)u]].L - 1);
-    std::vector<RcChunk> chunks;
+    LaneList lanes;
     std::vector<uint32_t> lane_stream;
     std::vector<uint32_t> stream_first((size_t)nstreams + 1, 0), stream_extra((size_t)std::max(nstreams, 1), 0);
     std::vector<size_t> hdr_bytes((size_t)K), scene_stream0((size_t)K + 1, 0);
-    uint32_t max_syms = 1;
-    size_t table_bound = 0, hdr_total = 0;
+    size_t hdr_total = 0;
     {
         int si = 0;
         uint32_t pending = 0;   // header bytes of the scenes in front of the next stream
@@ -240,23 +153,19 @@ int encode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *const *
                 const RcPlan pl = plan(nc);
                 const ForestSeg &sg = seg[d][(size_t)qi];
                 for (int s = 0; s < 4; ++s, ++si) {
-                    stream_first[(size_t)si] = (uint32_t)chunks.size();
+                    stream_first[(size_t)si] = (uint32_t)lanes.chunks.size();
                     stream_extra[(size_t)si] = pending; pending = 0;
-                    const int64_t base = (int64_t)sg.base + (int64_t)s * sg.slots;
-                    table_bound += 6 * (size_t)pl.nchunks + 8;
-                    if (pl.dual && ((base & 1) || pl.llog < 4)) return fail(GPCC_ERR_HIP, "internal: stream %d starts on an odd slot or has lanes below 16 symbols", si);
-                    for (uint32_t c = 0; c < pl.nlanes; ++c) {
-                        const int64_t cn = pl.lane_syms(nc, c);
-                        lane_stream.push_back((uint32_t)si);
-                        chunks.push_back(RcChunk{(uint32_t)(base + c), pl.nlanes, (uint32_t)cn, 0, 0, 0});
-                        max_syms = std::max<uint32_t>(max_syms, (uint32_t)cn);
-                    }
+                    GP_TRY(lanes_append(&lanes, si, (int64_t)sg.base + (int64_t)s * sg.slots, nc, pl));
+                    lane_stream.insert(lane_stream.end(), pl.nlanes, (uint32_t)si);
                 }
             }
         }
         scene_stream0[(size_t)K] = (size_t)si;
-        stream_first[(size_t)nstreams] = (uint32_t)chunks.size();
+        stream_first[(size_t)nstreams] = (uint32_t)lanes.chunks.size();
     }
+    const std::vector<RcChunk> &chunks = lanes.chunks;
+    const uint32_t max_syms = lanes.max_syms;
+    const size_t table_bound = lanes.table_bound;
     const int nchunks = (int)chunks.size();
     const Level *base = &T.lv[0];
     TAKE(base_xyz, int32_t, 3 * base->n);
@@ -313,11 +222,8 @@ int encode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *const *
     HIP_TRY(hipStreamSynchronize(st));
     ht.mark("benc coded (sync)");
     const uint32_t *hcnt = reinterpret_cast<const uint32_t *>(hs + off_cnt);
-    unsigned long long set_pairs[2] = {0, 0};
-    {
-        const unsigned long long *hp = reinterpret_cast<const unsigned long long *>(hs + off_pairs);
-        for (int d = 0; d < L; ++d) { if (d + 1 < L) set_pairs[0] += hp[d]; if (d) set_pairs[1] += hp[d]; }
-    }
+    unsigned long long set_pairs[2];
+    sum_set_pairs(reinterpret_cast<const unsigned long long *>(hs + off_pairs), L, set_pairs);
     if (ctx->prof.on) GP_TRY(prof_collect(ctx, set_pairs, 2));
     // ---- containers: header, then per stream its length, chunk table and (already in place) payload
     uint8_t *out = ctx->hbytes.p;
@@ -330,34 +236,18 @@ int encode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *const *
         offsets_out[u] = (int64_t)pos;
         if (pos + hdr_bytes[(size_t)u] > ctx->hbytes.cap) return fail(GPCC_ERR_HIP, "internal: container beyond its bound");
         uint8_t *o = out + pos;
-        o[0] = 0xFF; o[1] = 0xFF; o[2] = (uint8_t)CONTAINER_VERSION; o[3] = (uint8_t)chunk_log2; o[4] = (uint8_t)posq[u]; o[5] = (uint8_t)(posq[u] >> 8); o[6] = (uint8_t)sc.L; o[7] = 0;
-        size_t p = 8;
-        for (int d = 0; d < sc.L; ++d) { put32(o + p, (uint32_t)sc.n[d]); p += 4; }
-        put32(o + p, (uint32_t)sc.npts); p += 4;
-        put32(o + p, (uint32_t)sc.n[0]); p += 4;
+        size_t p = chunked_header_put(o, CONTAINER_VERSION, chunk_log2, posq[u], sc.L, sc.n, sc.npts);
         const uint32_t r0 = F.row0[0][(size_t)qi];
-        for (int64_t i = 0; i < sc.n[0]; ++i)
-            for (int a = 0; a < 3; ++a) { put32(o + p, (uint32_t)((int64_t)hbx[3 * (r0 + i) + a] - (sc.bias[a] >> sc.L))); p += 4; }
-        memcpy(o + p, hbo + r0, (size_t)sc.n[0]); p += (size_t)sc.n[0];
-        const int ns = 4 * (sc.L - 1);
-        o[p] = (uint8_t)ns; o[p + 1] = (uint8_t)(ns >> 8); p += 2;
+        const int64_t origin[3] = {sc.bias[0] >> sc.L, sc.bias[1] >> sc.L, sc.bias[2] >> sc.L};   // the scene's place in the forest's frame
+        p += base_block_put(o + p, sc.n[0], hbx + 3 * (size_t)r0, origin, hbo + r0, 4 * (sc.L - 1));
         if (p != hdr_bytes[(size_t)u]) return fail(GPCC_ERR_HIP, "internal: header size mismatch");
         pos += p;
         for (size_t si = scene_stream0[(size_t)u]; si < scene_stream0[(size_t)u + 1]; ++si) {
             const int c0 = (int)stream_first[si], c1 = (int)stream_first[si + 1];
-            size_t pay = 0;
-            uint32_t mb = 0;
-            for (int c = c0; c < c1; ++c) pay += hcnt[c];
-            for (int c = c0; c < c1; c += 2) mb = std::max(mb, hcnt[c] + (c + 1 < c1 ? hcnt[c + 1] : 0u));
-            const int stage_lp = STAGE_M[si & 3] + 1;
-            if (!rc_window_fits(stage_lp, mb)) return BATCH_SOLO;   // an oversize chunk: the solo path codes that scene again with smaller chunks
-            auto cb = [&](uint32_t c) { const int l = c0 + 2 * (int)c; return hcnt[l] + (l + 1 < c1 ? hcnt[l + 1] : 0u); };
-            const uint32_t nch = (uint32_t)((c1 - c0 + 1) / 2);
-            const size_t tab = rc_table_size(cb, nch);
-            if (pos + 4 + tab + pay > ctx->hbytes.cap) return fail(GPCC_ERR_HIP, "internal: container beyond its bound");
-            put32(out + pos, (uint32_t)(tab + pay)); pos += 4;
-            pos += rc_table_put(out + pos, cb, nch);
-            pos += pay;
+            const StreamSize z = stream_size(hcnt, c0, c1, (int)si, true);
+            if (!z.fits) return BATCH_SOLO;   // an oversize chunk: the solo path codes that scene again with smaller chunks
+            if (pos + 4 + z.tab + z.pay > ctx->hbytes.cap) return fail(GPCC_ERR_HIP, "internal: container beyond its bound");
+            pos += stream_head_put(out + pos, hcnt, c0, c1, z, true) + z.pay;
         }
         if (stats) {
             gpcc_stats *s = &stats[u];
@@ -431,8 +321,7 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
     const int L = H[(size_t)order[0]].L;
     F.L = L;
     // ---- base levels: every scene in a frame of its own (its base minimum at 0), z slabs one behind the other
-    struct BN { uint64_t mk, rk; uint8_t occ; };
-    std::vector<BN> bnodes;
+    std::vector<BaseNode> bnodes;
     std::vector<uint32_t> bparent;
     std::vector<uint64_t> root_rk;
     std::vector<uint8_t> root_occ;
@@ -457,14 +346,9 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
         const int64_t t3[3] = {-lo[0], -lo[1], -lo[2] + tz};
         for (int a = 0; a < 3; ++a) sc.bias[a] = t3[a] * ((int64_t)1 << h.L);
         const size_t b0 = bnodes.size();
-        for (int64_t i = 0; i < h.bn; ++i) {
-            uint32_t b[3];
-            for (int a = 0; a < 3; ++a) b[a] = (uint32_t)((int64_t)(int32_t)get32(h.bxyz + 12 * i + 4 * a) + t3[a]);
-            if (!h.bocc[i]) return fail(GPCC_ERR_FORMAT, "scene %d: empty base occupancy", u);
-            bnodes.push_back(BN{morton3(b[0], b[1], b[2]), rkey3(b[0], b[1], b[2]), h.bocc[i]});
-        }
-        std::sort(bnodes.begin() + (ptrdiff_t)b0, bnodes.end(), [](const BN &a, const BN &b) { return a.mk < b.mk; });
-        for (size_t i = b0 + 1; i < bnodes.size(); ++i) if (bnodes[i].mk == bnodes[i - 1].mk) return fail(GPCC_ERR_FORMAT, "scene %d: duplicate base node", u);
+        char who[24];
+        snprintf(who, sizeof who, "scene %d: ", u);
+        GP_TRY(base_nodes_append(h.bxyz, h.bocc, h.bn, t3, (int64_t)1 << 21, who, &bnodes));   // (the forest's frame: 21 bits per axis)
         // root level: the would-be parents of the base nodes (siblings are neighbours in Morton order)
         F.root0[(size_t)qi] = (uint32_t)root_rk.size();
         for (size_t i = b0; i < bnodes.size(); ++i) {
@@ -541,7 +425,7 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
     uint8_t *pin = ctx->hbatch.p;
     GP_TRY(ctx->side_init());
     hipStream_t sd = ctx->side;
-    struct SideGuard { hipStream_t s, x; ~SideGuard() { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(x); } } side_guard{sd, ctx->xfer};
+    SideGuard side_guard{sd, ctx->xfer};
     // ---- the containers go up on a stream of their own, one behind the other (16-byte aligned)
     TAKE(dbytes, uint8_t, blob + 16);
     std::vector<int64_t> byte0((size_t)K);
@@ -598,18 +482,11 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
     const int d_early = std::min(L, 1 + TAB_EARLY);
     GP_TRY(forest_upload_segs(ctx, st, &F, seg, pin + pin_seg, pin_seg_b));
     // ---- base and root levels
-    auto alloc_level = [&](Level *lv, int64_t n, int lvl) -> int {
-        lv->n = n; lv->lvl = lvl;
-        TAKE(rkey, uint64_t, n); TAKE(occ, uint8_t, n); TAKE(cstart, uint32_t, n + 1); TAKE(parent, uint32_t, n); TAKE(m2r, uint32_t, n); TAKE(r2m, uint32_t, n);
-        lv->rkey = rkey; lv->occ = occ; lv->cstart = cstart; lv->parent = parent; lv->m2r = m2r; lv->r2m = r2m;
-        lv->span0 = reinterpret_cast<char *>(rkey); lv->span_bytes = (size_t)(reinterpret_cast<char *>(r2m + n) - reinterpret_cast<char *>(rkey));
-        return GPCC_OK;
-    };
     Tree &T = F.T;
     T.L = L; T.npts = total_pts; T.hb = std::min(21, F.hb0 + L);
     Level &cur0 = T.lv[0];
-    GP_TRY(alloc_level(&cur0, bn, L));
-    GP_TRY(alloc_level(&F.root, nroot, L + 1));
+    GP_TRY(alloc_level(ctx, &cur0, bn, L));
+    GP_TRY(alloc_level(ctx, &F.root, nroot, L + 1));
     TAKE(droot0, uint32_t, K + 1);
     {
         uint8_t *p = pin + pin_base;
@@ -674,24 +551,13 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
         const int64_t np_in = F.inner(g);   // rows with children in level g + 1: the scenes that go on
         // ---- st: parent trunk (only the rows that have children need it: a prefix -- but a block of the tile list may straddle
         // the boundary, so the trunk runs on the whole level; the rows of finished scenes are a level's tail and cost their share)
-        TAKE_TOP(pF, float, np * m->C); TAKE_TOP(pA, float, np * m->C); TAKE_TOP(pB, float, np * m->C);
-        float *Pp = nullptr;
-        if (planP.valid()) { TAKE_TOP(pp, float, planP.pcap * 32); Pp = pp; }
-        if (planP.valid() && fmode == 1) {
-            ConvRec rec = {0, 0, g, 1, 0, 0, (long long)np, 0, 5, 1};
-            if (ctx->prof.on) GP_TRY(prof_event(ctx, st, &rec.e0));
-            GP_TRY(fused_parent_trunk(ctx, st, m, planP, planP_np, cur.occ, pF, pA, pB, Pp));
-            if (ctx->prof.on) { GP_TRY(prof_event(ctx, st, &rec.e1)); ctx->prof.recs.push_back(rec); }
-            any_fused = true;
-        } else {
-            { StageTimer tm(ctx, st, ST_ELEM, (double)np * 129); GP_TRY(embed_occ(st, m->prior_emb, cur.occ, np, pF, m->C)); }
-            GP_TRY(run_trunk(ctx, g, st, m, 0, Trunk{pF, pA, pB}, tilesP, np, planP.valid() ? &planP : nullptr, Pp));
-        }
+        float *pA = nullptr;
+        GP_TRY(dec_parent_trunk(ctx, st, m, g, cur.occ, np, tilesP, planP, planP_np, fmode, &pA, &any_fused));
         // ---- side: the child level's structure
         HIP_TRY(hipStreamWaitEvent(sd, ctx->ev_main, 0));
         Level &chi = T.lv[g + 1];
         const int64_t nc = lvl_n[g + 1];
-        GP_TRY(alloc_level(&chi, nc, L - g - 1));
+        GP_TRY(alloc_level(ctx, &chi, nc, L - g - 1));
         {
             Level pv = cur; pv.n = np_in;
             StageTimer tm(ctx, sd, ST_OCTREE, (double)np * 13 + (double)nc * 12 + (double)nc * 8);
@@ -704,18 +570,7 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
         ConvTiles tilesC;
         PairPlan planC;
         const bool child_plan = fuse_ctx && fused_level_ok(nc, m->k) && fused_windows_fit(nc, cur.n, nch_tot[g + 1], win_bytes[g + 1]);
-        if (child_plan) {
-            StageTimer tm(ctx, sd, ST_TILES, 0.0);
-            GP_TRY(pairplan_build(ctx, sd, &cur, cellP, &chi, cellC, m->k, &planC, pairs_dev + g + 1));
-        } else {
-            const TileLevel tl = {&chi, &cur, cellP, cellC};
-            const int R = conv_pick_rows(nc, m->k);
-            TilePool pool;
-            StageTimer tm(ctx, sd, ST_TILES, 0.0);
-            GP_TRY(tiles_build(ctx, sd, &tl, 1, m->k, R, conv_pick_height(nc, R), &pool, pairs_dev + g + 1));
-            GP_TRY(tiles_view(ctx, sd, pool, 0, 1, zero_base, &tilesC));
-            tm.add_bytes(pool.alg_bytes);
-        }
+        GP_TRY(dec_child_lists(ctx, sd, m, &cur, cellP, &chi, cellC, child_plan, pairs_dev + g + 1, &planC, &tilesC));
         // CDF row slot and symbol slot of every node (scene records of level g + 1)
         TAKE(cpos, uint32_t, nc);
         TAKE(spos, uint32_t, nc);
@@ -726,57 +581,24 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
         const int nch = (int)nch_tot[g + 1];
         const RcChunk *dchunks = dchunks_all + desc_at[g + 1];
         // ---- st: child trunk and the four stages
-        TAKE_TOP(cX, float, nc * m->C); TAKE_TOP(cA, float, nc * m->C); TAKE_TOP(cB, float, nc * m->C); TAKE_TOP(cU, float, nc * m->C);
-        float *Pc = nullptr;
-        if (child_plan) { TAKE_TOP(pc, float, planC.pcap * 32); Pc = pc; }
-        TAKE_TOP(cdf, uint16_t, rc_rows_capacity(nch, S) * 16);
-        uint8_t *sym[4];
-        for (int s = 0; s < 4; ++s) { TAKE_TOP(sy, uint8_t, symlen[g + 1]); sym[s] = sy; }
+        // (llog places CDF rows by raster rank and is unread when cpos brings every node's row: the scenes' lanes differ in size)
+        LevelCoder lc = {spos, cpos, (uint32_t)nch, 4, dchunks, {win_bytes[g + 1][0], win_bytes[g + 1][1], win_bytes[g + 1][2], win_bytes[g + 1][3]}, version >= 3, rc_coder_of_version(version)};
+        ChildBufs cb;
+        GP_TRY(child_bufs_take(ctx, m, nc, child_plan ? planC.pcap : 0, lc.nlanes, S, symlen[g + 1], &cb));
         if (g + 1 == d_early && d_early < L) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_tables, 0));   // the first level whose tables went up in the second batch
         if (child_plan && fmode == 1) {
-            // the level's whole chain in one persistent launch (fused.hip)
             if (g == 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_bytes, 0));
-            FusedChild fa = {};
-            fa.pA = pA; fa.np = np; fa.parent = chi.parent; fa.rkey = chi.rkey; fa.m2r = chi.m2r; fa.bytes = dbytes; fa.chunks = dchunks; fa.nlanes = (uint32_t)nch; fa.llog = 4;
-            fa.cpos = cpos; fa.spos = spos;
-            for (int s = 0; s < 4; ++s) { fa.win_bytes[s] = win_bytes[g + 1][s]; fa.sym[s] = sym[s]; }
-            fa.cX = cX; fa.cA = cA; fa.cB = cB; fa.cU = cU; fa.P = Pc; fa.cdf = cdf; fa.occ = chi.occ; fa.coder = rc_coder_of_version(version);
-            ConvRec rec = {0, 0, g + 1, 1, 0, 0, (long long)nc, 0, 13, 1};
-            if (ctx->prof.on) GP_TRY(prof_event(ctx, st, &rec.e0));
-            GP_TRY(fused_child_level(ctx, st, m, planC, fa));
-            if (ctx->prof.on) { GP_TRY(prof_event(ctx, st, &rec.e1)); ctx->prof.recs.push_back(rec); }
+            GP_TRY(dec_child_fused(ctx, st, m, g, planC, pA, np, chi, dbytes, lc, cb));
             any_fused = true;
         } else {
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nc * (128 + 12 + 128)); GP_TRY(child_features(st, pA, chi.parent, chi.rkey, m->temb, nc, cX, m->C)); }
-        GP_TRY(run_trunk(ctx, g + 1, st, m, 5, Trunk{cX, cA, cB}, tilesC, nc, child_plan ? &planC : nullptr, Pc));
-        for (int s = 0; s < 4; ++s) {
-            const float *xin = cA;
-            if (s) { StageTimer tm(ctx, st, ST_ELEM, (double)nc * (128 + 4 + s + 128)); GP_TRY(stage_input_dec(st, cA, m->semb[s - 1], sym, spos, s, nc, cU, m->C)); xin = cU; }
-            ConvBatch cb = {}; cb.C = m->C;
-            if (child_plan) {
-                GP_TRY(plan_conv(st, planC, ConvJob{xin, m->conv[10 + 2 * s], nullptr, cX}, Pc, 1));
-                GP_TRY(plan_conv(st, planC, ConvJob{cX, m->conv[10 + 2 * s + 1], nullptr, cB}, Pc, 0));
-            } else {
-            GP_TRY(conv_chain_begin(ctx, st));
-            cb.job[0] = ConvJob{xin, m->conv[10 + 2 * s], nullptr, cX};
-            GP_TRY(sparse_conv(ctx, g + 1, st, cb, 1, tilesC, nc, 1));
-            cb.job[0] = ConvJob{cX, m->conv[10 + 2 * s + 1], nullptr, cB};
-            GP_TRY(sparse_conv(ctx, g + 1, st, cb, 1, tilesC, nc, 0));
-            GP_TRY(conv_chain_end(ctx, st));
+            GP_TRY(dec_child_trunk(ctx, st, m, g, pA, chi, tilesC, child_plan ? &planC : nullptr, cb));
+            for (int s = 0; s < 4; ++s) {
+                GP_TRY(dec_child_stage(ctx, st, m, g, s, chi, tilesC, child_plan ? &planC : nullptr, lc, cb));
+                if (g == 0 && s == 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_bytes, 0));
+                StageTimer tm(ctx, st, ST_CODER, (double)nc * (stage_row_bytes(s) + 1));
+                GP_TRY(rc_decode_launch(st, cb.cdf, STAGE_M[s] + 1, dbytes, dchunks + (size_t)s * nch, nch, lc.win_bytes[s], lc.dual, cb.sym[s], lc.coder));
             }
-            HeadArgs ha = {}; ha.C = m->C;
-            ha.x = cB; ha.n = nc; ha.stage_m = STAGE_M[s];
-            ha.w1 = m->hw1[s]; ha.b1 = m->hb1[s]; ha.w2 = m->hw2[s]; ha.b2 = m->hb2[s]; ha.frag = m->hfrag[s];
-            ha.m2r = chi.m2r; ha.cdf = cdf; ha.mode = 1; ha.pos = cpos;
-            const int row_bytes = STAGE_M[s] == 2 ? 2 : STAGE_M[s] == 4 ? 8 : 32;
-            { StageTimer tm(ctx, st, ST_HEADS, (double)nc * (128 + 4 + row_bytes)); GP_TRY(head_cdf(st, ha)); }
-            if (g == 0 && s == 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev_bytes, 0));
-            {
-                StageTimer tm(ctx, st, ST_CODER, (double)nc * (row_bytes + 1));
-                GP_TRY(rc_decode_launch(st, cdf, STAGE_M[s] + 1, dbytes, dchunks + (size_t)s * nch, nch, win_bytes[g + 1][s], version >= 3, sym[s], rc_coder_of_version(version)));
-            }
-        }
-        { StageTimer tm(ctx, st, ST_ELEM, (double)nc * (4 + 4 + 1)); GP_TRY(assemble_occ(st, sym, spos, nc, chi.occ)); }
+            { StageTimer tm(ctx, st, ST_ELEM, (double)nc * (4 + 4 + 1)); GP_TRY(assemble_occ(st, cb.sym, spos, nc, chi.occ)); }
         }
         HIP_TRY(hipEventRecord(ctx->ev_main, st));
         if (g == 0 && d_early < L) GP_TRY(parse_levels(d_early, L, ctx->ev_tables));   // the other levels' tables: parsed while the device runs the first coded level
@@ -846,12 +668,6 @@ int decode_batch_body(gpcc_ctx *ctx, const gpcc_model *m, const uint8_t *const *
     return GPCC_OK;
 }
 
-size_t arena_scaled_b(size_t want)
-{
-    static const double scale = [] { const char *e = getenv("GAUSPCC_ARENA_SCALE"); const double v = e ? atof(e) : 1.0; return v > 0.0 ? v : 1.0; }();
-    return scale == 1.0 ? want : std::max<size_t>((size_t)((double)want * scale), (size_t)1 << 20);
-}
-
 }  // namespace
 
 extern "C" int gpcc_encode_batch(gpcc_ctx *ctx, const gpcc_model *m, const int32_t *const *xyz_dev, const int64_t *n, int nscenes, int chunk_log2, const uint16_t *posq_f16,
@@ -868,7 +684,7 @@ extern "C" int gpcc_encode_batch(gpcc_ctx *ctx, const gpcc_model *m, const int32
     if (chunk_log2 != 0 && nscenes <= FOREST_MAX_SCENES && !never) {
         int64_t total = 0;
         for (int q = 0; q < nscenes; ++q) total += n[q] > 0 ? n[q] : 0;
-        size_t want = arena_scaled_b(arena_estimate(total, m->K) + (size_t)total * 40 + (size_t)nscenes * 65536);
+        size_t want = arena_scaled(arena_estimate(total, m->K) + (size_t)total * 40 + (size_t)nscenes * 65536);
         for (int attempt = 0; attempt < 6; ++attempt) {
             GP_TRY(ctx->arena.reserve(want));
             rc = encode_batch_body(ctx, m, xyz_dev, n, nscenes, chunk_log2, posq_f16, bytes_out, offsets_out, stats, st);
@@ -942,7 +758,7 @@ extern "C" int gpcc_decode_batch(gpcc_ctx *ctx, const gpcc_model *m, const uint8
             ctx->fused_note_decode();
             int64_t nmax = 0;
             for (int d = 0; d < MAXLV; ++d) nmax = std::max(nmax, nmax_sum[d]);
-            size_t want = arena_scaled_b((size_t)nmax * 2700 + (size_t)nodes * (size_t)(4 * 125 + m->K * 81 / 16 + 96) + (size_t)npts * 32 + (size_t)total_bytes + (size_t)nscenes * 65536 + ((size_t)48 << 20));
+            size_t want = arena_scaled((size_t)nmax * 2700 + (size_t)nodes * (size_t)(4 * 125 + m->K * 81 / 16 + 96) + (size_t)npts * 32 + (size_t)total_bytes + (size_t)nscenes * 65536 + ((size_t)48 << 20));
             if (fused_enabled()) {   // small levels (fused.hpp): the product buffer n K + 1 rows, the plan and its build scratch
                 int64_t nf = 0;
                 for (int d = 0; d < MAXLV; ++d) if (nmax_sum[d] > 0 && fused_level_ok(nmax_sum[d], m->k)) nf = std::max(nf, nmax_sum[d]);
@@ -952,8 +768,7 @@ extern "C" int gpcc_decode_batch(gpcc_ctx *ctx, const gpcc_model *m, const uint8
                 GP_TRY(ctx->arena.reserve(want));
                 rc = decode_batch_body(ctx, m, bytes, nbytes, nscenes, xyz_dev, capacity_points, n_out, posq_f16_out, stats, st);
                 if (rc == BATCH_RETRY_UNFUSED) {
-                    static const bool loud = getenv("GAUSPCC_FUSED_QUIET") == nullptr;
-                    if (loud) fprintf(stderr, "[gauspcc] a persistent small-level launch timed out on device %d; the launch-per-layer path serves this context's next %d decodes\n", ctx->device, ctx->fused_rearm_after);
+                    fused_timeout_notice(ctx);
                     attempt -= 1;
                     continue;
                 }

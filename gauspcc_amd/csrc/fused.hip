@@ -548,7 +548,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void k_level_fused(FusedK k)
         }
         if (!grid_barrier(bc)) return;
     }
-    // Conv-ReLU-ResNet-ResNet (network_ue_4stage_conv.py:17-33; codec.hip: run_trunk) -> a
+    // Conv-ReLU-ResNet-ResNet (network_ue_4stage_conv.py:17-33; codec_shared.hpp: run_trunk) -> a
     if (!conv_phases(k, bc, m, pc, k.x, k.w[0], nullptr, k.a, 1, true)) return;
     if (!conv_phases(k, bc, m, pc, k.a, k.w[1], nullptr, k.b, 1, true)) return;
     if (!conv_phases(k, bc, m, pc, k.b, k.w[2], k.a, k.x, 1, true)) return;

@@ -591,7 +591,7 @@ int level_expand_rank(gpcc_ctx *ctx, hipStream_t st, Level *par, Level *chi, uin
     // decoder produced: a corrupt stream (or a lying header) leaves their tail unwritten.  Ranks are INDICES (rows of the
     // CDF and symbol arrays are addressed through m2r / r2m): stale arena bytes there become out-of-range addresses -- a
     // memory fault at 10^6 nodes, where the small clouds of the corruption tests never left mapped memory.  Zero = valid.
-    // One memset: the decoder carves a level's arrays from the arena back to back and records the span (codec.hip: alloc_level,
+    // One memset: the decoder carves a level's arrays from the arena back to back and records the span (codec_shared.hip: alloc_level,
     // Level::span0 / span_bytes); occ and cstart are written in full later (assemble_occ, the next level's popcount scan).
     {
         if (chi->span0 && chi->span_bytes) HIP_TRY(hipMemsetAsync(chi->span0, 0, chi->span_bytes, st));   // the span alloc_level recorded: nothing else lives in it

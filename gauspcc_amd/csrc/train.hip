@@ -204,21 +204,7 @@ int frame_body(gpcc_ctx *ctx, hipStream_t st, const int32_t *xyz, int64_t n, int
     TilePool pool;
     uint32_t total = 0;
     if (L > 1) {
-        const int NPc = cell_map_entries(k);
-        TileLevel tl[MAXLV];
-        const int32_t *cell_prev = nullptr;
-        for (int d = 0; d < L; ++d) {
-            int32_t *own = nullptr;
-            if (d + 1 < L) { TAKE(cm, int32_t, (int64_t)NPc * T.lv[d].n); own = cm; }
-            tl[d] = TileLevel{&T.lv[d], d ? &T.lv[d - 1] : nullptr, cell_prev, own};
-            cell_prev = own;
-        }
-        const int R = conv_pick_rows(F->nC, k), H = conv_pick_height(F->nC, R);
-        GP_TRY(tiles_build(ctx, st, tl, L, k, R, H, &pool, nullptr));
-        int64_t pb[MAXLV] = {0}, cb[MAXLV] = {0};
-        for (int d = 0; d + 1 < L; ++d) { pb[d] = F->level_base[d]; cb[d] = F->level_base[d + 1] - F->level_base[1]; }
-        GP_TRY(tiles_view(ctx, st, pool, 0, L - 1, pb, &F->set[0]));
-        GP_TRY(tiles_view(ctx, st, pool, 1, L, cb, &F->set[1]));
+        GP_TRY(tile_sets(ctx, st, T, nullptr, nullptr, k, nullptr, &pool, &F->set[0], &F->set[1]));
         HIP_TRY(hipMemcpyAsync(&total, pool.first + pool.nblk, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }

@@ -47,7 +47,7 @@ def test_fuzz_regression_fixtures(orc, golden_dir, synth_model_k3):
 
 @pytest.mark.gpu
 def test_fuzz_regression_fixtures_on_the_device(golden_dir):
-    """The product reader on the same damaged containers: it sorts the base level itself (codec.hip), so an unsorted base level
+    """The product reader on the same damaged containers: it sorts the base level itself (codec_shared.hip), so an unsorted base level
     decodes to the same cloud and a duplicate base node is a FORMAT error."""
     import torch
 
