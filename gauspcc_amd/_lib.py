@@ -55,6 +55,7 @@ EXPORTS = [
     "gpcc_knn", "gpcc_scatter_max", "gpcc_grow_voxels",
     "gsr_ssim_forward", "gsr_ssim_backward",
     "gsac_rate_forward", "gsac_rate_backward",
+    "gsge_plane_forward", "gsge_plane_backward",
 ]
 
 
@@ -161,6 +162,8 @@ def lib():
     pp, ip, f64 = C.POINTER(vp), C.POINTER(i32), C.c_double
     L.gsac_rate_forward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp]
     L.gsac_rate_backward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp, pp, pp, pp, vp, GSR_ALLOC, vp, vp]
+    L.gsge_plane_forward.argtypes = [vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, GSR_ALLOC, vp, vp]
+    L.gsge_plane_backward.argtypes = [vp, vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, vp, GSR_ALLOC, vp, vp]
     _lib = L
     return L
 

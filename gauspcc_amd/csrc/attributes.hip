@@ -15,6 +15,7 @@
 #include "octree.hpp"
 #include "primitives.hpp"
 #include "rangecoder.hpp"
+#include "sorted_sum.hpp"
 
 using namespace gpcc;
 
@@ -551,10 +552,8 @@ __global__ __launch_bounds__(TB) void k_grid_dydx(const float *__restrict__ inpu
 //              offsets[level] + idx / F (the sentinel n_rows when the corner is unused or the point out of range), the value the slot,
 //              and wts[s] = w_c wn_re.
 //   sort       stable LSD radix sort on the key: each row's contributions become one run in ascending slot order.
-//   sum        one thread per chunk of GB_CHUNK sorted entries sums each run it holds in order (fmaf(w, grad[l, b, ch], acc)).  A run
-//              wholly inside the chunk goes straight into grad_embeddings; a chunk's first run continued from the previous chunk leaves
-//              a head partial, a run that starts in it and continues leaves a tail partial and makes the chunk that row's owner.
-//   combine    each owner adds the following chunks' head partials to its tail partial in chunk order, then the total into the row.
+//   sum, combine   sorted_sum.hpp (shared with the tri-plane's backward): one thread per chunk of GB_CHUNK sorted entries sums each run it
+//              holds in order (fmaf(w, grad[l, b, ch], acc)); runs that cross chunks are finished by their first chunk's thread.
 // Every row is written by exactly one thread and summed in an order fixed by the sorted keys alone: bitwise reproducible.
 constexpr int GB_CHUNK = 32;
 
@@ -598,39 +597,33 @@ __device__ __forceinline__ void gb_add(float (&acc)[F], const float *__restrict_
     for (int ch = 0; ch < F; ++ch) acc[ch] = __builtin_fmaf(w, g[ch], acc[ch]);
 }
 
+template <int F> struct GridRowSum {
+    const float *__restrict__ grad;
+    const uint32_t *__restrict__ slots;
+    const float *__restrict__ wts;
+    int D;
+    uint32_t N, L;
+    float *__restrict__ grad_emb, *__restrict__ head, *__restrict__ tail;
+    float acc[F];
+    __device__ __forceinline__ void zero() { for (int ch = 0; ch < F; ++ch) acc[ch] = 0.0f; }
+    __device__ __forceinline__ void add(int64_t i) { gb_add<F>(acc, grad, slots, wts, i, D, N, L); }
+    __device__ __forceinline__ void to_head(int64_t t) { for (int ch = 0; ch < F; ++ch) head[t * F + ch] = acc[ch]; }
+    __device__ __forceinline__ void to_tail(int64_t t) { for (int ch = 0; ch < F; ++ch) tail[t * F + ch] = acc[ch]; }
+    __device__ __forceinline__ void to_row(uint32_t row) { for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += acc[ch]; }
+};
+
 template <int F>
 __global__ __launch_bounds__(TB) void k_grid_bwd_sum(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ slots, const float *__restrict__ wts,
                                                      const float *__restrict__ grad, int D, uint32_t N, uint32_t L, int64_t E, uint32_t n_rows,
                                                      float *__restrict__ grad_emb, float *__restrict__ head, float *__restrict__ tail, uint8_t *__restrict__ own)
 {
-    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x, i0 = t * GB_CHUNK;
-    if (i0 >= E) return;
-    const int64_t i1 = min(i0 + (int64_t)GB_CHUNK, E);
-    uint32_t row = (uint32_t)keys[i0];
-    bool first = true, starts = i0 == 0 || (uint32_t)keys[i0 - 1] != row;
-    uint8_t owner = 0;
-    float acc[F];
-    for (int ch = 0; ch < F; ++ch) acc[ch] = 0.0f;
-    auto flush = [&](bool cont) {
-        if (row >= n_rows) return;
-        if (first && !starts) { for (int ch = 0; ch < F; ++ch) head[t * F + ch] = acc[ch]; }
-        else if (cont) { for (int ch = 0; ch < F; ++ch) tail[t * F + ch] = acc[ch]; owner = 1; }
-        else { for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += acc[ch]; }
-    };
-    for (int64_t i = i0; i < i1; ++i) {
-        const uint32_t k = (uint32_t)keys[i];
-        if (k != row) {
-            flush(false);
-            row = k; first = false; starts = true;
-            for (int ch = 0; ch < F; ++ch) acc[ch] = 0.0f;
-        }
-        if (row < n_rows) gb_add<F>(acc, grad, slots, wts, i, D, N, L);
-    }
-    flush(i1 < E && (uint32_t)keys[i1] == row);
-    own[t] = owner;
+    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (t * GB_CHUNK >= E) return;
+    GridRowSum<F> a{grad, slots, wts, D, N, L, grad_emb, head, tail, {}};
+    sorted_chunk_sum<GB_CHUNK>(keys, t, E, n_rows, a, own);
 }
 
-// the owners' walk: partials are read GB_WALK chunks at a time, so that a long run waits on memory once per GB_WALK chunks
+// the owners' walk: partials are read GB_WALK chunks at a time
 constexpr int GB_WALK = 8;
 
 template <int F>
@@ -638,29 +631,9 @@ __global__ __launch_bounds__(TB) void k_grid_bwd_combine(const uint64_t *__restr
                                                          const float *__restrict__ tail, const uint8_t *__restrict__ own, float *__restrict__ grad_emb)
 {
     const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
-    if (t >= nchunks || !own[t]) return;
-    const uint32_t row = (uint32_t)keys[min((t + 1) * GB_CHUNK, E) - 1];
-    float s[F];
-    for (int ch = 0; ch < F; ++ch) s[ch] = tail[t * F + ch];
-    for (int64_t j0 = t + 1; j0 < nchunks; j0 += GB_WALK) {
-        float h[GB_WALK][F];
-        bool more[GB_WALK];
-#pragma unroll
-        for (int u = 0; u < GB_WALK; ++u) {
-            const int64_t j = j0 + u, nxt = (j + 1) * GB_CHUNK;
-            for (int ch = 0; ch < F; ++ch) h[u][ch] = j < nchunks ? head[j * F + ch] : 0.0f;
-            more[u] = j < nchunks && nxt < E && (uint32_t)keys[nxt] == row;
-        }
-        bool done = false;
-#pragma unroll
-        for (int u = 0; u < GB_WALK; ++u) {
-            if (done) break;
-            for (int ch = 0; ch < F; ++ch) s[ch] += h[u][ch];
-            done = !more[u];
-        }
-        if (done) break;
-    }
-    for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += s[ch];
+    sorted_combine<GB_CHUNK, F, GB_WALK>(keys, E, nchunks, t, head, tail, F, own, [&](uint32_t row, const float (&s)[F]) {
+        for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += s[ch];
+    });
 }
 
 // Backward, input gradient: one thread per point, dy_dx recomputed; levels outer, channels inner (gridencoder.cu:857-881)

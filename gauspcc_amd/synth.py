@@ -345,3 +345,29 @@ class SyntheticGaussianModelPlus(SyntheticGaussianModel):
         return ((rate > 0.0).float() - rate).detach() + rate          # (N, 1)
 
     get_deform_mlp = property(lambda self: self.mlp_deform)
+
+
+class SyntheticGaussianModelTC(SyntheticGaussianModel):
+    """What TC-GS puts in place of the hash grid in the slice of GaussianModel its rate estimate touches
+    (src/gs_compress/TC-GS/scene/gaussian_model.py:170-176, 322-323, 368, 1052-1059, 1084-1096): the `triplane` context sampler,
+    `mlp_triplane` behind `get_tri_mlp` on [K * 3 * tri_feat_dim plane features | anchor], the bounds as flat (3,) tensors and
+    `knnanchor` (N, K, 3), each anchor with its K - 1 nearest anchors.  Seeded random planes and weights, as the base class."""
+
+    def __init__(self, n_anchors, seed=0, knn=4, tri_feat_dim=50, resolution=256, spatial_lr_scale=5.0, **kw):
+        import torch
+        from .knn import kneighbors
+        from .triplane import Triplane
+
+        super().__init__(n_anchors, seed=seed, **kw)
+        nn = torch.nn
+        dev = self._anchor.device
+        F, K = self.feat_dim, self.n_offsets
+        self.knn, self.tri_feat_dim, self.resolution, self.spatial_lr_scale = knn, tri_feat_dim, resolution, spatial_lr_scale
+        self.x_bound_min, self.x_bound_max = self.x_bound_min.reshape(3), self.x_bound_max.reshape(3)
+        torch.manual_seed(seed + 2)
+        self.triplane = Triplane(feature_dim=tri_feat_dim, resolution=resolution, radii=spatial_lr_scale, device=dev).to(dev)
+        self.mlp_triplane = nn.Sequential(nn.Linear(knn * 3 * tri_feat_dim + 3, F * 2), nn.ReLU(True), nn.Linear(F * 2, (F + 6 + 3 * K) * 2 + 3)).to(dev)
+        self.knn_indices = kneighbors(self._anchor, knn)
+        self.knnanchor = self._anchor[self.knn_indices].detach()
+
+    get_tri_mlp = property(lambda self: self.mlp_triplane)

@@ -618,6 +618,31 @@ GPCC_API int gsac_rate_backward(gpcc_ctx *ctx, int k, int64_t n, int64_t c, cons
                                 double q_floor, int return_lkl, const float *grad_out, float *grad_x, float *const *grad_mean,
                                 float *const *grad_scale, float *const *grad_prob, float *grad_q, gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
+/* ================= Tri-plane context sampler (TC-GS/utils/triplane.py: sample_from_planes :87-164, Triplane.sample :226-238) =================
+ * planes (3, C, H, W), max_coords, min_coords (3), all float32 device; radii and box_warp = 1 as Triplane passes them (radii = 0.5 *
+ * spatial_lr_scale).  coordinates: (n, k, 3) with repeat = 0, or (n, 3) with repeat = 1: every anchor's one sample is written k times
+ * (the reference's anchor.unsqueeze(1).repeat(1, K, 1) call sites), bit-identical to the materialised form.  out (n, k * 3 * C):
+ * out[n, (k_i * 3 + p) * C + ch], the reference's (N, K, 3, C) result.  Per plane p, in float32 and the reference's expression order:
+ *   mag_sq[p] = min(min(|proj_p(max)|^2, |proj_p(min)|^2), radii^2), proj_0(b) = (b.x, b.y), proj_1(b) = (b.x, b.z), proj_2(b) = (b.z, b.x)
+ *   c = 2 coordinate; u_0 = (c.y, c.z), u_1 = (c.x, c.z), u_2 = (c.x, c.y); v = u / sqrt(mag_sq[p]) * 2 - 1; x = 6 v
+ *   m = max(|x|^2, FLT_EPSILON); z = x if m <= 1 else ((2 sqrt(m) - 1) / m) x; g = z / 2
+ *   bilinear grid_sample of planes[p] at g (padding zeros, align_corners false): pixel = ((g + 1) size - 1) / 2, g[0] along W, g[1] along H
+ * A sample whose pixel coordinate is not finite gives zeros and no gradient (torch would index with it); no index is formed from it.
+ * Limits: C in [1, 256], H and W in [2, 4096], k >= 1 (k <= 64 with repeat), n * k * 12 < 2^32; a violation returns GPCC_ERR_ARG before
+ * any launch.  n = 0 launches nothing (the backward zeroes grad_planes).
+ * gsge_plane_backward: grad_out (n, k * 3 * C).  OVERWRITES grad_planes (3, C, H, W) and, when it is not NULL, grad_coordinates (shaped
+ * as coordinates; through the bilinear weights, both branches of the contraction and the scaling; the repeat form's is the sum over its
+ * k copies).  No gradient for the bounds or radii.  Bitwise reproducible: no float atomics (one (texel, slot) key per (sample, plane,
+ * corner), stable radix sort, fixed-order sums; the repeat form adds its k gradient copies in k order first).
+ * Workspace through `alloc`: forward 3 C H W floats; backward about 28 bytes per (sample, plane, corner) plus up to 2 x 3 C H W floats.
+ * Both calls are enqueued on `stream` without synchronising. */
+GPCC_API int gsge_plane_forward(gpcc_ctx *ctx, const float *planes, const float *coordinates, const float *max_coords, const float *min_coords,
+                                double radii, int64_t n, int k, int repeat, int channels, int height, int width, float *out, gsr_alloc_fn alloc,
+                                void *alloc_user, void *stream);
+GPCC_API int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const float *planes, const float *coordinates, const float *max_coords,
+                                 const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
+                                 float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
