@@ -124,71 +124,15 @@ def arithmetic_decode(cdf, in_cache_all, in_cnt_all, chunk_size, N, Lp):
     return out
 
 
-def encode_gaussian(x, mean, scale, Q, chunk_size):
-    """round(x / Q) -> symbols -> chunked range coder with the Gaussian CDF entries evaluated on the fly.
-    Byte-identical to calculate_cdf + arithmetic_encode (encodings_cuda.py:336-371)."""
-    for t, nm in ((x, "x"), (mean, "mean"), (scale, "scale"), (Q, "Q")):
-        _chk(t, nm)
-    n = int(x.shape[0])
-    mn, mx = C.c_float(), C.c_float()
-    pb, nb, pc, nc = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
-    x32, m32, s32, q32 = _f32(x, mean, scale, Q)
-    _lib.check(_lib.lib().gsac_encode_gaussian(runtime.context(x.device), x32.data_ptr(), m32.data_ptr(), s32.data_ptr(),
-                                               q32.data_ptr(), n, int(chunk_size), C.byref(mn), C.byref(mx), C.byref(pb), C.byref(nb),
-                                               C.byref(pc), C.byref(nc), runtime.stream_ptr(x.device)))
-    out, cnt = _owned(pb, nb.value, np.uint8), _owned(pc, nc.value, np.int32)
-    return mn.value, mx.value, torch.from_numpy(out).to(x.device), torch.from_numpy(cnt).to(x.device)
-
-
-def decode_gaussian(mean, scale, Q, min_value, max_value, in_cache_all, in_cnt_all, chunk_size):
-    """Inverse of encode_gaussian: (sym + min) * Q, float32 on mean.device (encodings_cuda.py:399-433)."""
+# ---------------------------------------------------------------- the table-free Gaussian family
+# A "parameter block" is what tells the plain Gaussian from HAC++'s mixture in the eight calls below: the suffix of the export's name, the contiguous run
+# of ctypes arguments that carries the distribution, the tensors those point into (alive until the library call has returned), the element count and
+# the device.
+def _gauss_args(mean, scale, Q):
     for t, nm in ((mean, "mean"), (scale, "scale"), (Q, "Q")):
         _chk(t, nm)
-    data = np.ascontiguousarray(in_cache_all.detach().cpu().numpy().astype(np.uint8, copy=False))
-    cnt = np.ascontiguousarray(in_cnt_all.detach().cpu().numpy().astype(np.int32, copy=False))
-    n = int(mean.shape[0])
-    _check_cnt(cnt, [n], chunk_size, "decode_gaussian")
-    out = torch.empty(n, dtype=torch.float32, device=mean.device)
-    m32, s32, q32 = _f32(mean, scale, Q)
-    _lib.check(_lib.lib().gsac_decode_gaussian(runtime.context(mean.device), m32.data_ptr(), s32.data_ptr(), q32.data_ptr(), n,
-                                               float(min_value), float(max_value), data.ctypes.data, data.size, cnt.ctypes.data, int(chunk_size),
-                                               out.data_ptr(), runtime.stream_ptr(mean.device)))
-    return out
-
-
-def encode_gaussian_slices(x, mean, scale, Q, slice_start, chunk_size):
-    """All slices [slice_start[s], slice_start[s+1]) of an attribute in one call (gsac_encode_gaussian_slices).
-    Returns (mins, maxs, bytes, cnt) as numpy arrays: float32 (nslices) x 2, uint8, int32 (chunks, slice by slice)."""
-    for t, nm in ((x, "x"), (mean, "mean"), (scale, "scale"), (Q, "Q")):
-        _chk(t, nm)
-    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
-    ns = ss.size - 1
-    mins, maxs = np.empty(ns, dtype=np.float32), np.empty(ns, dtype=np.float32)
-    pb, nb, pc, nc = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
-    x32, m32, s32, q32 = _f32(x, mean, scale, Q)
-    _lib.check(_lib.lib().gsac_encode_gaussian_slices(runtime.context(x.device), x32.data_ptr(), m32.data_ptr(), s32.data_ptr(),
-                                                      q32.data_ptr(), ss.ctypes.data, ns, int(chunk_size), mins.ctypes.data, maxs.ctypes.data,
-                                                      C.byref(pb), C.byref(nb), C.byref(pc), C.byref(nc), runtime.stream_ptr(x.device)))
-    out, cnt = _owned(pb, nb.value, np.uint8), _owned(pc, nc.value, np.int32)
-    return mins, maxs, out, cnt
-
-
-def decode_gaussian_slices(mean, scale, Q, slice_start, mins, maxs, data, cnt, chunk_size):
-    """Inverse of encode_gaussian_slices; data / cnt are the concatenated payloads / chunk byte counts (numpy)."""
-    for t, nm in ((mean, "mean"), (scale, "scale"), (Q, "Q")):
-        _chk(t, nm)
-    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
-    mins = np.ascontiguousarray(mins, dtype=np.float32); maxs = np.ascontiguousarray(maxs, dtype=np.float32)
-    data = np.ascontiguousarray(data, dtype=np.uint8); cnt = np.ascontiguousarray(cnt, dtype=np.int32)
-    _check_cnt(cnt, np.diff(ss), chunk_size, "decode_gaussian_slices")
-    if mins.size != ss.size - 1 or maxs.size != ss.size - 1:
-        raise ValueError("decode_gaussian_slices: one (min, max) per slice")
-    out = torch.empty(int(ss[-1]), dtype=torch.float32, device=mean.device)
-    m32, s32, q32 = _f32(mean, scale, Q)
-    _lib.check(_lib.lib().gsac_decode_gaussian_slices(runtime.context(mean.device), m32.data_ptr(), s32.data_ptr(), q32.data_ptr(),
-                                                      ss.ctypes.data, ss.size - 1, mins.ctypes.data, maxs.ctypes.data, data.ctypes.data, data.size,
-                                                      cnt.ctypes.data, int(chunk_size), out.data_ptr(), runtime.stream_ptr(mean.device)))
-    return out
+    keep = _f32(mean, scale, Q)
+    return "gaussian", tuple(t.data_ptr() for t in keep), keep, int(mean.shape[0]), mean.device
 
 
 def _mix_args(mean_list, scale_list, prob_list, Q):
@@ -199,19 +143,94 @@ def _mix_args(mean_list, scale_list, prob_list, Q):
         for t, nm in ((m, f"mean[{i}]"), (s, f"scale[{i}]"), (p, f"prob[{i}]")):
             _chk(t, nm)
     _chk(Q, "Q")
-    keep = _f32(*mean_list, *scale_list, *prob_list, Q)      # alive until the library call has returned
-    return k, keep, runtime.ptrs(keep[:k]), runtime.ptrs(keep[k:2 * k]), runtime.ptrs(keep[2 * k:3 * k]), keep[3 * k]
+    keep = _f32(*mean_list, *scale_list, *prob_list, Q)
+    q32 = keep[3 * k]
+    args = (runtime.ptrs(keep[:k]), runtime.ptrs(keep[k:2 * k]), runtime.ptrs(keep[2 * k:3 * k]), k, q32.data_ptr())
+    return "gaussian_mixed", args, keep, int(q32.shape[0]), q32.device
+
+
+def _encode(x, block, chunk_size):
+    suffix, args, keep, _, _ = block
+    (x32,) = _f32(x)
+    mn, mx = C.c_float(), C.c_float()
+    pb, nb, pc, nc = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
+    _lib.check(getattr(_lib.lib(), "gsac_encode_" + suffix)(runtime.context(x.device), x32.data_ptr(), *args, int(x32.shape[0]), int(chunk_size),
+                                                            C.byref(mn), C.byref(mx), C.byref(pb), C.byref(nb), C.byref(pc), C.byref(nc),
+                                                            runtime.stream_ptr(x.device)))
+    out, cnt = _owned(pb, nb.value, np.uint8), _owned(pc, nc.value, np.int32)
+    return mn.value, mx.value, torch.from_numpy(out).to(x.device), torch.from_numpy(cnt).to(x.device)
+
+
+def _decode(block, min_value, max_value, in_cache_all, in_cnt_all, chunk_size, who):
+    suffix, args, keep, n, device = block
+    data = np.ascontiguousarray(in_cache_all.detach().cpu().numpy().astype(np.uint8, copy=False))
+    cnt = np.ascontiguousarray(in_cnt_all.detach().cpu().numpy().astype(np.int32, copy=False))
+    _check_cnt(cnt, [n], chunk_size, who)
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    _lib.check(getattr(_lib.lib(), "gsac_decode_" + suffix)(runtime.context(device), *args, n, float(min_value), float(max_value), data.ctypes.data, data.size,
+                                                            cnt.ctypes.data, int(chunk_size), out.data_ptr(), runtime.stream_ptr(device)))
+    return out
+
+
+def _encode_slices(x, block, slice_start, chunk_size):
+    suffix, args, keep, _, _ = block
+    (x32,) = _f32(x)
+    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
+    ns = ss.size - 1
+    mins, maxs = np.empty(ns, dtype=np.float32), np.empty(ns, dtype=np.float32)
+    pb, nb, pc, nc = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
+    _lib.check(getattr(_lib.lib(), f"gsac_encode_{suffix}_slices")(runtime.context(x.device), x32.data_ptr(), *args, ss.ctypes.data, ns, int(chunk_size),
+                                                                   mins.ctypes.data, maxs.ctypes.data, C.byref(pb), C.byref(nb), C.byref(pc), C.byref(nc),
+                                                                   runtime.stream_ptr(x.device)))
+    return mins, maxs, _owned(pb, nb.value, np.uint8), _owned(pc, nc.value, np.int32)
+
+
+def _decode_slices(block, slice_start, mins, maxs, data, cnt, chunk_size, who):
+    suffix, args, keep, _, device = block
+    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
+    mins = np.ascontiguousarray(mins, dtype=np.float32); maxs = np.ascontiguousarray(maxs, dtype=np.float32)
+    data = np.ascontiguousarray(data, dtype=np.uint8); cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+    _check_cnt(cnt, np.diff(ss), chunk_size, who)
+    if mins.size != ss.size - 1 or maxs.size != ss.size - 1:
+        raise ValueError(f"{who}: one (min, max) per slice")
+    out = torch.empty(int(ss[-1]), dtype=torch.float32, device=device)
+    _lib.check(getattr(_lib.lib(), f"gsac_decode_{suffix}_slices")(runtime.context(device), *args, ss.ctypes.data, ss.size - 1, mins.ctypes.data, maxs.ctypes.data,
+                                                                   data.ctypes.data, data.size, cnt.ctypes.data, int(chunk_size), out.data_ptr(),
+                                                                   runtime.stream_ptr(device)))
+    return out
+
+
+def encode_gaussian(x, mean, scale, Q, chunk_size):
+    """round(x / Q) -> symbols -> chunked range coder with the Gaussian CDF entries evaluated on the fly.
+    Byte-identical to calculate_cdf + arithmetic_encode (encodings_cuda.py:336-371)."""
+    _chk(x, "x")
+    return _encode(x, _gauss_args(mean, scale, Q), chunk_size)
+
+
+def decode_gaussian(mean, scale, Q, min_value, max_value, in_cache_all, in_cnt_all, chunk_size):
+    """Inverse of encode_gaussian: (sym + min) * Q, float32 on mean.device (encodings_cuda.py:399-433)."""
+    return _decode(_gauss_args(mean, scale, Q), min_value, max_value, in_cache_all, in_cnt_all, chunk_size, "decode_gaussian")
+
+
+def encode_gaussian_slices(x, mean, scale, Q, slice_start, chunk_size):
+    """All slices [slice_start[s], slice_start[s+1]) of an attribute in one call (gsac_encode_gaussian_slices).
+    Returns (mins, maxs, bytes, cnt) as numpy arrays: float32 (nslices) x 2, uint8, int32 (chunks, slice by slice)."""
+    _chk(x, "x")
+    return _encode_slices(x, _gauss_args(mean, scale, Q), slice_start, chunk_size)
+
+
+def decode_gaussian_slices(mean, scale, Q, slice_start, mins, maxs, data, cnt, chunk_size):
+    """Inverse of encode_gaussian_slices; data / cnt are the concatenated payloads / chunk byte counts (numpy)."""
+    return _decode_slices(_gauss_args(mean, scale, Q), slice_start, mins, maxs, data, cnt, chunk_size, "decode_gaussian_slices")
 
 
 def calculate_cdf_mixed(mean_list, scale_list, prob_list, Q, min_value, max_value):
     """The mixture's (n, max-min+2) table: sum of calculate_cdf(mean_c, scale_c, Q) * prob_c over the components, clamped."""
-    k, keep, pm, ps, pp, q32 = _mix_args(mean_list, scale_list, prob_list, Q)
+    _, args, keep, n, device = _mix_args(mean_list, scale_list, prob_list, Q)
     mn, mx = int(min_value), int(max_value)
-    n = int(q32.shape[0])
-    lower = torch.zeros((n, mx - mn + 2), dtype=torch.float32, device=q32.device)
+    lower = torch.zeros((n, mx - mn + 2), dtype=torch.float32, device=device)
     if n:
-        _lib.check(_lib.lib().gsac_calculate_cdf_mixed(runtime.context(q32.device), pm, ps, pp, k, q32.data_ptr(), n, mn, mx, lower.data_ptr(),
-                                                        runtime.stream_ptr(q32.device)))
+        _lib.check(_lib.lib().gsac_calculate_cdf_mixed(runtime.context(device), *args, n, mn, mx, lower.data_ptr(), runtime.stream_ptr(device)))
     return lower
 
 
@@ -219,30 +238,12 @@ def encode_gaussian_mixed(x, mean_list, scale_list, prob_list, Q, chunk_size):
     """round(x / Q) -> symbols -> chunked range coder, the mixture's CDF entries evaluated on the fly.
     Byte-identical to calculate_cdf_mixed + arithmetic_encode."""
     _chk(x, "x")
-    k, keep, pm, ps, pp, q32 = _mix_args(mean_list, scale_list, prob_list, Q)
-    (x32,) = _f32(x)
-    n = int(x32.shape[0])
-    mn, mx = C.c_float(), C.c_float()
-    pb, nb, pc, nc = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
-    _lib.check(_lib.lib().gsac_encode_gaussian_mixed(runtime.context(x.device), x32.data_ptr(), pm, ps, pp, k, q32.data_ptr(), n, int(chunk_size),
-                                                     C.byref(mn), C.byref(mx), C.byref(pb), C.byref(nb), C.byref(pc), C.byref(nc),
-                                                     runtime.stream_ptr(x.device)))
-    out, cnt = _owned(pb, nb.value, np.uint8), _owned(pc, nc.value, np.int32)
-    return mn.value, mx.value, torch.from_numpy(out).to(x.device), torch.from_numpy(cnt).to(x.device)
+    return _encode(x, _mix_args(mean_list, scale_list, prob_list, Q), chunk_size)
 
 
 def decode_gaussian_mixed(mean_list, scale_list, prob_list, Q, min_value, max_value, in_cache_all, in_cnt_all, chunk_size):
     """Inverse of encode_gaussian_mixed: (sym + min) * Q, float32 on the parameters' device."""
-    k, keep, pm, ps, pp, q32 = _mix_args(mean_list, scale_list, prob_list, Q)
-    data = np.ascontiguousarray(in_cache_all.detach().cpu().numpy().astype(np.uint8, copy=False))
-    cnt = np.ascontiguousarray(in_cnt_all.detach().cpu().numpy().astype(np.int32, copy=False))
-    n = int(q32.shape[0])
-    _check_cnt(cnt, [n], chunk_size, "decode_gaussian_mixed")
-    out = torch.empty(n, dtype=torch.float32, device=q32.device)
-    _lib.check(_lib.lib().gsac_decode_gaussian_mixed(runtime.context(q32.device), pm, ps, pp, k, q32.data_ptr(), n, float(min_value), float(max_value),
-                                                     data.ctypes.data, data.size, cnt.ctypes.data, int(chunk_size), out.data_ptr(),
-                                                     runtime.stream_ptr(q32.device)))
-    return out
+    return _decode(_mix_args(mean_list, scale_list, prob_list, Q), min_value, max_value, in_cache_all, in_cnt_all, chunk_size, "decode_gaussian_mixed")
 
 
 def encode_gaussian_mixed_slices(x, mean_list, scale_list, prob_list, Q, slice_start, chunk_size):
@@ -250,30 +251,9 @@ def encode_gaussian_mixed_slices(x, mean_list, scale_list, prob_list, Q, slice_s
     ten-channel groups per 3000-anchor slice, each group under a two-component mixture (HAC-plus/scene/gaussian_model.py:1300-1321).
     Returns (mins, maxs, bytes, cnt) as numpy arrays, as encode_gaussian_slices does."""
     _chk(x, "x")
-    k, keep, pm, ps, pp, q32 = _mix_args(mean_list, scale_list, prob_list, Q)
-    (x32,) = _f32(x)
-    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
-    ns = ss.size - 1
-    mins, maxs = np.empty(ns, dtype=np.float32), np.empty(ns, dtype=np.float32)
-    pb, nb, pc, nc = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
-    _lib.check(_lib.lib().gsac_encode_gaussian_mixed_slices(runtime.context(x.device), x32.data_ptr(), pm, ps, pp, k, q32.data_ptr(), ss.ctypes.data, ns,
-                                                            int(chunk_size), mins.ctypes.data, maxs.ctypes.data, C.byref(pb), C.byref(nb), C.byref(pc),
-                                                            C.byref(nc), runtime.stream_ptr(x.device)))
-    out, cnt = _owned(pb, nb.value, np.uint8), _owned(pc, nc.value, np.int32)
-    return mins, maxs, out, cnt
+    return _encode_slices(x, _mix_args(mean_list, scale_list, prob_list, Q), slice_start, chunk_size)
 
 
 def decode_gaussian_mixed_slices(mean_list, scale_list, prob_list, Q, slice_start, mins, maxs, data, cnt, chunk_size):
     """Inverse of encode_gaussian_mixed_slices."""
-    k, keep, pm, ps, pp, q32 = _mix_args(mean_list, scale_list, prob_list, Q)
-    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
-    mins = np.ascontiguousarray(mins, dtype=np.float32); maxs = np.ascontiguousarray(maxs, dtype=np.float32)
-    data = np.ascontiguousarray(data, dtype=np.uint8); cnt = np.ascontiguousarray(cnt, dtype=np.int32)
-    _check_cnt(cnt, np.diff(ss), chunk_size, "decode_gaussian_mixed_slices")
-    if mins.size != ss.size - 1 or maxs.size != ss.size - 1:
-        raise ValueError("decode_gaussian_mixed_slices: one (min, max) per slice")
-    out = torch.empty(int(ss[-1]), dtype=torch.float32, device=q32.device)
-    _lib.check(_lib.lib().gsac_decode_gaussian_mixed_slices(runtime.context(q32.device), pm, ps, pp, k, q32.data_ptr(), ss.ctypes.data, ss.size - 1,
-                                                            mins.ctypes.data, maxs.ctypes.data, data.ctypes.data, data.size, cnt.ctypes.data,
-                                                            int(chunk_size), out.data_ptr(), runtime.stream_ptr(q32.device)))
-    return out
+    return _decode_slices(_mix_args(mean_list, scale_list, prob_list, Q), slice_start, mins, maxs, data, cnt, chunk_size, "decode_gaussian_mixed_slices")

@@ -1,9 +1,8 @@
-// attributes.hip -- the HAC attribute-side kernels around the geometry path:
+// attributes.hip -- the chunked range coder of the HAC / HAC++ attributes:
 //   gsac_calculate_cdf   arithmetic.calculate_cdf      arithmetic.zip!arithmetic/arithmetic_kernel.cu:7-54
 //   gsac_encode/_decode  arithmetic.arithmetic_encode / arithmetic_decode   ...:94-232, 265-403
-//   gsge_forward         _gridencoder.grid_encode_forward   gridencoder.zip!gridencoder/src/gridencoder.cu:46-361
-//   gsge_forward_train   the same plus dy_dx                ...:363-657
-//   gsge_backward        _gridencoder.grid_encode_backward  ...:663-881, store-and-sum instead of atomicAdd
+//   gsac_*_gaussian*     the same without the CDF table: plain Gaussian or HAC++'s mixture, one stream or every slice of an attribute
+// (the hash-grid encoder is gridencoder.hip, the context MLP mlp2.hip)
 // Same byte format as the reference's CUDA coder (chunks of `chunk_size` symbols, per-chunk byte
 // counts), same integerisation of the float CDF rows (rint(cdf * (65536 - (Lp-1))) + index).
 //
@@ -15,7 +14,6 @@
 #include "octree.hpp"
 #include "primitives.hpp"
 #include "rangecoder.hpp"
-#include "sorted_sum.hpp"
 
 using namespace gpcc;
 
@@ -360,336 +358,6 @@ __global__ __launch_bounds__(64) void k_hac_decode_slices(CT table, const SliceC
                      [&](int64_t r, int s) { x[r] = ((float)s + (float)mn) * q[r]; });
 }
 
-// ------------------------------------------------------------------ hash-grid forward
-__device__ __forceinline__ uint32_t grid_index(int D, uint32_t F, uint32_t hashmap_size, uint32_t res, const uint32_t *pg)
-{
-    uint32_t stride = 1, index = 0;
-    for (int d = 0; d < D && stride <= hashmap_size; ++d) { index += pg[d] * stride; stride *= res; }
-    if (stride > hashmap_size) {  // gridencoder.cu:46-60: xor of coordinate * prime
-        const uint32_t primes[3] = {1u, 2654435761u, 805459861u};
-        uint32_t h = 0;
-        for (int d = 0; d < D; ++d) h ^= pg[d] * primes[d];
-        index = h;
-    }
-    return (index % hashmap_size) * F;
-}
-
-// The corners of point x at one level (gridencoder.cu:180-330), shared by the forward and the backward's key pass: per corner its
-// weight, whether it is used (no coordinate at 0 or res - 1, and an occupied voxel in its binary_vxl footprint) and, when used, its
-// element offset (index % hashmap_size) * F in the level's table.  Returns wn_re = 1 / (sum of the used weights, 1e-9 when none).
-template <int D>
-__device__ __forceinline__ float grid_corners(const float *x, uint32_t res, uint32_t hashmap_size, uint32_t F, uint32_t Rb, const uint8_t *__restrict__ binary_vxl,
-                                              float *w_list, uint32_t *idx_list, bool *use)
-{
-    float pos[D];
-    uint32_t pg[D];
-    for (int d = 0; d < D; ++d) {
-        const float t = x[d] * (float)(res - 2);
-        pos[d] = t + 0.5f;                           // (float)((double)t + 0.5): identical rounding
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
-    float wn = 0.0f;
-    for (int c = 0; c < (1 << D); ++c) {
-        float w = 1.0f;
-        uint32_t pl[D];
-        for (int d = 0; d < D; ++d) {
-            if ((c & (1 << d)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = min(pg[d] + 1u, res - 1u); }
-        }
-        bool zero = false;
-        for (int d = 0; d < D; ++d) zero |= (pl[d] == 0u || pl[d] == res - 1u);
-        bool m = true;
-        if (binary_vxl) {  // gridencoder.cu:262-317: any occupied voxel in the corner's footprint
-            m = false;
-            const float scale_re = (float)(1.0 / ((double)(float)res - 2.0));
-            int g0[D], g1[D];
-            for (int d = 0; d < D; ++d) {
-                const float pn = (float)(((double)(float)pl[d] - 0.5) * (double)scale_re);
-                float a = (pn - scale_re) * (float)Rb;
-                a = a < 0.0f ? 0.0f : a; a = a > (float)(Rb - 1) ? (float)(Rb - 1) : a;
-                g0[d] = (int)a;
-                float bb = (pn + scale_re) * (float)Rb;
-                bb = bb < 0.0f ? 0.0f : bb; bb = bb > (float)(Rb - 1) ? (float)(Rb - 1) : bb;
-                g1[d] = (int)bb;
-            }
-            if (D == 2) {
-                for (int ia = g0[0]; ia <= g1[0] && !m; ++ia)
-                    for (int ib = g0[1]; ib <= g1[1] && !m; ++ib) m = binary_vxl[(size_t)ia * Rb + ib] != 0;
-            } else if (D == 3) {
-                for (int ia = g0[0]; ia <= g1[0] && !m; ++ia)
-                    for (int ib = g0[1]; ib <= g1[1] && !m; ++ib)
-                        for (int ic = g0[D - 1]; ic <= g1[D - 1] && !m; ++ic) m = binary_vxl[((size_t)ia * Rb + ib) * Rb + ic] != 0;
-            } else {
-                for (int ia = g0[0]; ia <= g1[0] && !m; ++ia) m = binary_vxl[ia] != 0;
-            }
-        }
-        w_list[c] = w;
-        use[c] = !zero && m;
-        idx_list[c] = 0;
-        if (use[c]) { idx_list[c] = grid_index(D, F, hashmap_size, res, pl); wn += w; }
-    }
-    if (wn == 0.0f) wn = (float)((double)wn + 1e-9);
-    return (float)(1.0 / (double)wn);
-}
-
-template <int D, int F>
-__global__ __launch_bounds__(TB) void k_grid_forward(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
-                                                     const int *__restrict__ resolutions, float *__restrict__ outputs, uint32_t N, uint32_t Rb,
-                                                     const uint8_t *__restrict__ binary_vxl, const int *__restrict__ min_level_id)
-{
-    const uint32_t b = blockIdx.x * TB + threadIdx.x;
-    if (b >= N) return;
-    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
-    grid += (size_t)(uint32_t)offsets[level] * F;
-    const float *x = inputs + (size_t)b * D;
-    float *out = outputs + ((size_t)blockIdx.y * N + b) * F;
-    bool oob = false;
-    for (int d = 0; d < D; ++d) oob |= (x[d] < 0.0f || x[d] > 1.0f);
-    if (oob) { for (int ch = 0; ch < F; ++ch) out[ch] = 0.0f; return; }
-    const uint32_t hashmap_size = (uint32_t)(offsets[level + 1] - offsets[level]);
-    const uint32_t res = (uint32_t)resolutions[level];
-    float w_list[1 << D];
-    uint32_t idx_list[1 << D];
-    bool use[1 << D];
-    const float wn_re = grid_corners<D>(x, res, hashmap_size, F, Rb, binary_vxl, w_list, idx_list, use);
-    float r[F];
-    for (int ch = 0; ch < F; ++ch) r[ch] = 0.0f;
-    for (int c = 0; c < (1 << D); ++c)
-        if (use[c]) {
-            const float ww = w_list[c] * wn_re;
-            for (int ch = 0; ch < F; ++ch) r[ch] = __builtin_fmaf(ww, grid[idx_list[c] + ch], r[ch]);  // nvcc contracts mul+add (fmad) here
-        }
-    for (int ch = 0; ch < F; ++ch) out[ch] = r[ch];
-}
-
-template <int D>
-int grid_launch_f(hipStream_t st, int F, dim3 g, const float *in, const float *emb, const int *off, const int *res, float *out, uint32_t N, uint32_t Rb,
-                  const uint8_t *bv, const int *ml)
-{
-    switch (F) {
-    case 1: k_grid_forward<D, 1><<<g, TB, 0, st>>>(in, emb, off, res, out, N, Rb, bv, ml); break;
-    case 2: k_grid_forward<D, 2><<<g, TB, 0, st>>>(in, emb, off, res, out, N, Rb, bv, ml); break;
-    case 4: k_grid_forward<D, 4><<<g, TB, 0, st>>>(in, emb, off, res, out, N, Rb, bv, ml); break;
-    case 8: k_grid_forward<D, 8><<<g, TB, 0, st>>>(in, emb, off, res, out, N, Rb, bv, ml); break;
-    default: return fail(GPCC_ERR_ARG, "GridEncoding: n_features must be 1, 2, 4 or 8");
-    }
-    LAUNCH_CHECK();
-    return GPCC_OK;
-}
-
-// ------------------------------------------------------------------ hash-grid training: dy_dx and backward
-// dy_dx[gd][ch] of one point at one level as gridencoder.cu:363-657 writes it: per axis gd, over the 2^(D-1) edges along gd in ascending
-// edge index, w = (res - 2) * prod_{d != gd} (1 - pos[d] or pos[d]) times (g_right - g_left), the two corners at pg[gd] and
-// min(pg[gd] + 1, res - 1); a corner with a coordinate at 0 or res - 1 reads as 0.  No wn normalisation and no binary_vxl mask (the
-// reference's formula: the exact derivative only inside the grid with all corners used).
-template <int D, int F>
-__device__ __forceinline__ void grid_dydx(const float *x, const float *__restrict__ grid, uint32_t res, uint32_t hashmap_size, float (&g)[D][F])
-{
-    float pos[D];
-    uint32_t pg[D];
-    for (int d = 0; d < D; ++d) {
-        const float t = x[d] * (float)(res - 2);
-        pos[d] = t + 0.5f;
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
-    for (int gd = 0; gd < D; ++gd) {
-        for (int ch = 0; ch < F; ++ch) g[gd][ch] = 0.0f;
-        for (int e = 0; e < (1 << (D - 1)); ++e) {
-            float w = (float)(res - 2);
-            uint32_t pl[D];
-            for (int nd = 0; nd < D - 1; ++nd) {
-                const int d = nd >= gd ? nd + 1 : nd;
-                if ((e & (1 << nd)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
-                else { w *= pos[d]; pl[d] = min(pg[d] + 1u, res - 1u); }
-            }
-            bool zl = false, zr = false;
-            pl[gd] = pg[gd];
-            for (int d = 0; d < D; ++d) zl |= (pl[d] == 0u || pl[d] == res - 1u);
-            const uint32_t il = zl ? 0u : grid_index(D, F, hashmap_size, res, pl);
-            pl[gd] = min(pg[gd] + 1u, res - 1u);
-            for (int d = 0; d < D; ++d) zr |= (pl[d] == 0u || pl[d] == res - 1u);
-            const uint32_t ir = zr ? 0u : grid_index(D, F, hashmap_size, res, pl);
-            for (int ch = 0; ch < F; ++ch) {
-                const float gl = zl ? 0.0f : grid[il + ch], gr = zr ? 0.0f : grid[ir + ch];
-                g[gd][ch] = __builtin_fmaf(w, gr - gl, g[gd][ch]);
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ bool grid_oob(const float *x, int D)
-{
-    bool oob = false;
-    for (int d = 0; d < D; ++d) oob |= (x[d] < 0.0f || x[d] > 1.0f);
-    return oob;
-}
-
-// dy_dx (N, L, D, F) of the training forward: one thread per (point, level), beside the unchanged k_grid_forward
-template <int D, int F>
-__global__ __launch_bounds__(TB) void k_grid_dydx(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
-                                                  const int *__restrict__ resolutions, float *__restrict__ dy_dx, uint32_t N, const int *__restrict__ min_level_id)
-{
-    const uint32_t b = blockIdx.x * TB + threadIdx.x;
-    if (b >= N) return;
-    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
-    const float *x = inputs + (size_t)b * D;
-    float *out = dy_dx + ((size_t)b * gridDim.y + blockIdx.y) * D * F;
-    float g[D][F];
-    if (grid_oob(x, D)) {
-        for (int d = 0; d < D; ++d)
-            for (int ch = 0; ch < F; ++ch) g[d][ch] = 0.0f;
-    } else {
-        grid_dydx<D, F>(x, grid + (size_t)(uint32_t)offsets[level] * F, (uint32_t)resolutions[level], (uint32_t)(offsets[level + 1] - offsets[level]), g);
-    }
-    for (int d = 0; d < D; ++d)
-        for (int ch = 0; ch < F; ++ch) out[d * F + ch] = g[d][ch];
-}
-
-// Backward, embedding gradient: store and sum, no float atomics.
-//   key pass   one thread per (point b, level l): corner c's contribution lives at slot s = (b L + l) 2^D + c; the key is its table row
-//              offsets[level] + idx / F (the sentinel n_rows when the corner is unused or the point out of range), the value the slot,
-//              and wts[s] = w_c wn_re.
-//   sort       stable LSD radix sort on the key: each row's contributions become one run in ascending slot order.
-//   sum, combine   sorted_sum.hpp (shared with the tri-plane's backward): one thread per chunk of GB_CHUNK sorted entries sums each run it
-//              holds in order (fmaf(w, grad[l, b, ch], acc)); runs that cross chunks are finished by their first chunk's thread.
-// Every row is written by exactly one thread and summed in an order fixed by the sorted keys alone: bitwise reproducible.
-constexpr int GB_CHUNK = 32;
-
-template <int D>
-__global__ __launch_bounds__(TB) void k_grid_bwd_keys(const float *__restrict__ inputs, const int *__restrict__ offsets, const int *__restrict__ resolutions,
-                                                      uint32_t N, uint32_t F, uint32_t Rb, const uint8_t *__restrict__ binary_vxl,
-                                                      const int *__restrict__ min_level_id, uint32_t n_rows, uint64_t *__restrict__ keys,
-                                                      uint32_t *__restrict__ slots, float *__restrict__ wts)
-{
-    const uint32_t b = blockIdx.x * TB + threadIdx.x;
-    if (b >= N) return;
-    const uint32_t level = min_level_id ? (uint32_t)min_level_id[b] + blockIdx.y : blockIdx.y;
-    const uint32_t s0 = (b * gridDim.y + blockIdx.y) << D;
-    const float *x = inputs + (size_t)b * D;
-    float w_list[1 << D];
-    uint32_t idx_list[1 << D];
-    bool use[1 << D];
-    float wn_re = 0.0f;
-    const bool oob = grid_oob(x, D);
-    const uint32_t off = (uint32_t)offsets[level];
-    if (!oob) wn_re = grid_corners<D>(x, (uint32_t)resolutions[level], (uint32_t)(offsets[level + 1] - offsets[level]), F, Rb, binary_vxl, w_list, idx_list, use);
-    for (int c = 0; c < (1 << D); ++c) {
-        uint32_t row = n_rows;
-        if (!oob && use[c]) {
-            row = off + idx_list[c] / F;
-            if (row >= n_rows) row = n_rows;     // offsets beyond the caller's table: dropped, never written out of bounds
-            else wts[s0 + c] = w_list[c] * wn_re;
-        }
-        keys[s0 + c] = row;
-        slots[s0 + c] = s0 + c;
-    }
-}
-
-template <int F>
-__device__ __forceinline__ void gb_add(float (&acc)[F], const float *__restrict__ grad, const uint32_t *__restrict__ slots, const float *__restrict__ wts,
-                                       int64_t i, int D, uint32_t N, uint32_t L)
-{
-    const uint32_t s = slots[i], q = s >> D, b = q / L, l = q - b * L;
-    const float w = wts[s];
-    const float *g = grad + ((size_t)l * N + b) * F;
-    for (int ch = 0; ch < F; ++ch) acc[ch] = __builtin_fmaf(w, g[ch], acc[ch]);
-}
-
-template <int F> struct GridRowSum {
-    const float *__restrict__ grad;
-    const uint32_t *__restrict__ slots;
-    const float *__restrict__ wts;
-    int D;
-    uint32_t N, L;
-    float *__restrict__ grad_emb, *__restrict__ head, *__restrict__ tail;
-    float acc[F];
-    __device__ __forceinline__ void zero() { for (int ch = 0; ch < F; ++ch) acc[ch] = 0.0f; }
-    __device__ __forceinline__ void add(int64_t i) { gb_add<F>(acc, grad, slots, wts, i, D, N, L); }
-    __device__ __forceinline__ void to_head(int64_t t) { for (int ch = 0; ch < F; ++ch) head[t * F + ch] = acc[ch]; }
-    __device__ __forceinline__ void to_tail(int64_t t) { for (int ch = 0; ch < F; ++ch) tail[t * F + ch] = acc[ch]; }
-    __device__ __forceinline__ void to_row(uint32_t row) { for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += acc[ch]; }
-};
-
-template <int F>
-__global__ __launch_bounds__(TB) void k_grid_bwd_sum(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ slots, const float *__restrict__ wts,
-                                                     const float *__restrict__ grad, int D, uint32_t N, uint32_t L, int64_t E, uint32_t n_rows,
-                                                     float *__restrict__ grad_emb, float *__restrict__ head, float *__restrict__ tail, uint8_t *__restrict__ own)
-{
-    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
-    if (t * GB_CHUNK >= E) return;
-    GridRowSum<F> a{grad, slots, wts, D, N, L, grad_emb, head, tail, {}};
-    sorted_chunk_sum<GB_CHUNK>(keys, t, E, n_rows, a, own);
-}
-
-// the owners' walk: partials are read GB_WALK chunks at a time
-constexpr int GB_WALK = 8;
-
-template <int F>
-__global__ __launch_bounds__(TB) void k_grid_bwd_combine(const uint64_t *__restrict__ keys, int64_t E, int64_t nchunks, const float *__restrict__ head,
-                                                         const float *__restrict__ tail, const uint8_t *__restrict__ own, float *__restrict__ grad_emb)
-{
-    const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
-    sorted_combine<GB_CHUNK, F, GB_WALK>(keys, E, nchunks, t, head, tail, F, own, [&](uint32_t row, const float (&s)[F]) {
-        for (int ch = 0; ch < F; ++ch) grad_emb[(size_t)row * F + ch] += s[ch];
-    });
-}
-
-// Backward, input gradient: one thread per point, dy_dx recomputed; levels outer, channels inner (gridencoder.cu:857-881)
-template <int D, int F>
-__global__ __launch_bounds__(TB) void k_grid_bwd_inputs(const float *__restrict__ inputs, const float *__restrict__ grid, const int *__restrict__ offsets,
-                                                        const int *__restrict__ resolutions, const float *__restrict__ grad, uint32_t N, uint32_t L,
-                                                        const int *__restrict__ min_level_id, float *__restrict__ grad_inputs)
-{
-    const uint32_t b = blockIdx.x * TB + threadIdx.x;
-    if (b >= N) return;
-    const float *x = inputs + (size_t)b * D;
-    float r[D];
-    for (int d = 0; d < D; ++d) r[d] = 0.0f;
-    if (!grid_oob(x, D)) {
-        const uint32_t ml = min_level_id ? (uint32_t)min_level_id[b] : 0u;
-        for (uint32_t l = 0; l < L; ++l) {
-            const uint32_t level = ml + l;
-            float g[D][F];
-            grid_dydx<D, F>(x, grid + (size_t)(uint32_t)offsets[level] * F, (uint32_t)resolutions[level], (uint32_t)(offsets[level + 1] - offsets[level]), g);
-            const float *gp = grad + ((size_t)l * N + b) * F;
-            for (int ch = 0; ch < F; ++ch)
-                for (int d = 0; d < D; ++d) r[d] = __builtin_fmaf(gp[ch], g[d][ch], r[d]);
-        }
-    }
-    for (int d = 0; d < D; ++d) grad_inputs[(size_t)b * D + d] = r[d];
-}
-
-template <int D>
-int grid_dydx_launch(hipStream_t st, int F, dim3 g, const float *in, const float *emb, const int *off, const int *res, float *dy_dx, uint32_t N, const int *ml)
-{
-    switch (F) {
-    case 1: k_grid_dydx<D, 1><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
-    case 2: k_grid_dydx<D, 2><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
-    case 4: k_grid_dydx<D, 4><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
-    case 8: k_grid_dydx<D, 8><<<g, TB, 0, st>>>(in, emb, off, res, dy_dx, N, ml); break;
-    default: return fail(GPCC_ERR_ARG, "GridEncoding: n_features must be 1, 2, 4 or 8");
-    }
-    LAUNCH_CHECK();
-    return GPCC_OK;
-}
-
-template <int D, int F>
-void grid_bwd_inputs_launch(hipStream_t st, const float *in, const float *emb, const int *off, const int *res, const float *grad, uint32_t N, uint32_t L,
-                            const int *ml, float *gi)
-{
-    k_grid_bwd_inputs<D, F><<<(unsigned)cdiv(N, TB), TB, 0, st>>>(in, emb, off, res, grad, N, L, ml, gi);
-}
-
-template <int F>
-void grid_bwd_sum_launch(hipStream_t st, const uint64_t *keys, const uint32_t *slots, const float *wts, const float *grad, int D, uint32_t N, uint32_t L,
-                         int64_t E, uint32_t n_rows, float *grad_emb, float *head, float *tail, uint8_t *own, int64_t nchunks)
-{
-    k_grid_bwd_sum<F><<<(unsigned)cdiv(nchunks, TB), TB, 0, st>>>(keys, slots, wts, grad, D, N, L, E, n_rows, grad_emb, head, tail, own);
-    k_grid_bwd_combine<F><<<(unsigned)cdiv(nchunks, TB), TB, 0, st>>>(keys, E, nchunks, head, tail, own, grad_emb);
-}
-
 }  // namespace
 
 extern "C" int gsac_calculate_cdf(gpcc_ctx *ctx, const float *mean, const float *scale, const float *Q, int64_t n, int min_value, int max_value,
@@ -705,11 +373,47 @@ extern "C" int gsac_calculate_cdf(gpcc_ctx *ctx, const float *mean, const float 
     return GPCC_OK;
 }
 
-template <typename CT>
-static int gsac_encode_impl(gpcc_ctx *ctx, const int16_t *sym, CT cdf, int chunk_size, int64_t n, int lp, const uint8_t **bytes_out,
-                           int64_t *nbytes_out, const int32_t **cnt_out, int64_t *nchunks_out, void *stream, bool keep_arena = false)
+// where an encoder leaves its result: payload and chunk byte counts in the context's pinned buffers, valid until the context's next call
+struct CoderOut {
+    const uint8_t **bytes; int64_t *nbytes; const int32_t **cnt; int64_t *nchunks;
+    bool null() const { return !bytes || !nbytes || !cnt || !nchunks; }
+};
+
+// The tail of every encoder here, from the packed (low, high) words to the caller's pointers: lane-per-chunk coder, compaction, chunk byte counts
+// and payload into the pinned buffers.  The slices encoder also gets its (min, max) table back between the two synchronisations (mm: 2 * nslices
+// ints on the device; nullptr for a single stream).
+static int encode_tail(gpcc_ctx *ctx, hipStream_t st, const uint32_t *lohi, const RcChunk *dch, int nch, uint8_t *scratch, uint32_t sstride, uint32_t *dcnt,
+                       uint32_t *doff, uint8_t *payload, CoderOut out, const int32_t *mm = nullptr, int nslices = 0, float *min_out = nullptr,
+                       float *max_out = nullptr)
 {
-    if (!ctx || !sym || !bytes_out || !nbytes_out || !cnt_out || !nchunks_out) return fail(GPCC_ERR_ARG, "null argument");
+    GP_TRY(rc_encode_launch(st, lohi, dch, nch, scratch, sstride, dcnt));
+    GP_TRY(exclusive_scan_u32(ctx, st, dcnt, doff, nch, doff + nch));
+    GP_TRY(rc_compact_launch(st, scratch, sstride, dcnt, doff, nullptr, nch, payload));
+    GP_TRY(ctx->hstage.reserve(4 * (size_t)nch + 8 * (size_t)nslices + 64));
+    uint32_t *hcnt = reinterpret_cast<uint32_t *>(ctx->hstage.p);
+    int32_t *hmm = reinterpret_cast<int32_t *>(hcnt + nch + 1);
+    HIP_TRY(hipMemcpyAsync(hcnt, dcnt, 4 * (size_t)nch, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hcnt + nch, doff + nch, 4, hipMemcpyDeviceToHost, st));
+    if (mm) HIP_TRY(hipMemcpyAsync(hmm, mm, 8 * (size_t)nslices, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    GP_TRY(device_error_check(ctx));
+    for (int s = 0; s < nslices; ++s) {
+        if (hmm[2 * s + 1] - hmm[2 * s] + 2 > 32767) return fail(GPCC_ERR_RANGE, "slice %d: quantised values span %d levels (int16 symbols)", s, hmm[2 * s + 1] - hmm[2 * s] + 1);
+        min_out[s] = (float)hmm[2 * s]; max_out[s] = (float)hmm[2 * s + 1];
+    }
+    const size_t total = hcnt[nch];
+    GP_TRY(ctx->hbytes.reserve(total + 16));
+    if (total) HIP_TRY(hipMemcpyAsync(ctx->hbytes.p, payload, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out.bytes = ctx->hbytes.p; *out.nbytes = (int64_t)total;
+    *out.cnt = reinterpret_cast<const int32_t *>(hcnt); *out.nchunks = nch;
+    return GPCC_OK;
+}
+
+template <typename CT>
+static int gsac_encode_impl(gpcc_ctx *ctx, const int16_t *sym, CT cdf, int chunk_size, int64_t n, int lp, CoderOut out, void *stream, bool keep_arena = false)
+{
+    if (!ctx || !sym || out.null()) return fail(GPCC_ERR_ARG, "null argument");
     if (n <= 0 || chunk_size <= 0 || lp < 2) return fail(GPCC_ERR_ARG, "bad size");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
@@ -727,29 +431,14 @@ static int gsac_encode_impl(gpcc_ctx *ctx, const int16_t *sym, CT cdf, int chunk
     HIP_TRY(hipStreamSynchronize(st));
     k_hac_pack<CT><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(cdf, sym, n, lp, chunk_size, (uint32_t)nch, lohi);
     LAUNCH_CHECK();
-    GP_TRY(rc_encode_launch(st, lohi, dch, nch, scratch, sstride, dcnt));
-    GP_TRY(exclusive_scan_u32(ctx, st, dcnt, doff, nch, doff + nch));
-    GP_TRY(rc_compact_launch(st, scratch, sstride, dcnt, doff, nullptr, nch, payload));
-    GP_TRY(ctx->hstage.reserve(4 * (size_t)nch + 64));
-    uint32_t *hcnt = reinterpret_cast<uint32_t *>(ctx->hstage.p);
-    HIP_TRY(hipMemcpyAsync(hcnt, dcnt, 4 * (size_t)nch, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hcnt + nch, doff + nch, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    GP_TRY(device_error_check(ctx));
-    const size_t total = hcnt[nch];
-    GP_TRY(ctx->hbytes.reserve(total + 16));
-    if (total) HIP_TRY(hipMemcpyAsync(ctx->hbytes.p, payload, total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *bytes_out = ctx->hbytes.p; *nbytes_out = (int64_t)total;
-    *cnt_out = reinterpret_cast<const int32_t *>(hcnt); *nchunks_out = nch;
-    return GPCC_OK;
+    return encode_tail(ctx, st, lohi, dch, nch, scratch, sstride, dcnt, doff, payload, out);
 }
 
 extern "C" int gsac_encode(gpcc_ctx *ctx, const int16_t *sym, const float *cdf, int chunk_size, int64_t n, int lp, const uint8_t **bytes_out,
                            int64_t *nbytes_out, const int32_t **cnt_out, int64_t *nchunks_out, void *stream)
 {
     if (!cdf) return fail(GPCC_ERR_ARG, "null argument");
-    return gsac_encode_impl<const float *>(ctx, sym, cdf, chunk_size, n, lp, bytes_out, nbytes_out, cnt_out, nchunks_out, stream);
+    return gsac_encode_impl<const float *>(ctx, sym, cdf, chunk_size, n, lp, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
 }
 
 // the same with ONE row for all symbols (lp <= 4 entries, e.g. (0, 1 - p, 1) for a Bernoulli source): byte-identical to gsac_encode on the table that
@@ -760,14 +449,14 @@ extern "C" int gsac_encode_const(gpcc_ctx *ctx, const int16_t *sym, const float 
     if (!row_host || lp < 2 || lp > 4) return fail(GPCC_ERR_ARG, "constant-row coder: 2 <= lp <= 4");
     ConstTable t = {};
     for (int i = 0; i < lp; ++i) t.c[i] = row_host[i];
-    return gsac_encode_impl<ConstTable>(ctx, sym, t, chunk_size, n, lp, bytes_out, nbytes_out, cnt_out, nchunks_out, stream);
+    return gsac_encode_impl<ConstTable>(ctx, sym, t, chunk_size, n, lp, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
 }
 
 extern "C" int gsac_encode_u16(gpcc_ctx *ctx, const int16_t *sym, const uint16_t *cdf, int chunk_size, int64_t n, int lp, const uint8_t **bytes_out,
                                int64_t *nbytes_out, const int32_t **cnt_out, int64_t *nchunks_out, void *stream)
 {
     if (!cdf) return fail(GPCC_ERR_ARG, "null argument");
-    return gsac_encode_impl<const uint16_t *>(ctx, sym, cdf, chunk_size, n, lp, bytes_out, nbytes_out, cnt_out, nchunks_out, stream);
+    return gsac_encode_impl<const uint16_t *>(ctx, sym, cdf, chunk_size, n, lp, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
 }
 
 template <typename CT>
@@ -828,255 +517,22 @@ extern "C" int gsac_decode_u16(gpcc_ctx *ctx, const uint16_t *cdf, const uint8_t
     return gsac_decode_impl<const uint16_t *>(ctx, cdf, bytes, nbytes, cnt, chunk_size, n, lp, sym_out, stream);
 }
 
-// ------------------------------------------------------------------ mlp_grid (a16): Linear - ReLU - Linear
-// HAC's context MLP (scene/gaussian_model.py:258-262: Linear(96, 100) - ReLU - Linear(100, 175)) on the hash-grid
-// features of a slice of anchors.  Encoder and decoder must obtain bit-identical means / scales / step sizes from it,
-// so the arithmetic is specified, as for the geometry heads: acc = bias; for k ascending: acc = fmaf(x[k], W[c][k], acc).
-// 16 rows per 256-thread block: the rows and their hidden activations live in LDS, every thread walks the k chain of
-// its outputs; the two weight matrices (38 KB + 70 KB) stay in L1/L2.
-namespace {
-constexpr int MLP_ROWS = 16;
-__global__ __launch_bounds__(TB) void k_mlp2(const float *__restrict__ x, const float *__restrict__ w1, const float *__restrict__ b1,
-                                             const float *__restrict__ w2, const float *__restrict__ b2, int64_t n, int din, int dh, int dout,
-                                             float slope, float *__restrict__ y)
-{
-    extern __shared__ float sm[];
-    float *xs = sm, *hs = sm + MLP_ROWS * din;
-    const int64_t row0 = (int64_t)blockIdx.x * MLP_ROWS;
-    const int rows = (int)min((int64_t)MLP_ROWS, n - row0);
-    for (int i = threadIdx.x; i < rows * din; i += TB) xs[i] = x[row0 * din + i];
-    __syncthreads();
-    for (int i = threadIdx.x; i < rows * dh; i += TB) {
-        const int r = i / dh, c = i - r * dh;
-        const float *w = w1 + (size_t)c * din, *xr = xs + r * din;
-        float acc = b1[c];
-        for (int k = 0; k < din; ++k) acc = __builtin_fmaf(xr[k], w[k], acc);
-        hs[i] = acc > 0.0f ? acc : (slope != 0.0f ? acc * slope : 0.0f);   // ReLU (slope 0) or LeakyReLU(slope): x > 0 ? x : x * slope
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < rows * dout; i += TB) {
-        const int r = i / dout, c = i - r * dout;
-        const float *w = w2 + (size_t)c * dh, *hr = hs + r * dh;
-        float acc = b2[c];
-        for (int k = 0; k < dh; ++k) acc = __builtin_fmaf(hr[k], w[k], acc);
-        y[(row0 + r) * dout + c] = acc;
-    }
-}
-}  // namespace
-
-namespace {
-// The same two layers on the matrix pipe (round 3; k_mlp2 above stays for layer sizes this kernel does not take and as the
-// readable statement of the arithmetic).  v_mfma_f32_16x16x4_f32 with the bias as the initial accumulator is the specified
-// chain -- acc = b; for k ascending: acc = fmaf(x[k], W[c][k], acc) -- exactly (the heads of the geometry network rely on the
-// same fact): MFMA number kk covers k = 4 kk .. 4 kk + 3, lane group g supplying k = 4 kk + g.  16 rows x 16 outputs per
-// accumulator tile: 16 anchors are 7 x 24 + 11 x 25 = 443 MFMAs for HAC's 96-100-175 mlp_grid instead of ~55 k scalar
-// fmas per row at one lane each (9.5 ms per million anchors at 5.8 TFLOP/s; the matrix pipes need 0.4 ms).
-// One persistent workgroup per CU: both weight matrices in LDS ([c][k] at a pitch of K + 2 floats: the 32 lanes of an LDS
-// read group hit 32 different banks), every wave takes whole 16-row tiles: the rows staged in LDS, the hidden layer written
-// back over them, no block barrier after the weights have landed.
-typedef float f32x4m __attribute__((ext_vector_type(4)));
-constexpr int MLPM_WAVES_MAX = 8;   // waves per workgroup: 8 (two per SIMD: one's row loads, stores and drains under the other's MFMA chains) when the class's LDS allows, else 4
-// DIN / DH / DOUT are the CLASS of the kernel (register arrays and LDS pitches are compile-time); the layer's own sizes din <= DIN,
-// dh <= DH, dout <= DOUT are run-time: weights, biases and input columns beyond them are zeros in LDS, so the chain of an output
-// is its own k = 0 .. din - 1 steps followed by fmaf(0, 0, acc) steps, which leave acc unchanged.  HAC's 96-100-175 runs in its
-// exact class (no padding); HAC++'s mlp_grid (48-100-195 / 225) and its five channel-context MLPs (150 + 10 c - 40 - 30,
-// LeakyReLU) in classes <48, 100, 240> and <192, 40, 32> (HAC-plus/scene/gaussian_model.py:117-168, 370-374).
-template <int DIN, int DH, int DOUT>
-__global__ __launch_bounds__(64 * MLPM_WAVES_MAX) void k_mlp2_mfma(const float *__restrict__ x, const float *__restrict__ w1, const float *__restrict__ b1,
-                                                              const float *__restrict__ w2, const float *__restrict__ b2, int64_t n, int din, int dh, int dout,
-                                                              float slope, float *__restrict__ y, int PX)
-{
-    static_assert(DIN % 4 == 0 && DH % 4 == 0, "whole MFMA k-steps");
-    constexpr int NT1 = (DH + 15) / 16, NT2 = (DOUT + 15) / 16, P1 = DIN + 2, P2 = DH + 2;
-    // W1 holds DH rows and W2 DOUT rows, not whole tiles of 16: the B operands of the last tile's padding outputs are read from whatever follows
-    // (inside the allocation) -- they only reach accumulator columns that are never stored (hidden units >= DH, outputs >= dout)
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *W1s = sm, *W2s = W1s + DH * P1, *B1s = W2s + DOUT * P2, *B2s = B1s + NT1 * 16, *XS = B2s + NT2 * 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x, MLPM_WAVES = nthreads >> 6;
-    const int e = lane & 15, g = lane >> 4;
-    for (int i0 = tid; i0 < DH * DIN; i0 += 4 * nthreads) {     // (four loads in flight per trip, see the tile loads below)
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int i = i0 + u * nthreads, c = i / DIN, k = i - c * DIN; v[u] = (i < DH * DIN && c < dh && k < din) ? w1[(size_t)c * din + k] : 0.0f; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int i = i0 + u * nthreads, c = i / DIN, k = i - c * DIN; if (i < DH * DIN) W1s[c * P1 + k] = v[u]; }
-    }
-    for (int i0 = tid; i0 < DOUT * DH; i0 += 4 * nthreads) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int i = i0 + u * nthreads, c = i / DH, k = i - c * DH; v[u] = (i < DOUT * DH && c < dout && k < dh) ? w2[(size_t)c * dh + k] : 0.0f; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int i = i0 + u * nthreads, c = i / DH, k = i - c * DH; if (i < DOUT * DH) W2s[c * P2 + k] = v[u]; }
-    }
-    for (int i = tid; i < NT1 * 16; i += nthreads) B1s[i] = i < dh ? b1[i] : 0.0f;
-    for (int i = tid; i < NT2 * 16; i += nthreads) B2s[i] = i < dout ? b2[i] : 0.0f;
-    __syncthreads();
-    float *xs = XS + wave * 16 * PX;
-    const int64_t ntiles = (n + 15) / 16;
-    for (int64_t tile = (int64_t)blockIdx.x * MLPM_WAVES + wave; tile < ntiles; tile += (int64_t)gridDim.x * MLPM_WAVES) {
-        const int64_t row0 = tile * 16;
-        // the tile's rows: coalesced float2 loads (rows past n: the last row again), the wave's own LDS slice
-        // (loads in batches that are in flight together: as one run-time loop hipcc 7.2 waited for every element before it requested the next --
-        //  12 dependent round trips per tile of the 96-column class)
-        if (din == DIN) {
-            static_assert((16 * DIN / 2) % 64 == 0, "whole trips");
-            constexpr int NLD = 16 * DIN / 2 / 64, NB = NLD % 6 == 0 ? 6 : (NLD % 4 == 0 ? 4 : NLD);
-            const float *xt = x + (size_t)row0 * DIN;                        // wave-uniform base, 32-bit offsets
-            const int last = (int)min((int64_t)15, n - 1 - row0);
-#pragma unroll
-            for (int b0 = 0; b0 < NLD; b0 += NB) {
-                float2 v[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    const int i = lane + 64 * (b0 + u), r = i / (DIN / 2), c2 = i - r * (DIN / 2);
-                    v[u] = *reinterpret_cast<const float2 *>(xt + min(r, last) * DIN + 2 * c2);
-                }
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    const int i = lane + 64 * (b0 + u), r = i / (DIN / 2), c2 = i - r * (DIN / 2);
-                    *reinterpret_cast<float2 *>(xs + r * PX + 2 * c2) = v[u];
-                }
-            }
-        } else {   // a narrower layer in this class: column by column, zeros beyond din
-            const float *xn = x + (size_t)row0 * din;
-            const int lastn = (int)min((int64_t)15, n - 1 - row0);
-            static_assert((16 * DIN / 64) % 4 == 0, "whole batches");
-            for (int i0 = lane; i0 < 16 * DIN; i0 += 4 * 64) {      // unconditional loads (column clamped), four in flight
-                float v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const int i = i0 + 64 * u, r = i / DIN, c = i - r * DIN; v[u] = xn[min(r, lastn) * din + min(c, din - 1)]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const int i = i0 + 64 * u, r = i / DIN, c = i - r * DIN; xs[r * PX + c] = c < din ? v[u] : 0.0f; }
-            }
-        }
-        float a[DIN / 4 > DH / 4 ? DIN / 4 : DH / 4];
-#pragma unroll
-        for (int kk = 0; kk < DIN / 4; ++kk) a[kk] = xs[e * PX + 4 * kk + g];        // A operand: row e, k = 4 kk + g
-        // The weight operands of output tile t + 1 are read from LDS while the MFMAs of tile t run (two register sets, the scheduler held to that order):
-        // left to itself the compiler placed every ds_read directly in front of the two MFMAs that use it, with one register pair for all of them --
-        // a full LDS round trip (~110 cycles) per 64 cycles of matrix work, which is what "32 % of the fp32 matrix peak" was (round 3's figure).
-        f32x4m hid[NT1];
-        float wb[2][DIN / 4 > DH / 4 ? DIN / 4 : DH / 4];
-        {
-            const float *wr = W1s + e * P1 + g;                                    // B operand: output 16 t + e, k = 4 kk + g
-#pragma unroll
-            for (int kk = 0; kk < DIN / 4; ++kk) wb[0][kk] = wr[4 * kk];
-        }
-#pragma unroll
-        for (int t = 0; t < NT1; ++t) {
-            const float bias = B1s[16 * t + e];
-            f32x4m acc = {bias, bias, bias, bias};
-            if (t + 1 < NT1) {
-                const float *wr = W1s + (16 * (t + 1) + e) * P1 + g;
-#pragma unroll
-                for (int kk = 0; kk < DIN / 4; ++kk) wb[(t + 1) & 1][kk] = wr[4 * kk];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kk = 0; kk < DIN / 4; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], wb[t & 1][kk], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            hid[t] = acc;
-        }
-        // hidden = relu(...) over the rows' slots: lane (g, e) holds rows 4 g .. 4 g + 3 of output 16 t + e (LDS operations of a
-        // wave execute in program order: the A reads above are done)
-#pragma unroll
-        for (int t = 0; t < NT1; ++t)
-            if (16 * t + e < DH) {                 // the padding outputs of the last tile have no slot (and no reader)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { const float h = hid[t][i]; xs[(4 * g + i) * PX + 16 * t + e] = h > 0.0f ? h : (slope != 0.0f ? h * slope : 0.0f); }
-            }
-#pragma unroll
-        for (int kk = 0; kk < DH / 4; ++kk) a[kk] = xs[e * PX + 4 * kk + g];
-        {
-            const float *wr = W2s + e * P2 + g;
-#pragma unroll
-            for (int kk = 0; kk < DH / 4; ++kk) wb[0][kk] = wr[4 * kk];
-        }
-#pragma unroll
-        for (int t = 0; t < NT2; ++t) {
-            const float bias = B2s[16 * t + e];
-            f32x4m acc = {bias, bias, bias, bias};
-            if (t + 1 < NT2) {
-                const float *wr = W2s + (16 * (t + 1) + e) * P2 + g;
-#pragma unroll
-                for (int kk = 0; kk < DH / 4; ++kk) wb[(t + 1) & 1][kk] = wr[4 * kk];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kk = 0; kk < DH / 4; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], wb[t & 1][kk], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            const int c = 16 * t + e;
-            if (c < dout) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (row0 + 4 * g + i < n) y[(size_t)(row0 + 4 * g + i) * dout + c] = acc[i];
-            }
-        }
-    }
-}
-template <int DIN, int DH, int DOUT>
-static size_t mlpm_lds_bytes(int waves, int px)
-{
-    constexpr int NT1 = (DH + 15) / 16, NT2 = (DOUT + 15) / 16, P1 = DIN + 2, P2 = DH + 2;
-    return sizeof(float) * ((size_t)DH * P1 + (size_t)DOUT * P2 + NT1 * 16 + NT2 * 16 + (size_t)waves * 16 * px);
-}
-}  // namespace
-
-template <int DIN, int DH, int DOUT>
-static int mlp2_mfma_launch(gpcc_ctx *ctx, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, int64_t n, int din, int dh, int dout,
-                            float slope, float *y, hipStream_t st)
-{
-    static PerDeviceOnce attr;
-    // eight waves when they fit (if need be with the rows' LDS pitch without its two padding words: two-way conflicts on the 49 A-operand reads of a
-    // tile, nothing on the 443 B-operand reads), else four
-    constexpr int PXW = (DIN > DH ? DIN : DH);
-    constexpr size_t LDS_MAX = 160 * 1024;
-    int waves = 8, px = PXW + 2;
-    if (mlpm_lds_bytes<DIN, DH, DOUT>(8, px) > LDS_MAX) px = PXW;
-    if (mlpm_lds_bytes<DIN, DH, DOUT>(8, px) > LDS_MAX) { waves = 4; px = PXW + 2; }
-    const size_t lds = mlpm_lds_bytes<DIN, DH, DOUT>(waves, px);
-    GP_TRY(attr.run(ctx->device, [&]() -> int {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mlp2_mfma<DIN, DH, DOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        return GPCC_OK;
-    }));
-    const unsigned grid = (unsigned)std::min<int64_t>(256, cdiv(cdiv(n, 16), waves));
-    k_mlp2_mfma<DIN, DH, DOUT><<<grid, 64 * waves, lds, st>>>(x, w1, b1, w2, b2, n, din, dh, dout, slope, y, px);
-    LAUNCH_CHECK();
-    return GPCC_OK;
-}
-
-// act: 0 = ReLU, 1 = LeakyReLU(slope) between the two layers
-extern "C" int gshac_mlp2_act(gpcc_ctx *ctx, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, int64_t n, int din, int dh,
-                              int dout, int act, float slope, float *y, void *stream)
-{
-    if (!ctx || !x || !w1 || !b1 || !w2 || !b2 || !y) return fail(GPCC_ERR_ARG, "null argument");
-    if (act != 0 && act != 1) return fail(GPCC_ERR_ARG, "mlp2: activation must be 0 (ReLU) or 1 (LeakyReLU)");
-    if (n <= 0) return GPCC_OK;
-    if (din <= 0 || dh <= 0 || dout <= 0 || (size_t)MLP_ROWS * (size_t)(din + dh) * 4 > 64 * 1024) return fail(GPCC_ERR_ARG, "mlp2: unsupported layer sizes");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const float sl = act == 1 ? slope : 0.0f;
-    hipStream_t st = (hipStream_t)stream;
-    static const bool use_mfma = dev_env_int("GAUSPCC_MLP2_MFMA", 1) != 0;
-    if (use_mfma) {
-        // the smallest class that holds the layer (HAC's mlp_grid in its exact class)
-        if (din == 96 && dh == 100 && dout == 175) return mlp2_mfma_launch<96, 100, 175>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
-        if (din <= 192 && dh <= 40 && dout <= 32) return mlp2_mfma_launch<192, 40, 32>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
-        if (din <= 48 && dh <= 100 && dout <= 240) return mlp2_mfma_launch<48, 100, 240>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
-    }
-    k_mlp2<<<(unsigned)cdiv(n, MLP_ROWS), TB, (size_t)MLP_ROWS * (size_t)(din + dh) * 4, st>>>(x, w1, b1, w2, b2, n, din, dh, dout, sl, y);
-    LAUNCH_CHECK();
-    return GPCC_OK;
-}
-
-extern "C" int gshac_mlp2(gpcc_ctx *ctx, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, int64_t n, int din, int dh,
-                          int dout, float *y, void *stream)
-{
-    return gshac_mlp2_act(ctx, x, w1, b1, w2, b2, n, din, dh, dout, 0, 0.0f, y, stream);
-}
-
 
 // ------------------------------------------------------------------ fused Gaussian coder (no CDF table)
 namespace {
+// min / max over the block: the 64 lanes of every wave, then the waves; thread 0 hands the result to `done`
+template <class F> __device__ __forceinline__ void block_minmax(int mn, int mx, F done)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, __shfl_xor(mn, d, 64)); mx = max(mx, __shfl_xor(mx, d, 64)); }
+    __shared__ int red[TB / 64][2];
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = mn; red[threadIdx.x >> 6][1] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < TB / 64; ++w) { mn = min(mn, red[w][0]); mx = max(mx, red[w][1]); }
+        done(mn, mx);
+    }
+}
 // x_int = round(x / Q) (torch.round: half to even), its min / max over the slice (encodings_cuda.py:343-345)
 __global__ __launch_bounds__(TB) void k_quantise_minmax(const float *__restrict__ x, const float *__restrict__ q, int64_t n, int32_t *__restrict__ xi, int32_t *__restrict__ mm)
 {
@@ -1086,15 +542,7 @@ __global__ __launch_bounds__(TB) void k_quantise_minmax(const float *__restrict_
         xi[i] = v;
         mn = min(mn, v); mx = max(mx, v);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, __shfl_xor(mn, d, 64)); mx = max(mx, __shfl_xor(mx, d, 64)); }
-    __shared__ int red[TB / 64][2];
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = mn; red[threadIdx.x >> 6][1] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < TB / 64; ++w) { mn = min(mn, red[w][0]); mx = max(mx, red[w][1]); }
-        atomicMin(&mm[0], mn); atomicMax(&mm[1], mx);
-    }
+    block_minmax(mn, mx, [&](int mn, int mx) { atomicMin(&mm[0], mn); atomicMax(&mm[1], mx); });
 }
 __global__ __launch_bounds__(TB) void k_to_symbols(const int32_t *__restrict__ xi, int64_t n, int min_value, int16_t *__restrict__ sym)
 {
@@ -1109,34 +557,6 @@ __global__ __launch_bounds__(TB) void k_from_symbols(const int16_t *__restrict__
 }
 }  // namespace
 
-extern "C" int gsac_encode_gaussian(gpcc_ctx *ctx, const float *x, const float *mean, const float *scale, const float *Q, int64_t n, int chunk_size,
-                                    float *min_out, float *max_out, const uint8_t **bytes_out, int64_t *nbytes_out, const int32_t **cnt_out,
-                                    int64_t *nchunks_out, void *stream)
-{
-    if (!ctx || !x || !mean || !scale || !Q || !min_out || !max_out) return fail(GPCC_ERR_ARG, "null argument");
-    if (n <= 0 || chunk_size <= 0) return fail(GPCC_ERR_ARG, "bad size");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int nch = (int)cdiv(n, chunk_size);
-    const uint32_t sstride = rc_scratch_stride((uint32_t)std::min<int64_t>(chunk_size, n));
-    GP_TRY(ctx->arena.reserve((size_t)n * 8 + (size_t)nch * chunk_size * 4 + 2 * (size_t)nch * sstride + (size_t)nch * 64 + ((size_t)4 << 20)));
-    ctx->arena.reset();
-    TAKE(xi, int32_t, n); TAKE(sym, int16_t, n); TAKE(mm, int32_t, 2);
-    const int32_t init[2] = {INT32_MAX, INT32_MIN};
-    HIP_TRY(hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, st));
-    k_quantise_minmax<<<(unsigned)std::min<int64_t>(cdiv(n, TB), 512), TB, 0, st>>>(x, Q, n, xi, mm);
-    LAUNCH_CHECK();
-    int32_t hmm[2];
-    HIP_TRY(hipMemcpyAsync(hmm, mm, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int lp = hmm[1] - hmm[0] + 2;
-    if (lp > 32767) return fail(GPCC_ERR_RANGE, "quantised values span %d levels (int16 symbols)", lp - 1);
-    k_to_symbols<<<(unsigned)cdiv(n, TB), TB, 0, st>>>(xi, n, hmm[0], sym);
-    LAUNCH_CHECK();
-    *min_out = (float)hmm[0]; *max_out = (float)hmm[1];
-    return gsac_encode_impl<GaussTable>(ctx, sym, GaussTable{mean, scale, Q, hmm[0]}, chunk_size, n, lp, bytes_out, nbytes_out, cnt_out, nchunks_out, stream, true);
-}
-
 static int mix_table(const float *const *mean, const float *const *scale, const float *const *prob, int k, const float *Q, int min_value, MixTable *t)
 {
     if (!mean || !scale || !prob || !Q) return fail(GPCC_ERR_ARG, "null argument");
@@ -1150,15 +570,26 @@ static int mix_table(const float *const *mean, const float *const *scale, const 
     return GPCC_OK;
 }
 
-// HAC++'s encoder_gaussian_mixed without the (n, max - min + 2) table (HAC-plus/utils/encodings_cuda.py:205-247)
-extern "C" int gsac_encode_gaussian_mixed(gpcc_ctx *ctx, const float *x, const float *const *mean, const float *const *scale, const float *const *prob, int k,
-                                          const float *Q, int64_t n, int chunk_size, float *min_out, float *max_out, const uint8_t **bytes_out,
-                                          int64_t *nbytes_out, const int32_t **cnt_out, int64_t *nchunks_out, void *stream)
+// The symbol range [min, max] of a stream as its `.b` file stores it, two floats -> min and the row length max - min + 2.  The floats come off
+// disk: NaN, infinities, values that do not fit an int and alphabets that int16 symbols cannot index are format errors.
+static int symbol_range(float min_value, float max_value, int *mn, int *lp)
 {
-    if (!ctx || !x || !min_out || !max_out) return fail(GPCC_ERR_ARG, "null argument");
+    if (!(min_value >= -1.0e9f && min_value <= 1.0e9f) || !(max_value >= -1.0e9f && max_value <= 1.0e9f))
+        return fail(GPCC_ERR_FORMAT, "bad symbol range [%g, %g]", (double)min_value, (double)max_value);
+    const int64_t lp64 = (int64_t)(int)max_value - (int)min_value + 2;
+    if (lp64 < 2 || lp64 > 32767) return fail(GPCC_ERR_FORMAT, "bad symbol range [%d, %d]", (int)min_value, (int)max_value);
+    *mn = (int)min_value; *lp = (int)lp64;
+    return GPCC_OK;
+}
+
+// encoder_gaussian / HAC++'s encoder_gaussian_mixed without the (n, max - min + 2) table (encodings_cuda.py:336-371, HAC-plus/utils/
+// encodings_cuda.py:205-247): quantise, min / max, symbols, then the coder on the rows of `table` (GaussTable or MixTable; its min_value is set here)
+template <typename CT>
+static int encode_gaussian_impl(gpcc_ctx *ctx, const float *x, CT table, const float *Q, int64_t n, int chunk_size, float *min_out, float *max_out, CoderOut out,
+                                void *stream)
+{
+    if (!ctx || !x || !Q || !min_out || !max_out) return fail(GPCC_ERR_ARG, "null argument");
     if (n <= 0 || chunk_size <= 0) return fail(GPCC_ERR_ARG, "bad size");
-    MixTable t;
-    GP_TRY(mix_table(mean, scale, prob, k, Q, 0, &t));
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int nch = (int)cdiv(n, chunk_size);
@@ -1174,40 +605,68 @@ extern "C" int gsac_encode_gaussian_mixed(gpcc_ctx *ctx, const float *x, const f
     HIP_TRY(hipMemcpyAsync(hmm, mm, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int lp = hmm[1] - hmm[0] + 2;
-    // (the reference clamps the symbol to 32767, :227-228, and would then need a table of more than 32767 columns per element)
+    // (the reference clamps the symbol to 32767, HAC-plus :227-228, and would then need a table of more than 32767 columns per element)
     if (lp > 32767) return fail(GPCC_ERR_RANGE, "quantised values span %d levels (int16 symbols)", lp - 1);
     k_to_symbols<<<(unsigned)cdiv(n, TB), TB, 0, st>>>(xi, n, hmm[0], sym);
     LAUNCH_CHECK();
     *min_out = (float)hmm[0]; *max_out = (float)hmm[1];
-    t.min_value = hmm[0];
-    return gsac_encode_impl<MixTable>(ctx, sym, t, chunk_size, n, lp, bytes_out, nbytes_out, cnt_out, nchunks_out, stream, true);
+    table.min_value = hmm[0];
+    return gsac_encode_impl<CT>(ctx, sym, table, chunk_size, n, lp, out, stream, true);
 }
 
-// ... and decoder_gaussian_mixed (:271-317)
-extern "C" int gsac_decode_gaussian_mixed(gpcc_ctx *ctx, const float *const *mean, const float *const *scale, const float *const *prob, int k, const float *Q,
-                                          int64_t n, float min_value, float max_value, const uint8_t *bytes, int64_t nbytes, const int32_t *cnt, int chunk_size,
-                                          float *x_out, void *stream)
+// ... and decoder_gaussian / decoder_gaussian_mixed (encodings_cuda.py:399-433, HAC-plus :271-317)
+template <typename CT>
+static int decode_gaussian_impl(gpcc_ctx *ctx, CT table, const float *Q, int64_t n, float min_value, float max_value, const uint8_t *bytes, int64_t nbytes,
+                                const int32_t *cnt, int chunk_size, float *x_out, void *stream)
 {
-    if (!ctx || !x_out) return fail(GPCC_ERR_ARG, "null argument");
+    if (!ctx || !Q || !x_out) return fail(GPCC_ERR_ARG, "null argument");
     if (n <= 0 || chunk_size <= 0) return fail(GPCC_ERR_ARG, "bad size");
-    if (!(min_value >= -1.0e9f && min_value <= 1.0e9f) || !(max_value >= -1.0e9f && max_value <= 1.0e9f))
-        return fail(GPCC_ERR_FORMAT, "bad symbol range [%g, %g]", (double)min_value, (double)max_value);
-    const int mn = (int)min_value, mx = (int)max_value;
-    const int64_t lp64 = (int64_t)mx - mn + 2;
-    if (lp64 < 2 || lp64 > 32767) return fail(GPCC_ERR_FORMAT, "bad symbol range [%d, %d]", mn, mx);
-    MixTable t;
-    GP_TRY(mix_table(mean, scale, prob, k, Q, mn, &t));
+    int lp;
+    GP_TRY(symbol_range(min_value, max_value, &table.min_value, &lp));
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int nch = (int)cdiv(n, chunk_size);
     GP_TRY(ctx->arena.reserve((size_t)n * 2 + (size_t)nbytes + 8 * (size_t)nch + ((size_t)4 << 20)));
     ctx->arena.reset();
     TAKE(sym, int16_t, n);
-    GP_TRY(gsac_decode_impl<MixTable>(ctx, t, bytes, nbytes, cnt, chunk_size, n, (int)lp64, sym, stream, true));
+    GP_TRY(gsac_decode_impl<CT>(ctx, table, bytes, nbytes, cnt, chunk_size, n, lp, sym, stream, true));
     k_from_symbols<<<(unsigned)cdiv(n, TB), TB, 0, st>>>(sym, Q, n, min_value, x_out);
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(st));
     return GPCC_OK;
+}
+
+extern "C" int gsac_encode_gaussian(gpcc_ctx *ctx, const float *x, const float *mean, const float *scale, const float *Q, int64_t n, int chunk_size,
+                                    float *min_out, float *max_out, const uint8_t **bytes_out, int64_t *nbytes_out, const int32_t **cnt_out,
+                                    int64_t *nchunks_out, void *stream)
+{
+    if (!mean || !scale) return fail(GPCC_ERR_ARG, "null argument");
+    return encode_gaussian_impl(ctx, x, GaussTable{mean, scale, Q, 0}, Q, n, chunk_size, min_out, max_out, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
+}
+
+extern "C" int gsac_decode_gaussian(gpcc_ctx *ctx, const float *mean, const float *scale, const float *Q, int64_t n, float min_value, float max_value,
+                                    const uint8_t *bytes, int64_t nbytes, const int32_t *cnt, int chunk_size, float *x_out, void *stream)
+{
+    if (!mean || !scale) return fail(GPCC_ERR_ARG, "null argument");
+    return decode_gaussian_impl(ctx, GaussTable{mean, scale, Q, 0}, Q, n, min_value, max_value, bytes, nbytes, cnt, chunk_size, x_out, stream);
+}
+
+extern "C" int gsac_encode_gaussian_mixed(gpcc_ctx *ctx, const float *x, const float *const *mean, const float *const *scale, const float *const *prob, int k,
+                                          const float *Q, int64_t n, int chunk_size, float *min_out, float *max_out, const uint8_t **bytes_out,
+                                          int64_t *nbytes_out, const int32_t **cnt_out, int64_t *nchunks_out, void *stream)
+{
+    MixTable t;
+    GP_TRY(mix_table(mean, scale, prob, k, Q, 0, &t));
+    return encode_gaussian_impl(ctx, x, t, Q, n, chunk_size, min_out, max_out, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
+}
+
+extern "C" int gsac_decode_gaussian_mixed(gpcc_ctx *ctx, const float *const *mean, const float *const *scale, const float *const *prob, int k, const float *Q,
+                                          int64_t n, float min_value, float max_value, const uint8_t *bytes, int64_t nbytes, const int32_t *cnt, int chunk_size,
+                                          float *x_out, void *stream)
+{
+    MixTable t;
+    GP_TRY(mix_table(mean, scale, prob, k, Q, 0, &t));
+    return decode_gaussian_impl(ctx, t, Q, n, min_value, max_value, bytes, nbytes, cnt, chunk_size, x_out, stream);
 }
 
 // the mixture's CDF table itself: lower (n, max - min + 2), as HAC++ builds it before arithmetic_encode (:210-225)
@@ -1223,31 +682,6 @@ extern "C" int gsac_calculate_cdf_mixed(gpcc_ctx *ctx, const float *const *mean,
     k_mixture_cdf<<<(unsigned)cdiv(n * lp, TB), TB, 0, (hipStream_t)stream>>>(t, n, (int)lp, lower);
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return GPCC_OK;
-}
-
-extern "C" int gsac_decode_gaussian(gpcc_ctx *ctx, const float *mean, const float *scale, const float *Q, int64_t n, float min_value, float max_value,
-                                    const uint8_t *bytes, int64_t nbytes, const int32_t *cnt, int chunk_size, float *x_out, void *stream)
-{
-    if (!ctx || !mean || !scale || !Q || !x_out) return fail(GPCC_ERR_ARG, "null argument");
-    if (n <= 0 || chunk_size <= 0) return fail(GPCC_ERR_ARG, "bad size");
-    // min / max are floats read from a `.b` file: NaN, infinities and values that do not fit an int are format errors
-    if (!(min_value >= -1.0e9f && min_value <= 1.0e9f) || !(max_value >= -1.0e9f && max_value <= 1.0e9f))
-        return fail(GPCC_ERR_FORMAT, "bad symbol range [%g, %g]", (double)min_value, (double)max_value);
-    const int mn = (int)min_value, mx = (int)max_value;
-    const int64_t lp64 = (int64_t)mx - mn + 2;
-    if (lp64 < 2 || lp64 > 32767) return fail(GPCC_ERR_FORMAT, "bad symbol range [%d, %d]", mn, mx);
-    const int lp = (int)lp64;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int nch = (int)cdiv(n, chunk_size);
-    GP_TRY(ctx->arena.reserve((size_t)n * 2 + (size_t)nbytes + 8 * (size_t)nch + ((size_t)4 << 20)));
-    ctx->arena.reset();
-    TAKE(sym, int16_t, n);
-    GP_TRY(gsac_decode_impl<GaussTable>(ctx, GaussTable{mean, scale, Q, mn}, bytes, nbytes, cnt, chunk_size, n, lp, sym, stream, true));
-    k_from_symbols<<<(unsigned)cdiv(n, TB), TB, 0, st>>>(sym, Q, n, min_value, x_out);
-    LAUNCH_CHECK();
-    HIP_TRY(hipStreamSynchronize(st));
     return GPCC_OK;
 }
 
@@ -1275,15 +709,7 @@ __global__ __launch_bounds__(TB) void k_quantise_minmax_slices(const float *__re
         xi[i] = v;
         mn = min(mn, v); mx = max(mx, v);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, __shfl_xor(mn, d, 64)); mx = max(mx, __shfl_xor(mx, d, 64)); }
-    __shared__ int red[TB / 64][2];
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = mn; red[threadIdx.x >> 6][1] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < TB / 64; ++w) { mn = min(mn, red[w][0]); mx = max(mx, red[w][1]); }
-        if (hi > lo) { atomicMin(&mm[2 * s], mn); atomicMax(&mm[2 * s + 1], mx); }
-    }
+    block_minmax(mn, mx, [&](int mn, int mx) { if (hi > lo) { atomicMin(&mm[2 * s], mn); atomicMax(&mm[2 * s + 1], mx); } });
 }
 
 // (symbol, Gaussian parameters) -> the coder's two integers, in the chunk-interleaved layout of the element's slice
@@ -1310,11 +736,9 @@ __global__ __launch_bounds__(TB) void k_hac_pack_slices(CT table, const int32_t 
 
 template <typename CT>
 static int encode_slices_impl(gpcc_ctx *ctx, const float *x, CT table, const float *Q, const int64_t *slice_start,
-                              int nslices, int chunk_size, float *min_out, float *max_out, const uint8_t **bytes_out, int64_t *nbytes_out,
-                              const int32_t **cnt_out, int64_t *nchunks_out, void *stream)
+                              int nslices, int chunk_size, float *min_out, float *max_out, CoderOut out, void *stream)
 {
-    if (!ctx || !x || !Q || !slice_start || !min_out || !max_out || !bytes_out || !nbytes_out || !cnt_out || !nchunks_out)
-        return fail(GPCC_ERR_ARG, "null argument");
+    if (!ctx || !x || !Q || !slice_start || !min_out || !max_out || out.null()) return fail(GPCC_ERR_ARG, "null argument");
     if (nslices <= 0 || chunk_size <= 0) return fail(GPCC_ERR_ARG, "bad size");
     for (int s = 0; s < nslices; ++s)
         if (slice_start[s + 1] <= slice_start[s]) return fail(GPCC_ERR_ARG, "slice %d is empty", s);
@@ -1359,28 +783,7 @@ static int encode_slices_impl(gpcc_ctx *ctx, const float *x, CT table, const flo
     LAUNCH_CHECK();
     k_hac_pack_slices<CT><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(table, xi, n, dstart, nslices, mm, dlbase, dsnch, chunk_size, lohi);
     LAUNCH_CHECK();
-    GP_TRY(rc_encode_launch(st, lohi, dch, nch, scratch, sstride, dcnt));
-    GP_TRY(exclusive_scan_u32(ctx, st, dcnt, doff, nch, doff + nch));
-    GP_TRY(rc_compact_launch(st, scratch, sstride, dcnt, doff, nullptr, nch, payload));
-    GP_TRY(ctx->hstage.reserve(4 * (size_t)nch + 8 * (size_t)nslices + 64));
-    uint32_t *hcnt = reinterpret_cast<uint32_t *>(ctx->hstage.p);
-    int32_t *hmm = reinterpret_cast<int32_t *>(hcnt + nch + 1);
-    HIP_TRY(hipMemcpyAsync(hcnt, dcnt, 4 * (size_t)nch, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hcnt + nch, doff + nch, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hmm, mm, 8 * (size_t)nslices, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    GP_TRY(device_error_check(ctx));
-    for (int s = 0; s < nslices; ++s) {
-        if (hmm[2 * s + 1] - hmm[2 * s] + 2 > 32767) return fail(GPCC_ERR_RANGE, "slice %d: quantised values span %d levels (int16 symbols)", s, hmm[2 * s + 1] - hmm[2 * s] + 1);
-        min_out[s] = (float)hmm[2 * s]; max_out[s] = (float)hmm[2 * s + 1];
-    }
-    const size_t total = hcnt[nch];
-    GP_TRY(ctx->hbytes.reserve(total + 16));
-    if (total) HIP_TRY(hipMemcpyAsync(ctx->hbytes.p, payload, total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *bytes_out = ctx->hbytes.p; *nbytes_out = (int64_t)total;
-    *cnt_out = reinterpret_cast<const int32_t *>(hcnt); *nchunks_out = nch;
-    return GPCC_OK;
+    return encode_tail(ctx, st, lohi, dch, nch, scratch, sstride, dcnt, doff, payload, out, mm, nslices, min_out, max_out);
 }
 
 extern "C" int gsac_encode_gaussian_slices(gpcc_ctx *ctx, const float *x, const float *mean, const float *scale, const float *Q, const int64_t *slice_start,
@@ -1388,10 +791,8 @@ extern "C" int gsac_encode_gaussian_slices(gpcc_ctx *ctx, const float *x, const 
                                            const int32_t **cnt_out, int64_t *nchunks_out, void *stream)
 {
     if (!mean || !scale) return fail(GPCC_ERR_ARG, "null argument");
-    return encode_slices_impl(ctx, x, GaussTable{mean, scale, Q, 0}, Q, slice_start, nslices, chunk_size, min_out, max_out, bytes_out, nbytes_out, cnt_out, nchunks_out, stream);
+    return encode_slices_impl(ctx, x, GaussTable{mean, scale, Q, 0}, Q, slice_start, nslices, chunk_size, min_out, max_out, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
 }
-
-static int mix_table(const float *const *mean, const float *const *scale, const float *const *prob, int k, const float *Q, int min_value, MixTable *t);
 
 // HAC++: the slices of ONE channel group of `feat` under the two-component mixture (HAC-plus/scene/gaussian_model.py:1306-1321)
 extern "C" int gsac_encode_gaussian_mixed_slices(gpcc_ctx *ctx, const float *x, const float *const *mean, const float *const *scale, const float *const *prob, int k,
@@ -1400,7 +801,7 @@ extern "C" int gsac_encode_gaussian_mixed_slices(gpcc_ctx *ctx, const float *x, 
 {
     MixTable t;
     GP_TRY(mix_table(mean, scale, prob, k, Q, 0, &t));
-    return encode_slices_impl(ctx, x, t, Q, slice_start, nslices, chunk_size, min_out, max_out, bytes_out, nbytes_out, cnt_out, nchunks_out, stream);
+    return encode_slices_impl(ctx, x, t, Q, slice_start, nslices, chunk_size, min_out, max_out, CoderOut{bytes_out, nbytes_out, cnt_out, nchunks_out}, stream);
 }
 
 template <typename CT>
@@ -1418,13 +819,7 @@ static int decode_slices_impl(gpcc_ctx *ctx, CT table, const float *Q, const int
     for (int s = 0; s < nslices; ++s) {
         const int64_t len = slice_start[s + 1] - slice_start[s];
         if (len <= 0) return fail(GPCC_ERR_ARG, "slice %d is empty", s);
-        if (!(min_value[s] >= -1.0e9f && min_value[s] <= 1.0e9f) || !(max_value[s] >= -1.0e9f && max_value[s] <= 1.0e9f))
-            return fail(GPCC_ERR_FORMAT, "slice %d: bad symbol range", s);
-        const int mn = (int)min_value[s];
-        const int64_t lp64 = (int64_t)(int)max_value[s] - mn + 2;
-        if (lp64 < 2 || lp64 > 32767) return fail(GPCC_ERR_FORMAT, "slice %d: bad symbol range", s);
-        const int lp = (int)lp64;
-        smin[(size_t)s] = mn; slp[(size_t)s] = lp;
+        if (symbol_range(min_value[s], max_value[s], &smin[(size_t)s], &slp[(size_t)s]) != GPCC_OK) return fail(GPCC_ERR_FORMAT, "slice %d: bad symbol range", s);
         const int nch = (int)cdiv(len, chunk_size);
         for (int c = 0; c < nch; ++c) {
             const int32_t cb = cnt[chunks.size()];
@@ -1465,103 +860,4 @@ extern "C" int gsac_decode_gaussian_mixed_slices(gpcc_ctx *ctx, const float *con
     MixTable t;
     GP_TRY(mix_table(mean, scale, prob, k, Q, 0, &t));
     return decode_slices_impl(ctx, t, Q, slice_start, nslices, min_value, max_value, bytes, nbytes, cnt, chunk_size, x_out, stream);
-}
-
-extern "C" int gsge_forward(gpcc_ctx *ctx, const float *inputs, const float *embeddings, const int32_t *offsets, const int32_t *resolutions,
-                            float *outputs, int64_t N, int num_dim, int n_features, int n_levels, int Rb, const uint8_t *binary_vxl,
-                            const int32_t *min_level_id, void *stream)
-{
-    if (!ctx || !inputs || !embeddings || !offsets || !resolutions || !outputs) return fail(GPCC_ERR_ARG, "null argument");
-    if (N <= 0 || n_levels <= 0) return GPCC_OK;
-    if (N >= ((int64_t)1 << 31)) return fail(GPCC_ERR_ARG, "too many points");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((unsigned)cdiv(N, TB), (unsigned)n_levels);
-    switch (num_dim) {
-    case 1: return grid_launch_f<1>(st, n_features, g, inputs, embeddings, offsets, resolutions, outputs, (uint32_t)N, (uint32_t)Rb, binary_vxl, min_level_id);
-    case 2: return grid_launch_f<2>(st, n_features, g, inputs, embeddings, offsets, resolutions, outputs, (uint32_t)N, (uint32_t)Rb, binary_vxl, min_level_id);
-    case 3: return grid_launch_f<3>(st, n_features, g, inputs, embeddings, offsets, resolutions, outputs, (uint32_t)N, (uint32_t)Rb, binary_vxl, min_level_id);
-    default: return fail(GPCC_ERR_ARG, "GridEncoding: num_dim must be 1, 2 or 3");
-    }
-}
-
-// gsge_forward plus dy_dx (N, L, D, F) for the input gradient of _gridencoder's caller (NULL: outputs only).  outputs come from the same
-// k_grid_forward launch as gsge_forward's.
-extern "C" int gsge_forward_train(gpcc_ctx *ctx, const float *inputs, const float *embeddings, const int32_t *offsets, const int32_t *resolutions,
-                                  float *outputs, int64_t N, int num_dim, int n_features, int n_levels, int Rb, const uint8_t *binary_vxl,
-                                  const int32_t *min_level_id, float *dy_dx, void *stream)
-{
-    GP_TRY(gsge_forward(ctx, inputs, embeddings, offsets, resolutions, outputs, N, num_dim, n_features, n_levels, Rb, binary_vxl, min_level_id, stream));
-    if (!dy_dx || N <= 0 || n_levels <= 0) return GPCC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((unsigned)cdiv(N, TB), (unsigned)n_levels);
-    switch (num_dim) {
-    case 1: return grid_dydx_launch<1>(st, n_features, g, inputs, embeddings, offsets, resolutions, dy_dx, (uint32_t)N, min_level_id);
-    case 2: return grid_dydx_launch<2>(st, n_features, g, inputs, embeddings, offsets, resolutions, dy_dx, (uint32_t)N, min_level_id);
-    default: return grid_dydx_launch<3>(st, n_features, g, inputs, embeddings, offsets, resolutions, dy_dx, (uint32_t)N, min_level_id);
-    }
-}
-
-// _gridencoder.grid_encode_backward without float atomics (see k_grid_bwd_keys): adds into grad_embeddings (n_rows, F), overwrites grad_inputs
-// (N, D) when given.  Workspace (about 28 bytes per (point, level, corner)) through `alloc`; no synchronisation.
-extern "C" int gsge_backward(gpcc_ctx *ctx, const float *grad, const float *inputs, const float *embeddings, const int32_t *offsets, const int32_t *resolutions,
-                             int64_t n_rows, float *grad_embeddings, float *grad_inputs, int64_t N, int num_dim, int n_features, int n_levels, int Rb,
-                             const uint8_t *binary_vxl, const int32_t *min_level_id, gsr_alloc_fn alloc, void *alloc_user, void *stream)
-{
-    if (!ctx || !grad || !inputs || !embeddings || !offsets || !resolutions || !grad_embeddings || !alloc) return fail(GPCC_ERR_ARG, "null argument");
-    if (num_dim < 1 || num_dim > 3) return fail(GPCC_ERR_ARG, "GridEncoding: num_dim must be 1, 2 or 3");
-    if (n_features != 1 && n_features != 2 && n_features != 4 && n_features != 8) return fail(GPCC_ERR_ARG, "GridEncoding: n_features must be 1, 2, 4 or 8");
-    if (N <= 0 || n_levels <= 0) {
-        if (grad_inputs && N > 0) HIP_TRY(hipMemsetAsync(grad_inputs, 0, (size_t)N * num_dim * sizeof(float), (hipStream_t)stream));
-        return GPCC_OK;
-    }
-    if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31) - 1) return fail(GPCC_ERR_ARG, "bad embedding row count");
-    const int64_t E = (N * n_levels) << num_dim;
-    if (E >= ((int64_t)1 << 32)) return fail(GPCC_ERR_ARG, "too many (point, level, corner) slots for 32-bit slot ids");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int F = n_features;
-    const int64_t nchunks = cdiv(E, GB_CHUNK);
-    uint64_t *ka, *kb;
-    uint32_t *va, *vb, *hist;
-    float *wts, *head, *tail;
-    uint8_t *own;
-    GP_TRY(caller_block(alloc, alloc_user, "gsge_backward", [&](Carver &c) {
-        ka = c.take<uint64_t>(E); kb = c.take<uint64_t>(E); va = c.take<uint32_t>(E); vb = c.take<uint32_t>(E); wts = c.take<float>(E);
-        hist = c.take<uint32_t>(radix_sort_hist_words(E)); head = c.take<float>(nchunks * F); tail = c.take<float>(nchunks * F);
-        own = c.take<uint8_t>(nchunks);
-    }));
-    const uint32_t n = (uint32_t)N, L = (uint32_t)n_levels, nr = (uint32_t)n_rows;
-    dim3 g((unsigned)cdiv(N, TB), L);
-    switch (num_dim) {
-    case 1: k_grid_bwd_keys<1><<<g, TB, 0, st>>>(inputs, offsets, resolutions, n, (uint32_t)F, (uint32_t)Rb, binary_vxl, min_level_id, nr, ka, va, wts); break;
-    case 2: k_grid_bwd_keys<2><<<g, TB, 0, st>>>(inputs, offsets, resolutions, n, (uint32_t)F, (uint32_t)Rb, binary_vxl, min_level_id, nr, ka, va, wts); break;
-    default: k_grid_bwd_keys<3><<<g, TB, 0, st>>>(inputs, offsets, resolutions, n, (uint32_t)F, (uint32_t)Rb, binary_vxl, min_level_id, nr, ka, va, wts); break;
-    }
-    LAUNCH_CHECK();
-    int bits = 1;
-    while (((int64_t)1 << bits) <= n_rows) ++bits;    // the sentinel n_rows sorts last
-    uint64_t *k0 = ka, *k1 = kb;
-    uint32_t *v0 = va, *v1 = vb;
-    GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, E, bits, hist));
-    switch (F) {
-    case 1: grid_bwd_sum_launch<1>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
-    case 2: grid_bwd_sum_launch<2>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
-    case 4: grid_bwd_sum_launch<4>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
-    default: grid_bwd_sum_launch<8>(st, k0, v0, wts, grad, num_dim, n, L, E, nr, grad_embeddings, head, tail, own, nchunks); break;
-    }
-    LAUNCH_CHECK();
-    if (grad_inputs) {
-#define GB_IN(D, F) grid_bwd_inputs_launch<D, F>(st, inputs, embeddings, offsets, resolutions, grad, n, L, min_level_id, grad_inputs)
-#define GB_IN_F(D) switch (F) { case 1: GB_IN(D, 1); break; case 2: GB_IN(D, 2); break; case 4: GB_IN(D, 4); break; default: GB_IN(D, 8); break; }
-        switch (num_dim) {
-        case 1: GB_IN_F(1); break;
-        case 2: GB_IN_F(2); break;
-        default: GB_IN_F(3); break;
-        }
-#undef GB_IN_F
-#undef GB_IN
-        LAUNCH_CHECK();
-    }
-    return GPCC_OK;
 }

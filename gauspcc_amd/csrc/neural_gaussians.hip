@@ -207,7 +207,7 @@ __device__ __forceinline__ void ng_wave_sync()
 
 // The weight operands of output tile t + 1 are read from LDS while the MFMAs of tile t run -- two register sets and the scheduler held to that order
 // (__builtin_amdgcn_sched_barrier): left to itself the compiler re-read BOTH operands from LDS directly in front of every pair of MFMAs, one LDS round
-// trip per 64 cycles of matrix work (the same finding as in attributes.hip: k_mlp2_mfma).
+// trip per 64 cycles of matrix work (the same finding as in mlp2.hip: k_mlp2_mfma).
 template <int NK>
 __device__ __forceinline__ void ng_load_w(float (&w)[NK], const float *wr)
 {

@@ -1,5 +1,5 @@
 // sorted_sum.hpp -- the sum and combine passes of a backward that scatters without float atomics (the grid encoder's embedding gradient,
-// attributes.hip; the tri-plane's plane gradient, triplane.hip).  The caller has written one (row key, slot) entry per contribution and
+// gridencoder.hip; the tri-plane's plane gradient, triplane.hip).  The caller has written one (row key, slot) entry per contribution and
 // sorted the entries stably by key (primitives.hpp: radix_sort_u64), so every row's contributions are one run in ascending slot order:
 //   sum        one worker per chunk of CHUNK sorted entries sums each run it holds in order.  A run wholly inside the chunk goes straight
 //              to its row; a chunk's first run continued from the previous chunk leaves a head partial, a run that starts in it and

@@ -195,33 +195,43 @@ def decoder(N_len, file_name='tmp.b', device='cuda'):
 
 
 # ---------------------------------------------------------------- all slices of an attribute at once
+def _nonempty_slices(slice_start, device):
+    """(lens, keep, pick, cs): every slice's length, the indices of the non-empty slices, a function that takes their elements out of a flat tensor
+    (the tensor itself when no slice is empty) and their cumulative starts -- the slice_start of the device call, which takes no empty slice."""
+    ss = np.asarray(slice_start, dtype=np.int64)
+    lens = np.diff(ss)
+    keep = np.nonzero(lens > 0)[0]
+    sel = torch.cat([torch.arange(int(ss[i]), int(ss[i + 1]), device=device) for i in keep]) if 0 < keep.size != len(lens) else None
+    pick = (lambda t: t.reshape(-1).contiguous()) if sel is None else (lambda t: t.reshape(-1)[sel].contiguous())
+    return lens, keep, pick, np.concatenate([[0], np.cumsum(lens[keep])])
+
+
+def _slice_jobs(file_names, lens, mins, maxs, data, cnt):
+    """The `*_0.b` file of every slice from the concatenated output of a slices encoder: ([(path, blob)], [bits])."""
+    jobs, bits = [], []
+    c0 = b0 = 0
+    for fn, ln, mn, mx in zip(file_names, lens, mins, maxs):
+        c = cnt[c0:c0 + -(-int(ln) // chunk_size_cuda)]
+        nb = int(c.sum())
+        blob, nbits = _b_blob(mn, mx, c, data[b0:b0 + nb])
+        jobs.append((fn.replace('.b', '_0.b'), blob)); bits.append(nbits)
+        c0 += len(c); b0 += nb
+    return jobs, bits
+
+
 def encoder_gaussian_slices(x, mean, scale, Q, slice_start, file_names, chunk_size=1000_0000):
     """encoder_gaussian_chunk for MANY slices in one device call: slice s = elements [slice_start[s], slice_start[s+1]) goes
     to file_names[s] (a `*.b` name; as in encoder_gaussian_chunk the file written is `*_0.b`) with its own min / max.
     Same files as calling encoder_gaussian_chunk slice by slice.  Empty slices write nothing.  Returns the bit count per slice."""
-    ss = np.asarray(slice_start, dtype=np.int64)
-    lens = np.diff(ss)
+    lens, keep, pick, cs = _nonempty_slices(slice_start, x.device)
     assert lens.max(initial=0) <= chunk_size, "slices longer than chunk_size are split by encoder_gaussian_chunk; use it for those"
-    keep = np.nonzero(lens > 0)[0]
     bits = [0] * len(lens)
     if keep.size == 0:
         return bits
-    sel = torch.cat([torch.arange(int(ss[i]), int(ss[i + 1]), device=x.device) for i in keep]) if keep.size != len(lens) else None
-    pick = (lambda t: t.contiguous()) if sel is None else (lambda t: t[sel].contiguous())
-    cs = np.concatenate([[0], np.cumsum(lens[keep])])
     mins, maxs, data, cnt = arithmetic.encode_gaussian_slices(pick(x), pick(mean), pick(scale), pick(Q), cs, chunk_size_cuda)
-    nch = [-(-int(l) // chunk_size_cuda) for l in lens[keep]]
-    c0 = b0 = 0
-    jobs = []
-    for j, i in enumerate(keep):
-        c = cnt[c0:c0 + nch[j]]
-        nb = int(c.sum())
-        fn = file_names[i].replace('.b', '_0.b')
-        blob = b"".join((np.float32(mins[j]).tobytes(), np.float32(maxs[j]).tobytes(), np.array([4 * len(c)]).astype(np.int32).tobytes(),
-                         c.tobytes(), data[b0:b0 + nb].tobytes()))
-        jobs.append((fn, blob))
-        bits[i] = (nb + 4 * len(c)) * 8 + 32 * 3
-        c0 += nch[j]; b0 += nb
+    jobs, kept_bits = _slice_jobs([file_names[i] for i in keep], lens[keep], mins, maxs, data, cnt)
+    for i, b in zip(keep, kept_bits):
+        bits[i] = b
     _write_files(jobs)
     return bits
 
@@ -229,15 +239,10 @@ def encoder_gaussian_slices(x, mean, scale, Q, slice_start, file_names, chunk_si
 def decoder_gaussian_slices(mean, scale, Q, slice_start, file_names):
     """Inverse of encoder_gaussian_slices: reads the per-slice files, decodes every chunk of every slice concurrently.
     Returns the decoded values of all (non-empty) slices concatenated in slice order."""
-    ss = np.asarray(slice_start, dtype=np.int64)
-    lens = np.diff(ss)
-    keep = np.nonzero(lens > 0)[0]
+    lens, keep, pick, cs = _nonempty_slices(slice_start, mean.device)
     if keep.size == 0:
         return torch.empty(0, dtype=torch.float32, device=mean.device)
     mins, maxs, cnts, datas = _read_slice_files([file_names[i].replace('.b', '_0.b') for i in keep], lens[keep])
-    sel = torch.cat([torch.arange(int(ss[i]), int(ss[i + 1]), device=mean.device) for i in keep]) if keep.size != len(lens) else None
-    pick = (lambda t: t.contiguous()) if sel is None else (lambda t: t[sel].contiguous())
-    cs = np.concatenate([[0], np.cumsum(lens[keep])])
     return arithmetic.decode_gaussian_slices(pick(mean), pick(scale), pick(Q), cs, np.array(mins), np.array(maxs), np.concatenate(datas),
                                              np.concatenate(cnts), chunk_size_cuda)
 
@@ -250,16 +255,12 @@ def decoder_gaussian_slices_multi(jobs):
     dev = jobs[0][0].device
     parts, paths, lens_all, sizes = [], [], [], []
     for mean, scale, Q, slice_start, file_names in jobs:
-        ss = np.asarray(slice_start, dtype=np.int64)
-        lens = np.diff(ss)
-        keep = np.nonzero(lens > 0)[0]
+        lens, keep, pick, cs = _nonempty_slices(slice_start, dev)
         paths += [file_names[i].replace('.b', '_0.b') for i in keep]
-        sel = torch.cat([torch.arange(int(ss[i]), int(ss[i + 1]), device=dev) for i in keep]) if (keep.size != len(lens) and keep.size) else None
-        pick = (lambda t: t.reshape(-1)) if sel is None else (lambda t, sel=sel: t.reshape(-1)[sel])
         if keep.size:
             parts.append((pick(mean), pick(scale), pick(Q)))
             lens_all.append(lens[keep])
-        sizes.append(int(lens[keep].sum()) if keep.size else 0)
+        sizes.append(int(cs[-1]))
     if not parts:
         return [torch.empty(0, dtype=torch.float32, device=dev) for _ in jobs]
     mins, maxs, cnts, datas = _read_slice_files(paths, np.concatenate(lens_all))          # every job's files in one call (the blob is per thread and per call)
@@ -280,17 +281,7 @@ def encoder_gaussian_mixed_slices(x, mean_list, scale_list, prob_list, Q, slice_
     cont = lambda lst: [t.contiguous() for t in lst]
     mins, maxs, data, cnt = arithmetic.encode_gaussian_mixed_slices(x.contiguous(), cont(mean_list), cont(scale_list), cont(prob_list), Q.contiguous(), ss - ss[0],
                                                                     chunk_size_cuda)
-    bits, jobs = [], []
-    c0 = b0 = 0
-    for i, ln in enumerate(lens):
-        nch = -(-int(ln) // chunk_size_cuda)
-        c = cnt[c0:c0 + nch]
-        nb = int(c.sum())
-        blob = b"".join((np.float32(mins[i]).tobytes(), np.float32(maxs[i]).tobytes(), np.array([4 * len(c)]).astype(np.int32).tobytes(),
-                         c.tobytes(), data[b0:b0 + nb].tobytes()))
-        jobs.append((file_names[i].replace('.b', '_0.b'), blob))
-        bits.append((nb + 4 * len(c)) * 8 + 32 * 3)
-        c0 += nch; b0 += nb
+    jobs, bits = _slice_jobs(file_names, lens, mins, maxs, data, cnt)
     _write_files(jobs)
     return bits
 
@@ -306,17 +297,18 @@ def decoder_gaussian_mixed_slices(mean_list, scale_list, prob_list, Q, slice_sta
 
 
 # ---------------------------------------------------------------- `.b` container shared by the Gaussian-family coders
+def _b_blob(min_value, max_value, cnt, payload):
+    """f32 min | f32 max | i32 len(cnt bytes) | cnt | payload  (HAC/utils/encodings_cuda.py:366-376) from numpy cnt / payload: (blob, bit count)"""
+    cnt_bytes, payload_bytes = cnt.tobytes(), payload.tobytes()
+    blob = b"".join((np.float32(min_value).tobytes(), np.float32(max_value).tobytes(), np.array([len(cnt_bytes)]).astype(np.int32).tobytes(),
+                     cnt_bytes, payload_bytes))
+    return blob, (len(payload_bytes) + len(cnt_bytes)) * 8 + 32 * 3
+
+
 def _write_b(file_name, min_value, max_value, byte_stream_torch, cnt_torch):
-    """f32 min | f32 max | i32 len(cnt bytes) | cnt | payload  (HAC/utils/encodings_cuda.py:366-376); returns the bit count"""
-    cnt_bytes = cnt_torch.cpu().numpy().tobytes()
-    byte_stream_bytes = byte_stream_torch.cpu().numpy().tobytes()
-    with open(file_name, 'wb') as fout:
-        fout.write(np.float32(min_value).tobytes())
-        fout.write(np.float32(max_value).tobytes())
-        fout.write(np.array([len(cnt_bytes)]).astype(np.int32).tobytes())
-        fout.write(cnt_bytes)
-        fout.write(byte_stream_bytes)
-    return (len(byte_stream_bytes) + len(cnt_bytes)) * 8 + 32 * 3
+    blob, bits = _b_blob(min_value, max_value, cnt_torch.cpu().numpy(), byte_stream_torch.cpu().numpy())
+    _write_one((file_name, blob))
+    return bits
 
 
 def _read_b(file_name):

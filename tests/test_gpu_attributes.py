@@ -287,6 +287,87 @@ def test_mixture_coder_matches_table_path_and_oracle_files(torch_cuda, orc, tmp_
     assert (tmp_path / "k1.b").read_bytes() == (tmp_path / "g.b").read_bytes()
 
 
+def _two_component_mixture(torch, n, seed, spread=None):
+    """Parameters and samples as in test_mixture_coder_matches_table_path_and_oracle_files; spread: a per-element factor on the noise."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    mean = [(torch.randn(n, generator=g) * 2).cuda(), (torch.randn(n, generator=g) * 2).cuda()]
+    scale = [(torch.rand(n, generator=g) * 3 + 0.05).cuda(), (torch.rand(n, generator=g) * 0.5 + 1e-3).cuda()]
+    w = torch.softmax(torch.randn(n, 2, generator=g), dim=-1).cuda()
+    prob = [w[:, 0].contiguous(), w[:, 1].contiguous()]
+    q = (torch.rand(n, generator=g) * 0.5 + 0.75).cuda()
+    pick = (torch.rand(n, generator=g) < w[:, 0].cpu()).cuda()
+    spread = torch.ones(n).cuda() if spread is None else spread
+    x = torch.where(pick, mean[0] + torch.randn(n, generator=g).cuda() * scale[0] * spread, mean[1] + torch.randn(n, generator=g).cuda() * scale[1] * spread)
+    return x.contiguous(), mean, scale, prob, q
+
+
+def test_mixture_slices_write_the_per_slice_files(torch_cuda, tmp_path):
+    """encoder_gaussian_mixed_slices (every slice of a HAC++ channel group in one device call) writes the files encoder_gaussian_mixed_chunk
+    writes slice by slice, and decoder_gaussian_mixed_slices reads them back: a slice of two chunks whose second holds one symbol, a slice of
+    one element (min == max: the two-entry row, the smallest table) and a ragged two-chunk slice, each with its own min / max.  With one
+    component of weight 1 the files are encoder_gaussian_slices' files."""
+    torch = torch_cuda
+    from gauspcc_amd import encodings_cuda as ec
+
+    bounds = [0, 10001, 10002, 25000]
+    n, ns = bounds[-1], len(bounds) - 1
+    x, mean, scale, prob, q = _two_component_mixture(torch, n, 35, spread=1 + torch.arange(n).cuda() / n * 3)    # ranges differ per slice
+    names = lambda tag: [str(tmp_path / f"{tag}_{s}.b") for s in range(ns)]
+    file_of = lambda name: open(name.replace(".b", "_0.b"), "rb").read()
+    a, b = names("a"), names("b")
+    bits = ec.encoder_gaussian_mixed_slices(x, mean, scale, prob, q, bounds, a)
+    for s in range(ns):
+        sl = slice(bounds[s], bounds[s + 1])
+        ref_bits = ec.encoder_gaussian_mixed_chunk(x[sl], [t[sl] for t in mean], [t[sl] for t in scale], [t[sl] for t in prob], q[sl], file_name=b[s])
+        assert bits[s] == ref_bits
+        assert file_of(a[s]) == file_of(b[s])
+    assert len({file_of(f)[:8] for f in b}) == ns                             # every slice has its own (min, max)
+    assert file_of(b[1])[0:4] == file_of(b[1])[4:8]                           # the one-element slice: min == max
+    dec = ec.decoder_gaussian_mixed_slices(mean, scale, prob, q, bounds, b)   # reads the files of the slice-by-slice encoder
+    assert torch.equal(dec, torch.round(x / q) * q)
+    # K = 1, weight 1: the single-Gaussian slices coder
+    c, d = names("c"), names("d")
+    ec.encoder_gaussian_mixed_slices(x, mean[:1], scale[:1], [torch.ones(n, device="cuda")], q, bounds, c)
+    ec.encoder_gaussian_slices(x, mean[0], scale[0], q, bounds, d)
+    for s in range(ns):
+        assert file_of(c[s]) == file_of(d[s])
+
+
+@pytest.mark.parametrize("mixed", [False, True], ids=["plain", "mixture"])
+@pytest.mark.parametrize("slices", [False, True], ids=["stream", "slices"])
+def test_gaussian_decoders_reject_bad_headers(torch_cuda, mixed, slices):
+    """The (min, max) floats and the chunk byte counts of a `.b` file come off disk.  Each of the four table-free decoders refuses a header
+    that is not a symbol range -- NaN, infinity, max < min, more levels than int16 symbols index, a value that fits no int -- and a chunk
+    table whose counts add up to more than the payload, with GPCC_ERR_FORMAT; all on the host, before any kernel runs.  The context is usable
+    afterwards: the valid stream decodes exactly."""
+    torch = torch_cuda
+    from gauspcc_amd import _lib, arithmetic
+
+    fmt = -5                                                   # GPCC_ERR_FORMAT (include/gauspcc.h)
+    n, chunk, bounds = 2500, 1000, [0, 1200, 2500]
+    x, mean, scale, prob, q = _two_component_mixture(torch, n, 36)
+    params = (mean, scale, prob, q) if mixed else (mean[0], scale[0], q)
+    if slices:
+        enc = arithmetic.encode_gaussian_mixed_slices if mixed else arithmetic.encode_gaussian_slices
+        dec = arithmetic.decode_gaussian_mixed_slices if mixed else arithmetic.decode_gaussian_slices
+        mins, maxs, data, cnt = enc(x, *params, bounds, chunk)
+        decode = lambda mn, mx, c=cnt: dec(*params, bounds, np.array([mins[0], mn], np.float32), np.array([maxs[0], mx], np.float32), data, c, chunk)
+        mn, mx = float(mins[1]), float(maxs[1])                # the second slice's header is the one corrupted
+        over = cnt.copy()
+    else:
+        enc = arithmetic.encode_gaussian_mixed if mixed else arithmetic.encode_gaussian
+        dec = arithmetic.decode_gaussian_mixed if mixed else arithmetic.decode_gaussian
+        mn, mx, data, cnt = enc(x, *params, chunk)
+        decode = lambda mn, mx, c=cnt: dec(*params, mn, mx, data, c, chunk)
+        over = cnt.clone()
+    over[-1] += len(data) + 1                                  # the right number of counts, more bytes than the payload has
+    for bad in ((float("nan"), mx), (mn, float("inf")), (5.0, 3.0), (0.0, 40000.0), (-2e9, mx), (mn, mx, over)):
+        with pytest.raises(_lib.GpccError) as e:
+            decode(*bad)
+        assert e.value.code == fmt, (bad[:2], str(e.value))
+    assert torch.equal(decode(mn, mx), torch.round(x / q) * q)
+
+
 def test_factorized_coder_roundtrip_and_table(torch_cuda, orc, tmp_path):
     """encoder_factorized / decoder_factorized (HAC/utils/encodings_cuda.py:38-175): a per-channel learned density given as
     `lower_func` (the entropy bottleneck's cumulative logits).  The payload equals the oracle coder's on the same table, the

@@ -25,7 +25,9 @@ for spec in "$@"; do
   ) &
 done
 wait
+objs=" $(make -s --no-print-directory objs) "      # the library's objects as the Makefile lists them, with this variant's tiles and network
 for name in "${names[@]}"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../variants/libgauspcc_$name.so primitives.o octree.o ../variants/tiles_$name.o ../variants/network_$name.o network_any.o rangecoder.o hostcoder.o codec.o forest.o codec_batch.o fused.o api.o attributes.o rasterizer.o neural_gaussians.o
+  vobjs=${objs/ tiles.o / ../variants/tiles_$name.o }
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../variants/libgauspcc_$name.so ${vobjs/ network.o / ../variants/network_$name.o }
 done
 ls -la ../variants/*.so
