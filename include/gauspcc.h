@@ -643,6 +643,20 @@ GPCC_API int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const flo
                                  const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
                                  float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
+/* Backward of gshac_mlp2_act (the training forward IS gshac_mlp2_act: nothing is saved).  Recomputes h = b1 + x W1^T with the forward's chain, so
+ * the activation mask is the forward's bit for bit (act' = 0 / slope at h <= 0, as torch), then g = (dy W2) o act'(h), dx = g W1, dW2 = dy^T act(h),
+ * db2 = sum dy, dW1 = g^T x, db1 = sum g.  dy (n, dout); OVERWRITES dw1 (dh, din), db1 (dh), dw2 (dout, dh), db2 (dout) and, when it is not NULL,
+ * dx (n, din): a NULL dx skips that product and leaves the bits of the others unchanged.  The rows are cut into slabs of gshac_mlp2_slab_rows rows
+ * (a function of n and the sizes alone); every slab writes one partial of the parameter gradients into the workspace (slabs x (parameters + dh
+ * + dout) floats, through alloc) and a second launch adds them in slab order; the bias gradients, and the sum over the slabs, are compensated
+ * sums in that fixed order: no atomics, bitwise reproducible.  n == 0 zeroes the parameter gradients.  All
+ * pointers device; no host synchronisation.  The layer sizes are the forward's (16 (din + dh) floats <= 64 KB). */
+GPCC_API int gshac_mlp2_backward(gpcc_ctx *ctx, const float *x_dev, const float *w1_dev, const float *b1_dev, const float *w2_dev, const float *b2_dev,
+                                 int64_t n, int din, int dh, int dout, int act, float slope, const float *dy_dev, float *dx_dev, float *dw1_dev,
+                                 float *db1_dev, float *dw2_dev, float *db2_dev, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+/* rows per slab of gshac_mlp2_backward for n rows of this layer (0 for sizes it does not take) */
+GPCC_API int64_t gshac_mlp2_slab_rows(int64_t n, int din, int dh, int dout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,388 @@
+"""gauspcc_amd.mlp on the device: the forward is the codec's MLP bit for bit, the gradients against the float64 restatement tests/mlp_ref.py.
+
+Accuracy criterion (that of tests/test_gpu_triplane.py, no tolerance fixed in advance): for each of dx, dW1, db1, dW2, db2,
+e_dev = max |device - float64| must not exceed 4 x e_t32 = max |float32 nn.Sequential on the same GPU - float64|.  The factor covers two
+equally valid float32 summation orders compared by a maximum over the elements.  Rows with a hidden unit at |h| < 1e-4 are left out
+beforehand (mlp_ref.fixture), so the activation masks of float32 and float64 agree."""
+import functools
+import os
+import sys
+import types
+
+import pytest
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mlp_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+FACTOR = 4.0
+NAMES = ("dx", "dW1", "db1", "dW2", "db2")
+IDS = ["%d-%d-%d-%s" % s for s in ref.SHAPES]
+
+
+def _torch_module(din, dh, dout, act, w, dtype=torch.float32, device=DEV):
+    m = nn.Sequential(nn.Linear(din, dh), nn.ReLU() if act == "relu" else nn.LeakyReLU(ref.SLOPE), nn.Linear(dh, dout)).to(device=device, dtype=dtype)
+    with torch.no_grad():
+        for p, v in zip((m[0].weight, m[0].bias, m[2].weight, m[2].bias), w):
+            p.copy_(v)
+    return m
+
+
+def _ours(din, dh, dout, act, w):
+    from gauspcc_amd.mlp import ContextMLP
+
+    m = ContextMLP(din, dh, dout, act, ref.SLOPE).to(DEV)
+    with torch.no_grad():
+        for p, v in zip((m[0].weight, m[0].bias, m[2].weight, m[2].bias), w):
+            p.copy_(v)
+    return m
+
+
+def _grads(mod, x, dy, with_dx=True):
+    """(y, [dx, dW1, db1, dW2, db2]) of module `mod` on the device"""
+    x = x.to(DEV).requires_grad_(with_dx)
+    y = mod(x)
+    ps = [mod[0].weight, mod[0].bias, mod[2].weight, mod[2].bias]
+    g = torch.autograd.grad(y, ([x] if with_dx else []) + ps, dy.to(DEV))
+    return y.detach(), ([] if with_dx else [None]) + list(g)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(si, n):
+    """Inputs, the float64 reference (computed once, on the CPU) and the float32 nn.Sequential's gradients on the GPU."""
+    din, dh, dout, act = ref.SHAPES[si]
+    x, dy, w, _ = ref.fixture(din, dh, dout, n, seed=10 * si)
+    g64 = ref.closed_form_grads(x.double(), *(t.double() for t in w), dy.double(), act)
+    _, g32 = _grads(_torch_module(din, dh, dout, act, w), x, dy)
+    return dict(x=x, dy=dy, w=w, g64=g64, g32=[g.cpu() for g in g32])
+
+
+def _criterion(tag, dev, t32, want):
+    e_dev, e_t32 = float((dev.double().cpu() - want).abs().max()), float((t32.double().cpu() - want).abs().max())
+    print(f"{tag}: e_dev {e_dev:.3e}  e_t32 {e_t32:.3e}  ratio {e_dev / e_t32 if e_t32 else float('inf') if e_dev else 0.0:.2f}")
+    return e_dev <= FACTOR * e_t32, (tag, e_dev, e_t32)
+
+
+def _slab(si):
+    from gauspcc_amd.mlp import slab_rows
+
+    din, dh, dout, _ = ref.SHAPES[si]
+    return slab_rows(1, din, dh, dout)
+
+
+@pytest.mark.parametrize("si", range(len(ref.SHAPES)), ids=IDS)
+def test_forward_is_the_codecs_mlp_bit_for_bit(si):
+    from gauspcc_amd import hac_codec, hac_plus_codec
+
+    din, dh, dout, act = ref.SHAPES[si]
+    d = _case(si, 3 * _slab(si) + 5)
+    m = _ours(din, dh, dout, act, d["w"])
+    x = d["x"].to(DEV)
+    y = m(x)
+    ps = (m[0].weight, m[0].bias, m[2].weight, m[2].bias)
+    want = hac_codec.mlp2(x, *ps) if act == "relu" else hac_plus_codec.mlp2_act(x, *ps, ref.SLOPE)
+    assert y.requires_grad and torch.equal(y.detach(), want)
+    with torch.no_grad():
+        assert torch.equal(m(x), want)
+
+
+@pytest.mark.parametrize("si", range(len(ref.SHAPES)), ids=IDS)
+def test_gradients_match_float64_restatement(si):
+    din, dh, dout, act = ref.SHAPES[si]
+    bad = []
+    for n in ref.row_counts(_slab(si)):
+        d = _case(si, n)
+        _, g = _grads(_ours(din, dh, dout, act, d["w"]), d["x"], d["dy"])
+        for name, dev, t32, want in zip(NAMES, g, d["g32"], d["g64"]):
+            assert dev.shape == want.shape
+            ok, info = _criterion(f"n {n} {name}", dev, t32, want)
+            if not ok:
+                bad.append(info)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("si", [0, 3, 6], ids=[IDS[0], IDS[3], IDS[6]])
+def test_backward_is_bitwise_reproducible_also_on_a_side_stream(si):
+    din, dh, dout, act = ref.SHAPES[si]
+    d = _case(si, 3 * _slab(si) + 5)
+    m = _ours(din, dh, dout, act, d["w"])
+    _, g0 = _grads(m, d["x"], d["dy"])
+    for _ in range(2):
+        _, g = _grads(m, d["x"], d["dy"])
+        assert all(torch.equal(a, b) for a, b in zip(g, g0))
+    s = torch.cuda.Stream(DEV)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        _, g = _grads(m, d["x"], d["dy"])
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(g, g0))
+
+
+@pytest.mark.parametrize("si", [0, 4, 6], ids=[IDS[0], IDS[4], IDS[6]])
+def test_parameter_gradients_do_not_depend_on_dx(si):
+    din, dh, dout, act = ref.SHAPES[si]
+    d = _case(si, 3 * _slab(si) + 5)
+    m = _ours(din, dh, dout, act, d["w"])
+    _, g = _grads(m, d["x"], d["dy"])
+    _, h = _grads(m, d["x"], d["dy"], with_dx=False)
+    assert all(torch.equal(a, b) for a, b in zip(g[1:], h[1:]))
+
+
+@pytest.mark.parametrize("act", ["relu", "leaky_relu"])
+def test_kink_follows_torch(act):
+    """a hidden unit with zero weights and bias: h = 0 exactly; act' there is 0 (ReLU) / slope (LeakyReLU)"""
+    din, dh, dout, n, unit = 48, 100, 195, 300, 37
+    x, dy, w, _ = ref.fixture(din, dh, dout, n, seed=77)
+    w[0][unit] = 0
+    w[1][unit] = 0
+    _, g = _grads(_ours(din, dh, dout, act, w), x, dy)
+    _, t = _grads(_torch_module(din, dh, dout, act, w), x, dy)
+    if act == "relu":
+        assert not g[1][unit].any() and g[2][unit] == 0
+        assert not t[1][unit].any() and t[2][unit] == 0
+    else:
+        w64 = [v.double() for v in w]
+        want = ref.closed_form_grads(x.double(), *w64, dy.double(), act)
+        assert want[1][unit].abs().max() > 0
+        for name, i in (("dW1 row", 1), ("db1", 2)):
+            ok, info = _criterion(f"kink {name}", g[i][unit], t[i][unit], want[i][unit])
+            assert ok, info
+
+
+def test_edges():
+    from gauspcc_amd import _lib, runtime
+    from gauspcc_amd._lib import GpccError
+    from gauspcc_amd.mlp import ContextMLP, mlp2
+
+    din, dh, dout, act = ref.SHAPES[0]
+    d = _case(0, 3 * _slab(0) + 5)
+    m = _ours(din, dh, dout, act, d["w"])
+    # n = 0: empty output, zero parameter gradients
+    y = m(torch.empty(0, din, device=DEV))
+    assert y.shape == (0, dout)
+    gs = torch.autograd.grad(y.sum(), list(m.parameters()))
+    assert all(g.shape == p.shape and not g.any() for g, p in zip(gs, m.parameters()))
+    # strided and 3-D input: the contiguous 2-D call's bits
+    n = d["x"].shape[0] // 4 * 4
+    x2 = d["x"][:n].to(DEV)
+    y2, g2 = _grads(m, d["x"][:n], d["dy"][:n])
+    wide = torch.zeros(n, 2 * din, device=DEV)
+    wide[:, ::2] = x2
+    xs = wide[:, ::2].view(4, n // 4, din).requires_grad_(True)
+    assert not xs.is_contiguous()
+    ys = m(xs)
+    assert ys.shape == (4, n // 4, dout) and torch.equal(ys.detach().reshape(n, dout), y2)
+    gx, *gp = torch.autograd.grad(ys, [xs] + list(m.parameters()), d["dy"][:n].to(DEV).view(4, n // 4, dout))
+    assert torch.equal(gx.reshape(n, din), g2[0]) and all(torch.equal(a, b) for a, b in zip(gp, g2[1:]))
+    # float64 and CPU input: the torch path
+    m64 = ContextMLP(din, dh, dout).to(DEV).double()
+    x64 = x2[:9].double()
+    assert torch.equal(m64(x64), nn.Sequential.forward(m64, x64)) and m64(x64).dtype == torch.float64
+    mc = ContextMLP(10, 30, 30, "leaky_relu")
+    xc = torch.randn(5, 10)
+    assert torch.equal(mc(xc), nn.Sequential.forward(mc, xc))
+    # bad arguments
+    L, ctx = _lib.lib(), runtime.context(DEV)
+    p = [t.data_ptr() for t in (x2, m[0].weight, m[0].bias, m[2].weight, m[2].bias)]
+    out = torch.empty(n, dout, device=DEV)
+    ws = runtime.Workspace(DEV)
+    grads = [torch.empty_like(t) for t in m.parameters()]
+    gp = [g.data_ptr() for g in grads]
+    with pytest.raises(GpccError):      # activation code
+        _lib.check(L.gshac_mlp2_backward(ctx, *p, n, din, dh, dout, 2, 0.0, out.data_ptr(), None, *gp, ws.fn(), None, runtime.stream_ptr(DEV)))
+    with pytest.raises(GpccError):      # a size the forward does not take
+        _lib.check(L.gshac_mlp2_backward(ctx, *p, n, 3000, 2000, dout, 0, 0.0, out.data_ptr(), None, *gp, ws.fn(), None, runtime.stream_ptr(DEV)))
+    with pytest.raises(GpccError):      # no gradient buffer
+        _lib.check(L.gshac_mlp2_backward(ctx, *p, n, din, dh, dout, 0, 0.0, out.data_ptr(), None, None, *gp[1:], ws.fn(), None, runtime.stream_ptr(DEV)))
+    with pytest.raises(GpccError):      # negative n
+        _lib.check(L.gshac_mlp2_backward(ctx, *p, -1, din, dh, dout, 0, 0.0, out.data_ptr(), None, *gp, ws.fn(), None, runtime.stream_ptr(DEV)))
+    with pytest.raises(ValueError):
+        mlp2(x2, m[0].weight, m[0].bias, m[2].weight, m[2].bias, act="gelu")
+    with pytest.raises(ValueError):
+        mlp2(x2[:, :5], m[0].weight, m[0].bias, m[2].weight, m[2].bias)
+
+
+def test_from_sequential_shares_storage_and_state_dicts_load_both_ways():
+    from gauspcc_amd import hac_codec
+    from gauspcc_amd.mlp import ContextMLP
+
+    torch.manual_seed(1)
+    seq = nn.Sequential(nn.Linear(96, 100), nn.ReLU(True), nn.Linear(100, 175)).to(DEV)
+    m = ContextMLP.from_sequential(seq)
+    assert list(m.state_dict()) == ["0.weight", "0.bias", "2.weight", "2.bias"] == list(seq.state_dict())
+    assert all(a is b for a, b in zip(m.parameters(), seq.parameters()))
+    assert [type(c) for c in m] == [nn.Linear, nn.ReLU, nn.Linear]
+    opt = torch.optim.SGD(seq.parameters(), lr=0.1)
+    x = torch.randn(50, 96, device=DEV)
+    before = seq[0].weight.detach().clone()
+    m(x).square().mean().backward()
+    opt.step()
+    assert not torch.equal(seq[0].weight, before)
+    other = ContextMLP(96, 100, 175).to(DEV)
+    other.load_state_dict(seq.state_dict())
+    seq2 = nn.Sequential(nn.Linear(96, 100), nn.ReLU(True), nn.Linear(100, 175)).to(DEV)
+    seq2.load_state_dict(other.state_dict())
+    assert torch.equal(seq2[2].weight, seq[2].weight)
+    leaky = ContextMLP.from_sequential(nn.Sequential(nn.Linear(10, 30), nn.LeakyReLU(0.2), nn.Linear(30, 30)))
+    assert isinstance(leaky[1], nn.LeakyReLU) and leaky[1].negative_slope == 0.2
+    # the codec still recognises the module
+    model = types.SimpleNamespace(get_grid_mlp=other)
+    assert torch.equal(hac_codec.grid_mlp(model, x), other(x).detach())
+
+
+class _RefChannel(nn.Module):
+    """HAC++'s Channel_CTX_fea from its layer list: MLP_d{c} = Linear(150 + 10 c, 40) - LeakyReLU - Linear(40, 30) over cat([fea_q[:, :10 c], mean_scale])"""
+    def __init__(self):
+        super().__init__()
+        for c in range(5):
+            setattr(self, f"MLP_d{c}", nn.Sequential(nn.Linear(150 + 10 * c, 40), nn.LeakyReLU(inplace=True), nn.Linear(40, 30)))
+
+    def group(self, c, fea_q, mean_scale):
+        return torch.chunk(getattr(self, f"MLP_d{c}")(torch.cat([fea_q[:, :10 * c], mean_scale], dim=-1)), chunks=3, dim=-1)
+
+    def forward(self, fea_q, mean_scale, to_dec=-1):
+        if to_dec >= 0:
+            return self.group(to_dec, fea_q, mean_scale)
+        gs = [self.group(c, fea_q, mean_scale) for c in range(5)]
+        return tuple(torch.cat([g[j] for g in gs], dim=-1) for j in range(3))
+
+
+class _RefChannelTiny(nn.Module):
+    """Channel_CTX_fea_tiny: three (1, 10) constants for group 0, MLP_d{c} = Linear(10 c, 30) - LeakyReLU - Linear(30, 30) over fea_q[:, :10 c]"""
+    def __init__(self):
+        super().__init__()
+        for name in ("mean_d0", "scale_d0", "prob_d0"):
+            setattr(self, name, nn.Parameter(torch.zeros(1, 10)))
+        for c in range(1, 5):
+            setattr(self, f"MLP_d{c}", nn.Sequential(nn.Linear(10 * c, 30), nn.LeakyReLU(inplace=True), nn.Linear(30, 30)))
+
+    def group(self, c, fea_q, mean_scale):
+        if c == 0:
+            return tuple(p.repeat(fea_q.shape[0], 1) for p in (self.mean_d0, self.scale_d0, self.prob_d0))
+        return torch.chunk(getattr(self, f"MLP_d{c}")(fea_q[:, :10 * c]), chunks=3, dim=-1)
+
+    forward = _RefChannel.forward
+
+
+@pytest.mark.parametrize("tiny", [False, True], ids=["Channel_CTX_fea", "Channel_CTX_fea_tiny"])
+def test_channel_context_modules_match_the_torch_classes(tiny):
+    from gauspcc_amd import mlp
+
+    torch.manual_seed(11)
+    theirs = (_RefChannelTiny if tiny else _RefChannel)()
+    with torch.no_grad():
+        for name in ("mean_d0", "scale_d0", "prob_d0"):
+            if tiny:
+                getattr(theirs, name).normal_()
+    ours = (mlp.Channel_CTX_fea_tiny if tiny else mlp.Channel_CTX_fea)()
+    keys = sorted(ours.state_dict())
+    mlps = range(1, 5) if tiny else range(5)
+    assert keys == sorted([f"MLP_d{c}.{l}.{p}" for c in mlps for l in (0, 2) for p in ("weight", "bias")] + (["mean_d0", "scale_d0", "prob_d0"] if tiny else []))
+    ours.load_state_dict(theirs.state_dict())
+    theirs.load_state_dict(ours.state_dict())
+    ours, theirs = ours.to(DEV), theirs.to(DEV)
+    ref64 = (_RefChannelTiny if tiny else _RefChannel)().double()
+    ref64.load_state_dict({k: v.double().cpu() for k, v in theirs.state_dict().items()})
+    g = torch.Generator().manual_seed(12)
+    n = 2000
+    fea, ms = torch.round(torch.randn(n, 50, generator=g) * 3), torch.randn(n, 150, generator=g)
+    go = [torch.randn(n, 50, generator=g) for _ in range(3)]
+    # rows near a kink of any of the MLPs are left out (the fixture rule)
+    keep = torch.ones(n, dtype=torch.bool)
+    for c in mlps:
+        xin = torch.cat([fea[:, :10 * c], ms], dim=-1) if not tiny else fea[:, :10 * c]
+        keep &= (ref64.get_submodule(f"MLP_d{c}")[0](xin.double()).abs() >= ref.KINK_EPS).all(dim=1)
+    assert keep.double().mean() > 0.9
+    fea, ms, go = fea[keep], ms[keep], [t[keep] for t in go]
+
+    def run(mod, dev, dt):
+        f, m = fea.to(dev, dt).requires_grad_(True), ms.to(dev, dt).requires_grad_(True)
+        out = mod(f, m)
+        leaves = [f] + ([] if tiny else [m]) + list(mod.parameters())
+        grads = torch.autograd.grad(out, leaves, [t.to(dev, dt) for t in go])
+        per_group = [mod(f, m, to_dec=c) for c in range(5)]
+        return [o.detach() for o in out], list(grads), per_group
+
+    o64, g64, _ = run(ref64, "cpu", torch.float64)
+    o32, g32, _ = run(theirs, DEV, torch.float32)
+    od, gd, pg = run(ours, DEV, torch.float32)
+    checks = [_criterion(f"output {j}", od[j], o32[j], o64[j]) for j in range(3)]
+    assert [n_ for n_, _ in ours.named_parameters()] == [n_ for n_, _ in theirs.named_parameters()]
+    checks += [_criterion(f"grad {i}", gd[i], g32[i], g64[i]) for i in range(len(g64))]
+    assert all(ok for ok, _ in checks), [info for ok, info in checks if not ok]
+    for c in range(5):
+        assert len(pg[c]) == 3
+        for j in range(3):
+            assert pg[c][j].shape == (fea.shape[0], 10) and torch.equal(pg[c][j].detach(), od[j][:, 10 * c:10 * c + 10])
+
+
+class _Entropy(nn.Module):
+    """test-side stand-in for HAC's entropy_gaussian: bits of x under N(mean, scale) over a bin of width Q"""
+    def forward(self, x, mean, scale, Q, x_mean=None):
+        d = torch.distributions.normal.Normal(mean, torch.clamp(scale, min=1e-9))
+        return -torch.log2(torch.clamp(d.cdf(x + 0.5 * Q) - d.cdf(x - 0.5 * Q), min=1e-6))
+
+
+def test_training_branch_reaches_mlp_grid_and_the_hash_grid():
+    from gauspcc_amd.mlp import ContextMLP
+    from gauspcc_amd.neural_gaussians import generate_neural_gaussians
+    from gauspcc_amd.synth import SyntheticGaussianModel
+
+    from gauspcc_amd.gridencoder import mix_3D2D_encoding
+
+    pc = SyntheticGaussianModel(3000, seed=3, device=DEV)
+    # HAC's own widths: four features per level (the synthetic model has two), hence mlp_grid 96 - 100 - 175
+    torch.manual_seed(5)
+    pc.n_features_per_level = 4
+    pc.encoding_xyz = mix_3D2D_encoding(n_features=4, resolutions_list=(18, 24, 33, 44, 59, 80, 108, 148, 201, 275, 376, 514), log2_hashmap_size=13,
+                                        resolutions_list_2D=(130, 258, 514, 1026), log2_hashmap_size_2D=15, ste_binary=True, ste_multistep=False,
+                                        add_noise=False, Q=1, differentiable=True).to(DEV)
+    with torch.no_grad():
+        for p in pc.encoding_xyz.parameters():
+            p.normal_()
+    pc.mlp_grid = ContextMLP.from_sequential(nn.Sequential(nn.Linear(pc.encoding_xyz.output_dim, 100), nn.ReLU(True), nn.Linear(100, 175)).to(DEV))
+    assert isinstance(pc.get_grid_mlp, ContextMLP) and (pc.mlp_grid[0].in_features, pc.mlp_grid[2].out_features) == (96, 175)
+    pc.entropy_gaussian = _Entropy()
+    pc.update_anchor_bound = lambda: None
+    for p in pc.encoding_xyz.parameters():
+        p.requires_grad_(True)
+    cam = types.SimpleNamespace(camera_center=pc.get_anchor.mean(dim=0) + torch.tensor([0.0, 0.0, -2.0], device=DEV))
+    torch.manual_seed(0)
+    out = generate_neural_gaussians(cam, pc, None, is_training=True, step=12000)
+    assert len(out) == 11 and out[7] is not None
+    out[7].backward()
+    for name, p in list(pc.mlp_grid.named_parameters()) + list(pc.encoding_xyz.named_parameters()):
+        assert p.grad is not None and torch.isfinite(p.grad).all() and p.grad.abs().sum() > 0, name
+
+
+def test_short_optimisation_follows_the_torch_module():
+    din, dh, dout, act = ref.SHAPES[0]
+    g = torch.Generator().manual_seed(41)
+    n, lr, steps = 2000, 1e-3, 50
+    x = torch.randn(n, din, generator=g).to(DEV)
+    target = torch.randn(n, dout, generator=g).to(DEV) * 0.5
+    w = ref.weights(din, dh, dout, 42)
+    runs = []
+    for make in (_ours, _torch_module):
+        m = make(din, dh, dout, act, w)
+        opt = torch.optim.Adam(m.parameters(), lr=lr)
+        losses = []
+        for _ in range(steps):
+            opt.zero_grad()
+            loss = ((m(x) - target) ** 2).mean()
+            loss.backward()
+            opt.step()
+            losses.append(float(loss.detach()))
+        runs.append(([p.detach() for p in m.parameters()], losses))
+    (ph, lh), (pt, lt) = runs
+    print(f"losses hip {lh[0]:.6f} -> {lh[-1]:.6f}, torch -> {lt[-1]:.6f}")
+    assert lh[-1] < lh[0]
+    assert abs(lh[-1] - lt[-1]) <= 1e-2 * lt[-1], (lh[-1], lt[-1])
+    # As in test_gpu_triplane: Adam divides by sqrt(v), so a last-bit difference of a near-zero gradient becomes a step of up to lr.  The runs agree
+    # to 5 % of one step on average; no parameter can be further apart than the two programs can move it in opposite directions (2 lr per step).
+    for a, b in zip(ph, pt):
+        dlt = (a - b).abs()
+        assert float(dlt.mean()) <= 0.05 * lr and float(dlt.max()) <= 2 * lr * steps, (float(dlt.mean()), float(dlt.max()))
