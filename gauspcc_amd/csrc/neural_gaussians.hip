@@ -612,6 +612,100 @@ static int ng_mfma_emit(gpcc_ctx *ctx, const NGArgs &a, const EmitArgs &o, int w
     }
 }
 
+// mlp / d_mlp order: bank, opacity, cov, colour; {w1, b1, w2, b2} each
+void ng_mlps(const float *const *m, Mlp *bank, Mlp *opacity, Mlp *cov, Mlp *color)
+{
+    *bank = Mlp{m[0], m[1], m[2], m[3]}; *opacity = Mlp{m[4], m[5], m[6], m[7]}; *cov = Mlp{m[8], m[9], m[10], m[11]}; *color = Mlp{m[12], m[13], m[14], m[15]};
+}
+
+// the checks of the model's shape that every entry point makes; `who` names the Python function in the messages
+int ng_check(const char *who, int64_t n, int feat_dim, int n_offsets, const float *const *mlp)
+{
+    if (feat_dim != 32 && feat_dim != 50) return fail(GPCC_ERR_ARG, "%s: feat_dim must be 32 or 50 (got %d)", who, feat_dim);
+    if (n_offsets < 1 || n_offsets > 64) return fail(GPCC_ERR_ARG, "%s: bad n_offsets %d", who, n_offsets);
+    if (n < 0 || n * n_offsets >= ((int64_t)1 << 31)) return fail(GPCC_ERR_ARG, "%s: too many Gaussians", who);
+    for (int q = 4; q < 16; ++q)
+        if (!mlp[q]) return fail(GPCC_ERR_ARG, "null MLP tensor %d", q);
+    if (mlp[0] && feat_dim % 4) return fail(GPCC_ERR_ARG, "the feature bank needs feat_dim divisible by 4");
+    return GPCC_OK;
+}
+
+// The launches that come per <F, ROWS, TR>, and the one place that maps the run-time triple (feat_dim, rows given, training) to the
+// instantiations that exist: <32|50, true|false, false> and <32|50, false, true> -- the training path has no rows.  The three lines of ng_launch
+// stand in the order rows, plain, training on purpose: it is the order of instantiation, and the compiler's inlining of the helpers the k_ng_opacity
+// variants share follows it (with the training line first, four of them come out with other instruction streams).
+enum NGStage { NG_OPACITY, NG_EMIT, NG_LANES };
+
+template <int F, bool ROWS, bool TR>
+int ng_launch_as(NGStage stage, gpcc_ctx *ctx, const NGArgs &a, const EmitArgs &o, int waves, hipStream_t st)
+{
+    if (stage == NG_OPACITY) return ng_mfma_opacity<F, ROWS, TR>(ctx, a, waves, st);
+    if (stage == NG_EMIT) return ng_mfma_emit<F, ROWS, TR>(ctx, a, o, waves, st);
+    k_anchor_mlps<F, TR><<<(unsigned)cdiv(a.n, TB), TB, 0, st>>>(a);
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
+int ng_launch(NGStage stage, int feat_dim, bool tr, gpcc_ctx *ctx, const NGArgs &a, const EmitArgs &o, int waves, hipStream_t st)
+{
+    if (a.rows) return feat_dim == 32 ? ng_launch_as<32, true, false>(stage, ctx, a, o, waves, st) : ng_launch_as<50, true, false>(stage, ctx, a, o, waves, st);
+    if (!tr) return feat_dim == 32 ? ng_launch_as<32, false, false>(stage, ctx, a, o, waves, st) : ng_launch_as<50, false, false>(stage, ctx, a, o, waves, st);
+    return feat_dim == 32 ? ng_launch_as<32, false, true>(stage, ctx, a, o, waves, st) : ng_launch_as<50, false, true>(stage, ctx, a, o, waves, st);
+}
+
+struct NGMode {            // what differs between gsnn_generate and gsnn_forward_train (the training path at the end of the file)
+    bool tr;               // the TR kernels: bool keep flags, HAC++'s order on request
+    const int32_t *rows;   // inference: NGArgs::rows
+    uint32_t *pos;         // (n K + 1) the scan of the keep flags: memory of the caller (the backward's state), or null: arena
+    float *nopa;           // (n K) an output of the training call, or null: arena
+    int mafter; uint8_t *keep8;   // NGArgs::mafter, NGArgs::keep8
+};
+
+// The forward for n > 0 anchors: flags -> scan -> the surviving rows, and their count.
+int ng_forward(gpcc_ctx *ctx, const NGMode &m, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
+               const float *scaling, const float *mask, const float *cam_center, const float *const *mlp, float *xyz_out, float *color_out, float *opacity_out,
+               float *scale_out, float *rot_out, int64_t *count_out, hipStream_t st)
+{
+    const int64_t nk = n * n_offsets;
+    static const bool use_mfma = dev_env_int("GAUSPCC_NG_MFMA", 1) != 0;
+    const int waves = !use_mfma ? 0 : feat_dim == 32 ? ng_mfma_waves<32>(mlp[0] != nullptr, n_offsets) : ng_mfma_waves<50>(mlp[0] != nullptr, n_offsets);
+    GP_TRY(ctx->arena.reserve((size_t)nk * (4 + (waves ? 0 : 40) + 4 + 4) + ((size_t)4 << 20)));
+    ctx->arena.reset();
+    TAKE(keep, uint32_t, nk);
+    float *nopa = m.nopa ? m.nopa : ctx->arena.take<float>(nk);
+    uint32_t *pos = m.pos ? m.pos : ctx->arena.take<uint32_t>(nk + 1);
+    if (!nopa || !pos) return fail(GPCC_ERR_NOMEM, "neural Gaussians workspace");
+    NGArgs a = {};
+    a.anchor = anchor; a.feat = feat; a.offsets = offsets; a.scaling = scaling; a.mask = mask; a.rows = m.rows; a.n = n; a.K = n_offsets; a.cam = cam_center;
+    ng_mlps(mlp, &a.bank, &a.opacity, &a.cov, &a.color);
+    a.nopa = nopa; a.keep = keep; a.mafter = m.mafter; a.keep8 = m.keep8;
+    // the survivor count lands in pinned memory: a copy into the stack variable is staged by the runtime and holds the host until it is done -- the emission
+    // was enqueued ~18 us after the scan ended
+    GP_TRY(ctx->hstage.reserve(64));
+    volatile uint32_t *htotal = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
+    *htotal = 0;
+    const EmitArgs o = {offsets, scaling, pos, 0, xyz_out, color_out, opacity_out, scale_out, rot_out};
+    if (!waves) {   // lane kernels: the head outputs go through `dense`
+        TAKE(dense, float, nk * 10);
+        a.dense = dense;
+    }
+    GP_TRY(ng_launch(waves ? NG_OPACITY : NG_LANES, feat_dim, m.tr, ctx, a, o, waves, st));
+    GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
+    HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
+    if (waves) {    // matrix pipe: colour / covariance and the surviving rows in one launch
+        GP_TRY(ng_launch(NG_EMIT, feat_dim, m.tr, ctx, a, o, waves, st));
+    } else {
+        const AsmArgs b = {anchor, offsets, scaling, nopa, a.dense, m.rows, keep, pos, nk, n_offsets, xyz_out, color_out, opacity_out, scale_out, rot_out,
+                           m.mafter ? mask : nullptr};
+        if (m.tr) k_assemble<true><<<(unsigned)cdiv(nk, TB), TB, 0, st>>>(b);
+        else k_assemble<false><<<(unsigned)cdiv(nk, TB), TB, 0, st>>>(b);
+        LAUNCH_CHECK();
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    GP_TRY(device_error_check(ctx));
+    *count_out = (int64_t)*htotal;
+    return GPCC_OK;
+}
+
 }  // namespace
 
 extern "C" int gsnn_generate(gpcc_ctx *ctx, int64_t n, const int32_t *rows, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
@@ -622,57 +716,10 @@ extern "C" int gsnn_generate(gpcc_ctx *ctx, int64_t n, const int32_t *rows, int 
         return fail(GPCC_ERR_ARG, "null argument");
     *count_out = 0;
     if (n <= 0) return GPCC_OK;
-    if (feat_dim != 32 && feat_dim != 50) return fail(GPCC_ERR_ARG, "generate_neural_gaussians: feat_dim must be 32 or 50 (got %d)", feat_dim);
-    if (n_offsets < 1 || n_offsets > 64) return fail(GPCC_ERR_ARG, "generate_neural_gaussians: bad n_offsets %d", n_offsets);
-    if (n * n_offsets >= ((int64_t)1 << 31)) return fail(GPCC_ERR_ARG, "too many Gaussians");
-    for (int q = 4; q < 16; ++q)
-        if (!mlp[q]) return fail(GPCC_ERR_ARG, "null MLP tensor %d", q);
-    if (mlp[0] && feat_dim % 4) return fail(GPCC_ERR_ARG, "the feature bank needs feat_dim divisible by 4");
+    GP_TRY(ng_check("generate_neural_gaussians", n, feat_dim, n_offsets, mlp));
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t nk = n * n_offsets;
-    static const bool use_mfma = dev_env_int("GAUSPCC_NG_MFMA", 1) != 0;
-    const int waves = !use_mfma ? 0 : feat_dim == 32 ? ng_mfma_waves<32>(mlp[0] != nullptr, n_offsets) : ng_mfma_waves<50>(mlp[0] != nullptr, n_offsets);
-    GP_TRY(ctx->arena.reserve((size_t)nk * (4 + (waves ? 0 : 40) + 4 + 4) + ((size_t)4 << 20)));
-    ctx->arena.reset();
-    TAKE(nopa, float, nk); TAKE(keep, uint32_t, nk); TAKE(pos, uint32_t, nk + 1);
-    NGArgs a = {};
-    a.anchor = anchor; a.feat = feat; a.offsets = offsets; a.scaling = scaling; a.mask = mask; a.rows = rows; a.n = n; a.K = n_offsets;
-    a.cam = cam_center;
-    a.bank = Mlp{mlp[0], mlp[1], mlp[2], mlp[3]};
-    a.opacity = Mlp{mlp[4], mlp[5], mlp[6], mlp[7]};
-    a.cov = Mlp{mlp[8], mlp[9], mlp[10], mlp[11]};
-    a.color = Mlp{mlp[12], mlp[13], mlp[14], mlp[15]};
-    a.nopa = nopa; a.keep = keep;
-    // the survivor count lands in pinned memory: a copy into the stack variable is staged by the runtime and holds the host until it is done -- the emission
-    // was enqueued ~18 us after the scan ended
-    GP_TRY(ctx->hstage.reserve(64));
-    volatile uint32_t *htotal = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
-    *htotal = 0;
-    if (waves) {   // matrix pipe: flags -> scan -> colour / covariance and the surviving rows in one launch
-        if (rows) { if (feat_dim == 32) GP_TRY((ng_mfma_opacity<32, true>(ctx, a, waves, st))); else GP_TRY((ng_mfma_opacity<50, true>(ctx, a, waves, st))); }
-        else { if (feat_dim == 32) GP_TRY((ng_mfma_opacity<32, false>(ctx, a, waves, st))); else GP_TRY((ng_mfma_opacity<50, false>(ctx, a, waves, st))); }
-        GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
-        HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
-        EmitArgs o = {offsets, scaling, pos, 0, xyz_out, color_out, opacity_out, scale_out, rot_out};
-        if (rows) { if (feat_dim == 32) GP_TRY((ng_mfma_emit<32, true>(ctx, a, o, waves, st))); else GP_TRY((ng_mfma_emit<50, true>(ctx, a, o, waves, st))); }
-        else { if (feat_dim == 32) GP_TRY((ng_mfma_emit<32, false>(ctx, a, o, waves, st))); else GP_TRY((ng_mfma_emit<50, false>(ctx, a, o, waves, st))); }
-    } else {
-        TAKE(dense, float, nk * 10);
-        a.dense = dense;
-        if (feat_dim == 32) k_anchor_mlps<32><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(a);
-        else k_anchor_mlps<50><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(a);
-        LAUNCH_CHECK();
-        GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
-        HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
-        AsmArgs b = {anchor, offsets, scaling, nopa, dense, rows, keep, pos, nk, n_offsets, xyz_out, color_out, opacity_out, scale_out, rot_out, nullptr};
-        k_assemble<<<(unsigned)cdiv(nk, TB), TB, 0, st>>>(b);
-        LAUNCH_CHECK();
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    GP_TRY(device_error_check(ctx));
-    *count_out = (int64_t)*htotal;
-    return GPCC_OK;
+    return ng_forward(ctx, NGMode{false, rows, nullptr, nullptr, 0, nullptr}, n, feat_dim, n_offsets, anchor, feat, offsets, scaling, mask, cam_center, mlp, xyz_out,
+                      color_out, opacity_out, scale_out, rot_out, count_out, (hipStream_t)stream);
 }
 
 
@@ -996,17 +1043,6 @@ __global__ void k_ngb_zero(float *p, int64_t n)
     if (i < n) p[i] = 0.0f;
 }
 
-int ngb_check(int64_t n, int feat_dim, int n_offsets, const float *const *mlp, int mlp_count)
-{
-    if (feat_dim != 32 && feat_dim != 50) return fail(GPCC_ERR_ARG, "neural_gaussians_train: feat_dim must be 32 or 50 (got %d)", feat_dim);
-    if (n_offsets < 1 || n_offsets > 64) return fail(GPCC_ERR_ARG, "neural_gaussians_train: bad n_offsets %d", n_offsets);
-    if (n < 0 || n * n_offsets >= ((int64_t)1 << 31)) return fail(GPCC_ERR_ARG, "neural_gaussians_train: too many Gaussians");
-    for (int q = 4; q < mlp_count; ++q)
-        if (!mlp[q]) return fail(GPCC_ERR_ARG, "null MLP tensor %d", q);
-    if (mlp[0] && feat_dim % 4) return fail(GPCC_ERR_ARG, "the feature bank needs feat_dim divisible by 4");
-    return GPCC_OK;
-}
-
 }  // namespace
 
 extern "C" int gsnn_forward_train(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
@@ -1017,55 +1053,18 @@ extern "C" int gsnn_forward_train(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_
     if (!ctx || !mlp || !alloc || !pos_out || !count_out) return fail(GPCC_ERR_ARG, "null argument");
     *count_out = 0;
     *pos_out = nullptr;
-    GP_TRY(ngb_check(n, feat_dim, n_offsets, mlp, 16));
+    GP_TRY(ng_check("neural_gaussians_train", n, feat_dim, n_offsets, mlp));
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const int64_t nk = n * n_offsets;
     uint32_t *pos;
-    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)(nk + 1) * 4, &pos, "gsnn_forward_train"));
+    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)(n * n_offsets + 1) * 4, &pos, "gsnn_forward_train"));
     *pos_out = pos;
     if (n == 0) { HIP_TRY(hipMemsetAsync(pos, 0, 4, st)); return GPCC_OK; }
     if (!anchor || !feat || !offsets || !scaling || !mask || !cam_center || !xyz_out || !color_out || !opacity_out || !scale_out || !rot_out || !nopa_out ||
         !keep_out)
         return fail(GPCC_ERR_ARG, "null argument");
-    const int waves = feat_dim == 32 ? ng_mfma_waves<32>(mlp[0] != nullptr, n_offsets) : ng_mfma_waves<50>(mlp[0] != nullptr, n_offsets);
-    GP_TRY(ctx->arena.reserve((size_t)nk * (4 + (waves ? 0 : 40) + 8) + ((size_t)4 << 20)));
-    ctx->arena.reset();
-    TAKE(keep, uint32_t, nk);
-    NGArgs a = {};
-    a.anchor = anchor; a.feat = feat; a.offsets = offsets; a.scaling = scaling; a.mask = mask; a.rows = nullptr; a.n = n; a.K = n_offsets;
-    a.cam = cam_center;
-    a.bank = Mlp{mlp[0], mlp[1], mlp[2], mlp[3]};
-    a.opacity = Mlp{mlp[4], mlp[5], mlp[6], mlp[7]};
-    a.cov = Mlp{mlp[8], mlp[9], mlp[10], mlp[11]};
-    a.color = Mlp{mlp[12], mlp[13], mlp[14], mlp[15]};
-    a.nopa = nopa_out; a.keep = keep; a.mafter = mask_after_opacity != 0; a.keep8 = keep_out;
-    GP_TRY(ctx->hstage.reserve(64));
-    volatile uint32_t *htotal = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
-    *htotal = 0;
-    if (waves) {
-        if (feat_dim == 32) GP_TRY((ng_mfma_opacity<32, false, true>(ctx, a, waves, st))); else GP_TRY((ng_mfma_opacity<50, false, true>(ctx, a, waves, st)));
-        GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
-        HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
-        EmitArgs o = {offsets, scaling, pos, 0, xyz_out, color_out, opacity_out, scale_out, rot_out};
-        if (feat_dim == 32) GP_TRY((ng_mfma_emit<32, false, true>(ctx, a, o, waves, st))); else GP_TRY((ng_mfma_emit<50, false, true>(ctx, a, o, waves, st)));
-    } else {
-        TAKE(dense, float, nk * 10);
-        a.dense = dense;
-        if (feat_dim == 32) k_anchor_mlps<32, true><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(a);
-        else k_anchor_mlps<50, true><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(a);
-        LAUNCH_CHECK();
-        GP_TRY(exclusive_scan_u32(ctx, st, keep, pos, nk, pos + nk));
-        HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(htotal), pos + nk, 4, hipMemcpyDeviceToHost, st));
-        AsmArgs b = {anchor, offsets, scaling, nopa_out, dense, nullptr, keep, pos, nk, n_offsets, xyz_out, color_out, opacity_out, scale_out, rot_out,
-                     mask_after_opacity ? mask : nullptr};
-        k_assemble<true><<<(unsigned)cdiv(nk, TB), TB, 0, st>>>(b);
-        LAUNCH_CHECK();
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    GP_TRY(device_error_check(ctx));
-    *count_out = (int64_t)*htotal;
-    return GPCC_OK;
+    return ng_forward(ctx, NGMode{true, nullptr, pos, nopa_out, mask_after_opacity != 0, keep_out}, n, feat_dim, n_offsets, anchor, feat, offsets, scaling, mask,
+                      cam_center, mlp, xyz_out, color_out, opacity_out, scale_out, rot_out, count_out, st);
 }
 
 extern "C" int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets, const float *anchor, const float *feat, const float *offsets,
@@ -1075,7 +1074,7 @@ extern "C" int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offse
                              gsr_alloc_fn alloc, void *alloc_user, void *stream)
 {
     if (!ctx || !mlp || !d_mlp || !alloc) return fail(GPCC_ERR_ARG, "null argument");
-    GP_TRY(ngb_check(n, feat_dim, n_offsets, mlp, 16));
+    GP_TRY(ng_check("neural_gaussians_train", n, feat_dim, n_offsets, mlp));
     const bool bank = mlp[0] != nullptr;
     for (int q = bank ? 0 : 4; q < 16; ++q)
         if (!d_mlp[q]) return fail(GPCC_ERR_ARG, "null MLP gradient %d", q);
@@ -1105,10 +1104,7 @@ extern "C" int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offse
     NGBArgs b = {};
     b.anchor = anchor; b.feat = feat; b.offsets = offsets; b.scaling = scaling; b.mask = mask; b.cam = cam_center; b.pos = pos;
     b.n = n; b.np = np; b.K = K; b.mafter = mask_after_opacity != 0;
-    b.bank = Mlp{mlp[0], mlp[1], mlp[2], mlp[3]};
-    b.opacity = Mlp{mlp[4], mlp[5], mlp[6], mlp[7]};
-    b.cov = Mlp{mlp[8], mlp[9], mlp[10], mlp[11]};
-    b.color = Mlp{mlp[12], mlp[13], mlp[14], mlp[15]};
+    ng_mlps(mlp, &b.bank, &b.opacity, &b.cov, &b.color);
     b.g_xyz = g_xyz; b.g_color = g_color; b.g_opacity = g_opacity; b.g_scale = g_scale; b.g_rot = g_rot; b.g_nopa = g_nopa;
     b.d_anchor = d_anchor; b.d_feat = d_feat; b.d_offsets = d_offsets; b.d_scaling = d_scaling; b.d_mask = d_mask;
     float *q = ws;

@@ -719,6 +719,176 @@ int make_cam(Cam *cam, int W, int H, const float *view_dev, const float *proj_de
     return GPCC_OK;
 }
 
+// The frame state gsr_forward_train hands to gsr_backward: GSR_STATE_WORDS host words, the fields below in this order (word 0 = L ... word 13 = n_end).
+struct FrameState {
+    uint64_t L, P, W, H;
+    const float2 *xy;
+    const float4 *conic_op;
+    const uint32_t *perm, *offs;
+    const uint2 *ranges;
+    const uint32_t *tile_order, *slots, *slot_ids;
+    const float *final_T;
+    const uint32_t *n_end;
+};
+static_assert(sizeof(FrameState) == 14 * 8 && sizeof(FrameState) <= GSR_STATE_WORDS * 8, "the frame state is fourteen 64-bit words of gsr_forward_train's state[]");
+void store_state(const FrameState &s, uint64_t *state) { memcpy(state, &s, sizeof s); }
+FrameState load_state(const uint64_t *state) { FrameState s; memcpy(&s, state, sizeof s); return s; }
+
+// The buffers of a frame that the backward reads again (and the ping-pong halves of the sorts that fill them), with their element counts.  The
+// training frame takes them from the caller, once; the inference frame from the arena, per attempt, with npix = 0 (final_T and n_end unused).
+struct FrameBufs {
+    float2 *xy;
+    float4 *conic_op;
+    uint32_t *perm_a, *perm_b, *offs, *ord_a, *ord_b, *n_end;
+    uint2 *ranges;
+    float *final_T;
+};
+template <class Taker> void take_frame_bufs(Taker &c, FrameBufs &b, size_t P1, size_t ntiles, size_t npix)
+{
+    b.xy = c.template take<float2>(P1); b.conic_op = c.template take<float4>(P1); b.perm_a = c.template take<uint32_t>(P1); b.perm_b = c.template take<uint32_t>(P1);
+    b.offs = c.template take<uint32_t>(P1 + 1); b.ranges = c.template take<uint2>(ntiles); b.ord_a = c.template take<uint32_t>(ntiles); b.ord_b = c.template take<uint32_t>(ntiles);
+    b.final_T = c.template take<float>(npix); b.n_end = c.template take<uint32_t>(npix);
+}
+
+// What differs between the two frames.  Training: the frame state lives in memory the caller hands out through `alloc` (so that it outlives the
+// call and any other call on the context) and its addresses go to `state`; the tile sort carries slots (k_iota) with the Gaussian ids in slot_ids,
+// and k_render<true> leaves final_T / n_end.  Only the scratch of the sorts stays in ctx->arena.
+struct FrameMode {
+    bool train;
+    gsr_alloc_fn alloc;
+    void *alloc_user;
+    uint64_t *state;
+};
+
+// One frame, from the camera to the image: gsr_forward and gsr_forward_train after their argument checks.
+int render_frame(gpcc_ctx *ctx, const FrameMode &m, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                 const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                 const float *projmatrix, float tan_fovx, float tan_fovy, float *out_color, int *radii, int64_t *num_rendered_out, hipStream_t st)
+{
+    Cam cam;
+    GP_TRY(make_cam(&cam, W, H, viewmatrix, projmatrix, tan_fovx, tan_fovy, scale_modifier));
+    const int ntiles = cam.gx * cam.gy;
+    const size_t P1 = (size_t)std::max(P, 1);
+    static const bool sort2 = dev_env_int("GAUSPCC_RASTER_SORT2", 1) != 0;
+    static const int cull = dev_env_int("GAUSPCC_RASTER_CULL", 1) != 0 ? 1 : 0;   // exact tile culling (tile_touches); 0: the reference's lists
+    static const bool stats = dev_env_int("GAUSPCC_RASTER_STATS", 0) != 0;
+    const bool two_level = m.train || sort2;   // the single sort on (tile << 32 | depth bits) exists for the inference frame only
+    FrameBufs b = {};
+    if (m.train)   // frame state sized by P, the tiles and the pixels: one block from the caller
+        GP_TRY(caller_block(m.alloc, m.alloc_user, "gsr_forward_train: frame state", [&](Carver &c) { take_frame_bufs(c, b, P1, ntiles, (size_t)W * H); }));
+    uint32_t *slot_ids = nullptr, *sa = nullptr, *sb = nullptr;   // training, sized by the pair count: slot -> Gaussian, and the sorted slots (the sort ping-pongs)
+    size_t want = P1 * 112 + (size_t)ntiles * (m.train ? 32 : 8) + ((size_t)8 << 20);
+    uint32_t L = 0;
+    // the two counts a frame reads back mid-way land in pinned memory (copies into stack variables are staged by the runtime, one blocking hop each)
+    GP_TRY(ctx->hstage.reserve(64));
+    volatile uint32_t *hL = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
+    volatile unsigned long long *hrect = reinterpret_cast<volatile unsigned long long *>(ctx->hstage.p + 8);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        GP_TRY(ctx->arena.reserve(want + (size_t)L * 40));
+        ctx->arena.reset();
+        if (!m.train) {   // `want` covers what P sizes and the ranges; the tile order's pair comes out of the slack, or of a second attempt
+            take_frame_bufs(ctx->arena, b, P1, ntiles, 0);
+            if (!b.xy || !b.conic_op || !b.perm_a || !b.perm_b || !b.offs || !b.ranges) return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
+            if (!b.ord_a || !b.ord_b) { want += (size_t)ntiles * 32; continue; }
+        }
+        TAKE(depth, float, P1); TAKE(touched, uint32_t, P1 + 1);
+        TAKE(rect_total, unsigned long long, RECT_SLOTS + 1);      // the slots of k_preprocess, then their sum
+        TAKE(dka, uint64_t, P1); TAKE(dkb, uint64_t, P1); TAKE(recs, uint4, P1);
+        HIP_TRY(hipMemsetAsync(b.ranges, 0, sizeof(uint2) * (size_t)ntiles, st));
+        HIP_TRY(hipMemsetAsync(rect_total, 0, 8 * (RECT_SLOTS + 1), st));
+        unsigned long long rect_host = 0;
+        const uint32_t *perm = two_level ? b.perm_a : nullptr;   // Gaussians in depth order (two-level sort)
+        const uint32_t *offs = two_level ? b.offs : touched;
+        if (P > 0) {
+            k_preprocess<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, means3D, scales, rotations, cov3D_precomp, opacities, cam, radii, b.xy, depth, b.conic_op, touched, cull,
+                                                               cull ? rect_total : nullptr, two_level ? dka : nullptr, two_level ? b.perm_a : nullptr,
+                                                               two_level ? recs : nullptr);
+            LAUNCH_CHECK();
+            if (cull) { k_sum_slots<<<1, RECT_SLOTS, 0, st>>>(rect_total, rect_total + RECT_SLOTS); LAUNCH_CHECK(); }
+            if (two_level) {
+                uint64_t *k0 = dka, *k1 = dkb; uint32_t *v0 = b.perm_a, *v1 = b.perm_b;
+                GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, P, 32));
+                k_sorted_counts<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, k0, b.offs);
+                LAUNCH_CHECK();
+                GP_TRY(exclusive_scan_u32(ctx, st, b.offs, b.offs, P, b.offs + P));
+                perm = v0;
+            } else {
+                GP_TRY(exclusive_scan_u32(ctx, st, touched, touched, P, touched + P));
+            }
+            HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(hL), offs + P, 4, hipMemcpyDeviceToHost, st));
+            if (cull) HIP_TRY(hipMemcpyAsync(const_cast<unsigned long long *>(hrect), rect_total + RECT_SLOTS, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            L = *hL;
+            if (cull) rect_host = *hrect;
+        }
+        if (stats && !m.train)
+            fprintf(stderr, "[gauspcc] rasteriser: %u (Gaussian, tile) pairs sorted and blended, %llu in the bounding squares\n", L, cull ? rect_host : (unsigned long long)L);
+        if (num_rendered_out) *num_rendered_out = cull ? (int64_t)rect_host : (int64_t)L;   // the reference's count: every tile of every bounding square
+        uint32_t *vals_sorted = nullptr;   // what the tile sort carried: Gaussian ids, or (training) slots
+        if (L > 0) {
+            if (m.train && !slot_ids)      // once: a second attempt keeps the block of the first
+                GP_TRY(caller_block(m.alloc, m.alloc_user, "gsr_forward_train: pair state", [&](Carver &c) {
+                    slot_ids = c.take<uint32_t>(L); sa = c.take<uint32_t>(L); sb = c.take<uint32_t>(L);
+                }));
+            uint64_t *ka = ctx->arena.take<uint64_t>(L), *kb = ctx->arena.take<uint64_t>(L);
+            uint32_t *va = m.train ? sa : ctx->arena.take<uint32_t>(L), *vb = m.train ? sb : ctx->arena.take<uint32_t>(L);
+            if (!ka || !kb || !va || !vb || ctx->arena.cap - ctx->arena.off < (size_t)L * 2 + ((size_t)2 << 20)) { want += (size_t)L * 4; continue; }  // grow and redo
+            int tbits = 1;
+            while ((1 << tbits) < ntiles) ++tbits;
+            uint64_t *k0 = ka, *k1 = kb; uint32_t *v0 = va, *v1 = vb;
+            if (two_level) {
+                k_duplicate_sorted<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, perm, recs, b.xy, offs, radii, cam.gx, cam.gy, ka, m.train ? slot_ids : va, b.conic_op, cull);
+                LAUNCH_CHECK();
+                if (m.train) { k_iota<<<(unsigned)cdiv(L, TB), TB, 0, st>>>(L, va); LAUNCH_CHECK(); }
+                GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, L, tbits));   // stable on the same keys: one permutation, carrying ids or slots
+                k_tile_ranges<<<(unsigned)cdiv(L, TB), TB, 0, st>>>((int)L, k0, 0, b.ranges);
+            } else {
+                k_duplicate<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, b.xy, depth, offs, radii, cam.gx, cam.gy, ka, va, b.conic_op, cull);
+                LAUNCH_CHECK();
+                GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, L, 32 + tbits));
+                k_tile_ranges<<<(unsigned)cdiv(L, TB), TB, 0, st>>>((int)L, k0, 32, b.ranges);
+            }
+            LAUNCH_CHECK();
+            vals_sorted = v0;
+        }
+        uint32_t *tile_order = nullptr;
+        {
+            uint64_t *oka = ctx->arena.take<uint64_t>(ntiles), *okb = ctx->arena.take<uint64_t>(ntiles);
+            if (!oka || !okb) { want += (size_t)ntiles * 32; continue; }
+            k_tile_order_keys<<<(unsigned)cdiv(ntiles, TB), TB, 0, st>>>(b.ranges, ntiles, oka, b.ord_a);
+            LAUNCH_CHECK();
+            uint64_t *k0 = oka, *k1 = okb; uint32_t *v0 = b.ord_a, *v1 = b.ord_b;
+            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, ntiles, 8));
+            tile_order = v0;
+        }
+        if (m.train)
+            k_render<true><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background, out_color,
+                                                            slot_ids, b.final_T, b.n_end);
+        else
+            k_render<false><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background, out_color,
+                                                             nullptr, nullptr, nullptr);
+        LAUNCH_CHECK();
+        HIP_TRY(hipStreamSynchronize(st));
+        if (m.train)
+            store_state(FrameState{L, (uint64_t)P, (uint64_t)W, (uint64_t)H, b.xy, b.conic_op, perm, offs, b.ranges, tile_order, vals_sorted, slot_ids, b.final_T, b.n_end},
+                        m.state);
+        return device_error_check(ctx);
+    }
+    return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
+}
+
+// the argument checks gsr_forward and gsr_forward_train share
+int check_frame_args(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp, const float *opacities,
+                     const float *scales, const float *rotations, const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix,
+                     const float *out_color, const int *radii)
+{
+    if (!ctx || !background || !viewmatrix || !projmatrix || !out_color) return fail(GPCC_ERR_ARG, "null argument");
+    if (P > 0 && (!means3D || !colors_precomp || !opacities || !radii)) return fail(GPCC_ERR_ARG, "null argument");
+    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) return fail(GPCC_ERR_ARG, "provide scales + rotations or cov3D_precomp");
+    if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
+    return GPCC_OK;
+}
+
 }  // namespace
 
 extern "C" int gsr_visible_filter(gpcc_ctx *ctx, int P, int W, int H, const float *means3D, const float *scales, float scale_modifier,
@@ -744,213 +914,25 @@ extern "C" int gsr_forward(gpcc_ctx *ctx, int P, const float *background, int W,
                            int *radii, int64_t *num_rendered_out, void *stream)
 {
     (void)prefiltered;
-    if (!ctx || !background || !viewmatrix || !projmatrix || !out_color) return fail(GPCC_ERR_ARG, "null argument");
-    if (P > 0 && (!means3D || !colors_precomp || !opacities || !radii)) return fail(GPCC_ERR_ARG, "null argument");
-    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) return fail(GPCC_ERR_ARG, "provide scales + rotations or cov3D_precomp");
-    if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
+    GP_TRY(check_frame_args(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, out_color, radii));
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    Cam cam;
-    GP_TRY(make_cam(&cam, W, H, viewmatrix, projmatrix, tan_fovx, tan_fovy, scale_modifier));
-    const int ntiles = cam.gx * cam.gy;
-    size_t want = (size_t)std::max(P, 1) * 112 + (size_t)ntiles * 8 + ((size_t)8 << 20);
-    uint32_t L = 0;
-    // the two counts a frame reads back mid-way land in pinned memory (copies into stack variables are staged by the runtime, one blocking hop each)
-    GP_TRY(ctx->hstage.reserve(64));
-    volatile uint32_t *hL = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
-    volatile unsigned long long *hrect = reinterpret_cast<volatile unsigned long long *>(ctx->hstage.p + 8);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        GP_TRY(ctx->arena.reserve(want + (size_t)L * 40));
-        ctx->arena.reset();
-        TAKE(xy, float2, std::max(P, 1)); TAKE(depth, float, std::max(P, 1)); TAKE(conic_op, float4, std::max(P, 1));
-        TAKE(touched, uint32_t, std::max(P, 1) + 1); TAKE(ranges, uint2, ntiles);
-        HIP_TRY(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)ntiles, st));
-        static const bool two_level = dev_env_int("GAUSPCC_RASTER_SORT2", 1) != 0;
-        static const int cull = dev_env_int("GAUSPCC_RASTER_CULL", 1) != 0 ? 1 : 0;   // exact tile culling (tile_touches); 0: the reference's lists
-        TAKE(rect_total, unsigned long long, RECT_SLOTS + 1);      // the slots of k_preprocess, then their sum
-        HIP_TRY(hipMemsetAsync(rect_total, 0, 8 * (RECT_SLOTS + 1), st));
-        unsigned long long rect_host = 0;
-        const uint32_t *perm = nullptr;          // Gaussians in depth order (two-level sort)
-        const uint32_t *offs = touched;
-        uint4 *recs = nullptr;
-        if (P > 0) {
-            uint64_t *dka = nullptr, *dkb = nullptr; uint32_t *dva = nullptr, *dvb = nullptr, *ts = nullptr;
-            if (two_level) {
-                dka = ctx->arena.take<uint64_t>(P); dkb = ctx->arena.take<uint64_t>(P); dva = ctx->arena.take<uint32_t>(P); dvb = ctx->arena.take<uint32_t>(P);
-                ts = ctx->arena.take<uint32_t>((size_t)P + 1); recs = ctx->arena.take<uint4>(P);
-                if (!dka || !dkb || !dva || !dvb || !ts || !recs) return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
-            }
-            k_preprocess<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, means3D, scales, rotations, cov3D_precomp, opacities, cam, radii, xy, depth, conic_op, touched, cull,
-                                                               cull ? rect_total : nullptr, dka, dva, recs);
-            LAUNCH_CHECK();
-            if (cull) { k_sum_slots<<<1, RECT_SLOTS, 0, st>>>(rect_total, rect_total + RECT_SLOTS); LAUNCH_CHECK(); }
-            if (two_level) {
-                uint64_t *k0 = dka, *k1 = dkb; uint32_t *v0 = dva, *v1 = dvb;
-                GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, P, 32));
-                k_sorted_counts<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, k0, ts);
-                LAUNCH_CHECK();
-                GP_TRY(exclusive_scan_u32(ctx, st, ts, ts, P, ts + P));
-                HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(hL), ts + P, 4, hipMemcpyDeviceToHost, st));
-                perm = v0; offs = ts;
-            } else {
-                GP_TRY(exclusive_scan_u32(ctx, st, touched, touched, P, touched + P));
-                HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(hL), touched + P, 4, hipMemcpyDeviceToHost, st));
-            }
-            if (cull) HIP_TRY(hipMemcpyAsync(const_cast<unsigned long long *>(hrect), rect_total + RECT_SLOTS, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            L = *hL;
-            if (cull) rect_host = *hrect;
-        }
-        static const bool stats = dev_env_int("GAUSPCC_RASTER_STATS", 0) != 0;
-        if (stats) fprintf(stderr, "[gauspcc] rasteriser: %u (Gaussian, tile) pairs sorted and blended, %llu in the bounding squares\n", L, cull ? rect_host : (unsigned long long)L);
-        if (num_rendered_out) *num_rendered_out = cull ? (int64_t)rect_host : (int64_t)L;   // the reference's count: every tile of every bounding square
-        uint32_t *vals_sorted = nullptr;
-        if (L > 0) {
-            uint64_t *ka = ctx->arena.take<uint64_t>(L), *kb = ctx->arena.take<uint64_t>(L);
-            uint32_t *va = ctx->arena.take<uint32_t>(L), *vb = ctx->arena.take<uint32_t>(L);
-            if (!ka || !kb || !va || !vb || ctx->arena.cap - ctx->arena.off < (size_t)L * 2 + ((size_t)2 << 20)) { want += (size_t)L * 4; continue; }  // grow and redo
-            int tbits = 1;
-            while ((1 << tbits) < ntiles) ++tbits;
-            uint64_t *k0 = ka, *k1 = kb; uint32_t *v0 = va, *v1 = vb;
-            if (perm) {
-                k_duplicate_sorted<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, perm, recs, xy, offs, radii, cam.gx, cam.gy, ka, va, conic_op, cull);
-                LAUNCH_CHECK();
-                GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, L, tbits));
-                k_tile_ranges<<<(unsigned)cdiv(L, TB), TB, 0, st>>>((int)L, k0, 0, ranges);
-            } else {
-                k_duplicate<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, xy, depth, offs, radii, cam.gx, cam.gy, ka, va, conic_op, cull);
-                LAUNCH_CHECK();
-                GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, L, 32 + tbits));
-                k_tile_ranges<<<(unsigned)cdiv(L, TB), TB, 0, st>>>((int)L, k0, 32, ranges);
-            }
-            LAUNCH_CHECK();
-            vals_sorted = v0;
-        }
-        uint32_t *tile_order = nullptr;
-        {
-            uint64_t *oka = ctx->arena.take<uint64_t>(ntiles), *okb = ctx->arena.take<uint64_t>(ntiles);
-            uint32_t *ova = ctx->arena.take<uint32_t>(ntiles), *ovb = ctx->arena.take<uint32_t>(ntiles);
-            if (!oka || !okb || !ova || !ovb) { want += (size_t)ntiles * 32; continue; }
-            k_tile_order_keys<<<(unsigned)cdiv(ntiles, TB), TB, 0, st>>>(ranges, ntiles, oka, ova);
-            LAUNCH_CHECK();
-            uint64_t *k0 = oka, *k1 = okb; uint32_t *v0 = ova, *v1 = ovb;
-            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, ntiles, 8));
-            tile_order = v0;
-        }
-        k_render<false><<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, vals_sorted, W, H, cam.gx, xy, colors_precomp, conic_op, background, out_color, nullptr, nullptr, nullptr);
-        LAUNCH_CHECK();
-        HIP_TRY(hipStreamSynchronize(st));
-        return device_error_check(ctx);
-    }
-    return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
+    return render_frame(ctx, FrameMode{false, nullptr, nullptr, nullptr}, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations,
+                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, out_color, radii, num_rendered_out, (hipStream_t)stream);
 }
 
-// The training forward: gsr_forward's two-level path, with the frame state the backward needs placed in memory the caller hands out through
-// `alloc` (so that it outlives this call and any other call on the context); only the scratch of the sorts stays in ctx->arena.
+// The training forward: gsr_forward's two-level path with the frame state the backward needs kept (FrameMode).
 extern "C" int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
                                  const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
                                  const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
                                  int *radii, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state, int64_t *num_rendered_out, void *stream)
 {
     (void)prefiltered;
-    if (!ctx || !background || !viewmatrix || !projmatrix || !out_color || !alloc || !state) return fail(GPCC_ERR_ARG, "null argument");
-    if (P > 0 && (!means3D || !colors_precomp || !opacities || !radii)) return fail(GPCC_ERR_ARG, "null argument");
-    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) return fail(GPCC_ERR_ARG, "provide scales + rotations or cov3D_precomp");
-    if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
+    if (!alloc || !state) return fail(GPCC_ERR_ARG, "null argument");
+    GP_TRY(check_frame_args(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, out_color, radii));
     for (int k = 0; k < GSR_STATE_WORDS; ++k) state[k] = 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    Cam cam;
-    GP_TRY(make_cam(&cam, W, H, viewmatrix, projmatrix, tan_fovx, tan_fovy, scale_modifier));
-    const int ntiles = cam.gx * cam.gy;
-    const size_t P1 = (size_t)std::max(P, 1), npix = (size_t)W * H;
-    // frame state sized by P, the tiles and the pixels: one block from the caller
-    float2 *xy;
-    float4 *conic_op;
-    uint32_t *perm_a, *perm_b, *offs, *ord_a, *ord_b, *n_end;
-    uint2 *ranges;
-    float *final_T;
-    GP_TRY(caller_block(alloc, alloc_user, "gsr_forward_train: frame state", [&](Carver &c) {
-        xy = c.take<float2>(P1); conic_op = c.take<float4>(P1); perm_a = c.take<uint32_t>(P1); perm_b = c.take<uint32_t>(P1);
-        offs = c.take<uint32_t>(P1 + 1); ranges = c.take<uint2>(ntiles); ord_a = c.take<uint32_t>(ntiles); ord_b = c.take<uint32_t>(ntiles);
-        final_T = c.take<float>(npix); n_end = c.take<uint32_t>(npix);
-    }));
-    uint32_t *slot_ids = nullptr, *sa, *sb;   // sized by the pair count: slot -> Gaussian, and the sorted slots (two buffers: the sort ping-pongs)
-    size_t want = P1 * 112 + (size_t)ntiles * 32 + ((size_t)8 << 20);
-    uint32_t L = 0;
-    GP_TRY(ctx->hstage.reserve(64));
-    volatile uint32_t *hL = reinterpret_cast<volatile uint32_t *>(ctx->hstage.p);
-    volatile unsigned long long *hrect = reinterpret_cast<volatile unsigned long long *>(ctx->hstage.p + 8);
-    static const int cull = dev_env_int("GAUSPCC_RASTER_CULL", 1) != 0 ? 1 : 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        GP_TRY(ctx->arena.reserve(want + (size_t)L * 40));
-        ctx->arena.reset();
-        TAKE(depth, float, P1); TAKE(touched, uint32_t, P1 + 1);
-        TAKE(rect_total, unsigned long long, RECT_SLOTS + 1);
-        TAKE(dka, uint64_t, P1); TAKE(dkb, uint64_t, P1); TAKE(recs, uint4, P1);
-        HIP_TRY(hipMemsetAsync(ranges, 0, sizeof(uint2) * (size_t)ntiles, st));
-        HIP_TRY(hipMemsetAsync(rect_total, 0, 8 * (RECT_SLOTS + 1), st));
-        unsigned long long rect_host = 0;
-        const uint32_t *perm = perm_a;
-        if (P > 0) {
-            k_preprocess<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, means3D, scales, rotations, cov3D_precomp, opacities, cam, radii, xy, depth, conic_op, touched, cull,
-                                                               cull ? rect_total : nullptr, dka, perm_a, recs);
-            LAUNCH_CHECK();
-            if (cull) { k_sum_slots<<<1, RECT_SLOTS, 0, st>>>(rect_total, rect_total + RECT_SLOTS); LAUNCH_CHECK(); }
-            uint64_t *k0 = dka, *k1 = dkb; uint32_t *v0 = perm_a, *v1 = perm_b;
-            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, P, 32));
-            k_sorted_counts<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, k0, offs);
-            LAUNCH_CHECK();
-            GP_TRY(exclusive_scan_u32(ctx, st, offs, offs, P, offs + P));
-            HIP_TRY(hipMemcpyAsync(const_cast<uint32_t *>(hL), offs + P, 4, hipMemcpyDeviceToHost, st));
-            if (cull) HIP_TRY(hipMemcpyAsync(const_cast<unsigned long long *>(hrect), rect_total + RECT_SLOTS, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            L = *hL;
-            if (cull) rect_host = *hrect;
-            perm = v0;
-        }
-        if (num_rendered_out) *num_rendered_out = cull ? (int64_t)rect_host : (int64_t)L;
-        uint32_t *slots = nullptr;
-        if (L > 0) {
-            if (!slot_ids)
-                GP_TRY(caller_block(alloc, alloc_user, "gsr_forward_train: pair state", [&](Carver &c) {
-                    slot_ids = c.take<uint32_t>(L); sa = c.take<uint32_t>(L); sb = c.take<uint32_t>(L);
-                }));
-            uint64_t *ka = ctx->arena.take<uint64_t>(L), *kb = ctx->arena.take<uint64_t>(L);
-            if (!ka || !kb || ctx->arena.cap - ctx->arena.off < (size_t)L * 2 + ((size_t)2 << 20)) { want += (size_t)L * 4; continue; }  // grow and redo
-            int tbits = 1;
-            while ((1 << tbits) < ntiles) ++tbits;
-            k_duplicate_sorted<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, perm, recs, xy, offs, radii, cam.gx, cam.gy, ka, slot_ids, conic_op, cull);
-            LAUNCH_CHECK();
-            k_iota<<<(unsigned)cdiv(L, TB), TB, 0, st>>>(L, sa);
-            LAUNCH_CHECK();
-            uint64_t *k0 = ka, *k1 = kb; uint32_t *v0 = sa, *v1 = sb;
-            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, L, tbits));   // stable on the same keys: gsr_forward's permutation, carrying slots
-            k_tile_ranges<<<(unsigned)cdiv(L, TB), TB, 0, st>>>((int)L, k0, 0, ranges);
-            LAUNCH_CHECK();
-            slots = v0;
-        }
-        uint32_t *tile_order = nullptr;
-        {
-            uint64_t *oka = ctx->arena.take<uint64_t>(ntiles), *okb = ctx->arena.take<uint64_t>(ntiles);
-            if (!oka || !okb) { want += (size_t)ntiles * 32; continue; }
-            k_tile_order_keys<<<(unsigned)cdiv(ntiles, TB), TB, 0, st>>>(ranges, ntiles, oka, ord_a);
-            LAUNCH_CHECK();
-            uint64_t *k0 = oka, *k1 = okb; uint32_t *v0 = ord_a, *v1 = ord_b;
-            GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, ntiles, 8));
-            tile_order = v0;
-        }
-        k_render<true><<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, slots, W, H, cam.gx, xy, colors_precomp, conic_op, background, out_color,
-                                                        slot_ids, final_T, n_end);
-        LAUNCH_CHECK();
-        HIP_TRY(hipStreamSynchronize(st));
-        state[0] = L; state[1] = (uint64_t)P; state[2] = (uint64_t)W; state[3] = (uint64_t)H;
-        state[4] = (uint64_t)(uintptr_t)xy; state[5] = (uint64_t)(uintptr_t)conic_op; state[6] = (uint64_t)(uintptr_t)perm; state[7] = (uint64_t)(uintptr_t)offs;
-        state[8] = (uint64_t)(uintptr_t)ranges; state[9] = (uint64_t)(uintptr_t)tile_order; state[10] = (uint64_t)(uintptr_t)slots;
-        state[11] = (uint64_t)(uintptr_t)slot_ids; state[12] = (uint64_t)(uintptr_t)final_T; state[13] = (uint64_t)(uintptr_t)n_end;
-        return device_error_check(ctx);
-    }
-    return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
+    return render_frame(ctx, FrameMode{true, alloc, alloc_user, state}, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations,
+                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, out_color, radii, num_rendered_out, (hipStream_t)stream);
 }
 
 extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
@@ -961,7 +943,8 @@ extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const f
 {
     (void)opacities;
     if (!ctx || !state || !background || !viewmatrix || !projmatrix || !dL_dout || !alloc) return fail(GPCC_ERR_ARG, "null argument");
-    if (state[1] != (uint64_t)P || state[2] != (uint64_t)W || state[3] != (uint64_t)H) return fail(GPCC_ERR_ARG, "frame state of another frame");
+    const FrameState s = load_state(state);
+    if (s.P != (uint64_t)P || s.W != (uint64_t)W || s.H != (uint64_t)H) return fail(GPCC_ERR_ARG, "frame state of another frame");
     if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
     if (P <= 0) return GPCC_OK;
     if (!means3D || !colors_precomp || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities) return fail(GPCC_ERR_ARG, "null argument");
@@ -971,23 +954,14 @@ extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const f
     Cam cam;
     GP_TRY(make_cam(&cam, W, H, viewmatrix, projmatrix, tan_fovx, tan_fovy, scale_modifier));
     const int ntiles = cam.gx * cam.gy;
-    const uint64_t L = state[0];
-    const float2 *xy = reinterpret_cast<const float2 *>(state[4]);
-    const float4 *conic_op = reinterpret_cast<const float4 *>(state[5]);
-    const uint32_t *perm = reinterpret_cast<const uint32_t *>(state[6]), *offs = reinterpret_cast<const uint32_t *>(state[7]);
-    const uint2 *ranges = reinterpret_cast<const uint2 *>(state[8]);
-    const uint32_t *tile_order = reinterpret_cast<const uint32_t *>(state[9]), *slots = reinterpret_cast<const uint32_t *>(state[10]);
-    const uint32_t *slot_ids = reinterpret_cast<const uint32_t *>(state[11]);
-    const float *final_T = reinterpret_cast<const float *>(state[12]);
-    const uint32_t *n_end = reinterpret_cast<const uint32_t *>(state[13]);
     float *rec = nullptr;
-    if (L > 0) {
-        GP_TRY(caller_alloc(alloc, alloc_user, (size_t)L * NREC * sizeof(float), &rec, "gsr_backward: records"));
-        k_render_backward<<<(unsigned)ntiles, RT, 0, st>>>(ranges, tile_order, slots, slot_ids, W, H, cam.gx, xy, colors_precomp, conic_op, background,
-                                                           final_T, n_end, dL_dout, rec);
+    if (s.L > 0) {
+        GP_TRY(caller_alloc(alloc, alloc_user, (size_t)s.L * NREC * sizeof(float), &rec, "gsr_backward: records"));
+        k_render_backward<<<(unsigned)ntiles, RT, 0, st>>>(s.ranges, s.tile_order, s.slots, s.slot_ids, W, H, cam.gx, s.xy, colors_precomp, s.conic_op, background,
+                                                           s.final_T, s.n_end, dL_dout, rec);
         LAUNCH_CHECK();
     }
-    k_preprocess_backward<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, perm, offs, rec, means3D, scales, rotations, cov3D_precomp, cam, radii, dL_dmeans3D,
+    k_preprocess_backward<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, s.perm, s.offs, rec, means3D, scales, rotations, cov3D_precomp, cam, radii, dL_dmeans3D,
                                                                 dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D);
     LAUNCH_CHECK();
     return GPCC_OK;

@@ -24,7 +24,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
-from .runtime import ptrs
+from .runtime import ptr, ptrs
 from .hac_codec import Q_FEAT, Q_OFFSETS, Q_SCALING, grid_mlp, ste_multistep
 
 
@@ -42,11 +42,24 @@ def quant_steps(pc, anchor):
             (Q_OFFSETS * (1 + torch.tanh(qa_o.contiguous()))).repeat(1, 3 * K))
 
 
-def _linears(seq):
-    mods = [m for m in seq if isinstance(m, torch.nn.Linear)]
-    if len(mods) != 2:
-        raise TypeError("expected nn.Sequential(Linear, ReLU, Linear, ...) as built in HAC/scene/gaussian_model.py:229-256")
-    return [t.detach().float().contiguous() for t in (mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias)]
+def _f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _mlp_tensors(pc, convert=lambda p: p):
+    """{w1, b1, w2, b2} of mlp_feature_bank (None x 4 without the bank), mlp_opacity, mlp_cov, mlp_color, each through `convert`."""
+    def walk(seq):
+        mods = [m for m in seq if isinstance(m, torch.nn.Linear)]
+        if len(mods) != 2:
+            raise TypeError("expected nn.Sequential(Linear, ReLU, Linear, ...) as built in HAC/scene/gaussian_model.py:229-256")
+        return [convert(p) for p in (mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias)]
+    bank = walk(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
+    return bank + walk(pc.get_opacity_mlp) + walk(pc.get_cov_mlp) + walk(pc.get_color_mlp)
+
+
+def _linears(pc):
+    """The 16 tensors as detached float32 contiguous copies: what the inference call reads."""
+    return _mlp_tensors(pc, _f32)
 
 
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0):
@@ -58,7 +71,6 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
 @torch.no_grad()
 def _generate_inference(viewpoint_camera, pc, visible_mask):
     time_sub = 0
-    f32 = lambda t: t.detach().float().contiguous()
     dev = pc.get_anchor.device
     K, F = pc.n_offsets, pc.feat_dim
     rows = None
@@ -85,21 +97,15 @@ def _generate_inference(viewpoint_camera, pc, visible_mask):
         if visible_mask is not None:
             rows = torch.nonzero(visible_mask).view(-1).to(torch.int32)
             n = rows.numel()
-    tensors = []
-    if getattr(pc, "use_feat_bank", False):
-        tensors += _linears(pc.get_featurebank_mlp)
-    else:
-        tensors += [None] * 4
-    tensors += _linears(pc.get_opacity_mlp) + _linears(pc.get_cov_mlp) + _linears(pc.get_color_mlp)
-    ptrs = (C.c_void_p * 16)(*[None if t is None else t.data_ptr() for t in tensors])
-    anchor, feat, grid_offsets, grid_scaling = f32(anchor), f32(feat), f32(grid_offsets), f32(grid_scaling)
-    mask = f32(binary_grid_masks).view(-1, K)
-    cam = f32(viewpoint_camera.camera_center).view(3)
+    tensors = _linears(pc)
+    anchor, feat, grid_offsets, grid_scaling = _f32(anchor), _f32(feat), _f32(grid_offsets), _f32(grid_scaling)
+    mask = _f32(binary_grid_masks).view(-1, K)
+    cam = _f32(viewpoint_camera.camera_center).view(3)
     xyz = torch.empty(n * K, 3, device=dev); color = torch.empty(n * K, 3, device=dev); opacity = torch.empty(n * K, 1, device=dev)
     scaling = torch.empty(n * K, 3, device=dev); rot = torch.empty(n * K, 4, device=dev)
     m = C.c_int64()
-    _lib.check(_lib.lib().gsnn_generate(runtime.context(dev), n, None if rows is None else rows.data_ptr(), F, K, anchor.data_ptr(), feat.data_ptr(),
-                                        grid_offsets.data_ptr(), grid_scaling.data_ptr(), mask.data_ptr(), cam.data_ptr(), ptrs, xyz.data_ptr(), color.data_ptr(),
+    _lib.check(_lib.lib().gsnn_generate(runtime.context(dev), n, ptr(rows), F, K, anchor.data_ptr(), feat.data_ptr(),
+                                        grid_offsets.data_ptr(), grid_scaling.data_ptr(), mask.data_ptr(), cam.data_ptr(), ptrs(tensors, 16), xyz.data_ptr(), color.data_ptr(),
                                         opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), C.byref(m), runtime.stream_ptr(dev)))
     m = m.value
     return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m], time_sub
@@ -108,15 +114,8 @@ def _generate_inference(viewpoint_camera, pc, visible_mask):
 # ---- training path ----------------------------------------------------------------------------------------------------------------------
 
 def _mlp_params(pc):
-    """The 16 parameters {w1, b1, w2, b2} of mlp_feature_bank (None x 4 without the bank), mlp_opacity, mlp_cov, mlp_color: the tensors
-    themselves, so that autograd delivers their gradients."""
-    def lin(seq):
-        mods = [m for m in seq if isinstance(m, torch.nn.Linear)]
-        if len(mods) != 2:
-            raise TypeError("expected nn.Sequential(Linear, ReLU, Linear, ...) as built in HAC/scene/gaussian_model.py:229-256")
-        return [mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias]
-    bank = lin(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
-    return bank + lin(pc.get_opacity_mlp) + lin(pc.get_cov_mlp) + lin(pc.get_color_mlp)
+    """The 16 parameters themselves, so that autograd delivers their gradients."""
+    return _mlp_tensors(pc)
 
 
 class _NeuralGaussians(torch.autograd.Function):
@@ -125,12 +124,11 @@ class _NeuralGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mask_after, anchor, feat, grid_offsets, grid_scaling, masks, cam, *params):
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
         dev = anchor.device
         n, F = feat.shape
         K = grid_offsets.shape[1]
-        ins = [f32(anchor), f32(feat), f32(grid_offsets), f32(grid_scaling), f32(masks).view(n, K), f32(cam).view(3)]
-        ws = [None if p is None else f32(p) for p in params]
+        ins = [_f32(anchor), _f32(feat), _f32(grid_offsets), _f32(grid_scaling), _f32(masks).view(n, K), _f32(cam).view(3)]
+        ws = [None if p is None else _f32(p) for p in params]
         nk = n * K
         xyz, color, scaling = (torch.empty(nk, 3, device=dev) for _ in range(3))
         opacity, rot = torch.empty(nk, 1, device=dev), torch.empty(nk, 4, device=dev)
@@ -154,8 +152,7 @@ class _NeuralGaussians(torch.autograd.Function):
         saved = ctx.saved_tensors
         ins, ws = saved[:6], list(saved[6:])
         dev = ins[0].device
-        f32 = lambda t: t.to(torch.float32).contiguous()
-        gs = [f32(g) for g in (g_xyz, g_color, g_opacity, g_scaling, g_rot, g_nopa)]
+        gs = [_f32(g) for g in (g_xyz, g_color, g_opacity, g_scaling, g_rot, g_nopa)]
         d_anchor, d_feat = torch.empty(n, 3, device=dev), torch.empty(n, F, device=dev)
         d_off, d_sc, d_mask = torch.empty(n, K, 3, device=dev), torch.empty(n, 6, device=dev), torch.empty(n, K, device=dev)
         d_ws = [None if w is None else torch.empty_like(w) for w in ws]

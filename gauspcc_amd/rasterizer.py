@@ -49,30 +49,41 @@ def _check_args(shs, colors_precomp, scales, rotations, cov3D_precomp):
         raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
 
 
+class _Frame:
+    """The frame arguments every entry point marshals: the float32 contiguous tensors (held here until the call has returned: their
+    pointers cross the ABI) and the leading C arguments the gsr_* calls share."""
+
+    def __init__(self, rs, means3D, colors=None, opacities=None, scales=None, rotations=None, cov3D_precomp=None):
+        self.means, self.colors, self.opac = _f32(means3D), _f32(colors), _f32(opacities)
+        self.scales, self.rots, self.cov = _f32(scales), _f32(rotations), _f32(cov3D_precomp)
+        self.view, self.proj, self.bg = _f32(rs.viewmatrix), _f32(rs.projmatrix), _f32(rs.bg)
+        self.P, self.dev = self.means.shape[0], self.means.device
+        self.H, self.W = int(rs.image_height), int(rs.image_width)
+        self.scale_modifier, self.prefiltered = float(rs.scale_modifier), int(bool(rs.prefiltered))
+        self.camera = (self.view.data_ptr(), self.proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy))
+        # P, background, W, H, means3D, colors, opacities, scales, scale_modifier, rotations, cov3D_precomp, view, proj, tan_fovx, tan_fovy
+        self.args = (self.P, ptr(self.bg), self.W, self.H, self.means.data_ptr(), ptr(self.colors), ptr(self.opac), ptr(self.scales),
+                     self.scale_modifier, ptr(self.rots), ptr(self.cov), *self.camera)
+
+    def empty(self, *shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=self.dev)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """Training path.  The frame state the backward needs lives in uint8 tensors handed to the library through its allocator callback and
     kept on the autograd context: it dies with the graph, and other rasteriser calls may run between forward and backward."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, opacities, colors_precomp, scales, rotations, cov3D_precomp, raster_settings, info):
-        rs = raster_settings
-        m, col, op = _f32(means3D), _f32(colors_precomp), _f32(opacities)
-        sc, rot, cov = _f32(scales), _f32(rotations), _f32(cov3D_precomp)
-        P = m.shape[0]
-        dev = m.device
-        H, W = int(rs.image_height), int(rs.image_width)
-        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
-        view, proj, bg = _f32(rs.viewmatrix), _f32(rs.projmatrix), _f32(rs.bg)
-        work = runtime.Workspace(dev)
+        f = _Frame(raster_settings, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp)
+        color, radii = f.empty(3, f.H, f.W), f.empty(f.P, dtype=torch.int32)
+        work = runtime.Workspace(f.dev)
         state = (C.c_uint64 * _lib.GSR_STATE_WORDS)()
         n = C.c_int64()
-        _lib.check(_lib.lib().gsr_forward_train(
-            runtime.context(dev), P, bg.data_ptr(), W, H, m.data_ptr(), col.data_ptr(), op.data_ptr(), ptr(sc), float(rs.scale_modifier), ptr(rot),
-            ptr(cov), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy), int(bool(rs.prefiltered)), color.data_ptr(), radii.data_ptr(),
-            work.fn(), None, state, C.byref(n), runtime.stream_ptr(dev)))
+        _lib.check(_lib.lib().gsr_forward_train(runtime.context(f.dev), *f.args, f.prefiltered, color.data_ptr(), radii.data_ptr(), work.fn(), None, state,
+                                                C.byref(n), runtime.stream_ptr(f.dev)))
         info["num_rendered"] = n.value
-        ctx.rs = rs
+        ctx.rs = raster_settings
         ctx.frame = (work, state)
         ctx.save_for_backward(means3D, means2D, opacities, colors_precomp, scales, rotations, cov3D_precomp, radii)
         ctx.mark_non_differentiable(radii)
@@ -82,26 +93,16 @@ class _RasterizeGaussians(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_color, grad_radii):
         means3D, means2D, opacities, colors_precomp, scales, rotations, cov3D_precomp, radii = ctx.saved_tensors
-        rs = ctx.rs
-        state = ctx.frame[1]
-        m, col, op = _f32(means3D), _f32(colors_precomp), _f32(opacities)
-        sc, rot, cov = _f32(scales), _f32(rotations), _f32(cov3D_precomp)
-        P = m.shape[0]
-        dev = m.device
-        H, W = int(rs.image_height), int(rs.image_width)
-        view, proj, bg = _f32(rs.viewmatrix), _f32(rs.projmatrix), _f32(rs.bg)
+        f = _Frame(ctx.rs, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp)
         dout = _f32(grad_color)
-        g = {k: torch.empty(shape, dtype=torch.float32, device=dev)
-             for k, shape in (("m3", (P, 3)), ("m2", (P, 3)), ("col", (P, 3)), ("op", (P,)))}
-        if cov is None:
-            g["sc"], g["rot"] = torch.empty((P, 3), dtype=torch.float32, device=dev), torch.empty((P, 4), dtype=torch.float32, device=dev)
+        g = {"m3": f.empty(f.P, 3), "m2": f.empty(f.P, 3), "col": f.empty(f.P, 3), "op": f.empty(f.P)}
+        if f.cov is None:
+            g["sc"], g["rot"] = f.empty(f.P, 3), f.empty(f.P, 4)
         else:
-            g["cov"] = torch.empty((P, 6), dtype=torch.float32, device=dev)
+            g["cov"] = f.empty(f.P, 6)
         _lib.check(_lib.lib().gsr_backward(
-            runtime.context(dev), state, P, bg.data_ptr(), W, H, m.data_ptr(), col.data_ptr(), op.data_ptr(), ptr(sc), float(rs.scale_modifier), ptr(rot),
-            ptr(cov), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy), radii.data_ptr(), dout.data_ptr(),
-            runtime.Workspace(dev).fn(), None, g["m3"].data_ptr(), g["m2"].data_ptr(), g["col"].data_ptr(), g["op"].data_ptr(), ptr(g.get("sc")),
-            ptr(g.get("rot")), ptr(g.get("cov")), runtime.stream_ptr(dev)))
+            runtime.context(f.dev), ctx.frame[1], *f.args, radii.data_ptr(), dout.data_ptr(), runtime.Workspace(f.dev).fn(), None, g["m3"].data_ptr(),
+            g["m2"].data_ptr(), g["col"].data_ptr(), g["op"].data_ptr(), ptr(g.get("sc")), ptr(g.get("rot")), ptr(g.get("cov")), runtime.stream_ptr(f.dev)))
         ctx.frame = None   # the frame state goes with its workspace
 
         def out(key, t):
@@ -120,16 +121,10 @@ class GaussianRasterizer(nn.Module):
 
     @torch.no_grad()
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
-        rs = self.raster_settings
-        means3D, scales, rotations, cov3D_precomp = _f32(means3D), _f32(scales), _f32(rotations), _f32(cov3D_precomp)
-        P = means3D.shape[0]
-        radii = torch.empty(P, dtype=torch.int32, device=means3D.device)       # k_preprocess writes every entry
-        view, proj = _f32(rs.viewmatrix), _f32(rs.projmatrix)
-        _lib.check(_lib.lib().gsr_visible_filter(
-            runtime.context(means3D.device), P, int(rs.image_width), int(rs.image_height), means3D.data_ptr(),
-            None if scales is None else scales.data_ptr(), float(rs.scale_modifier), None if rotations is None else rotations.data_ptr(),
-            None if cov3D_precomp is None else cov3D_precomp.data_ptr(), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy),
-            int(bool(rs.prefiltered)), radii.data_ptr(), runtime.stream_ptr(means3D.device)))
+        f = _Frame(self.raster_settings, means3D, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+        radii = f.empty(f.P, dtype=torch.int32)       # k_preprocess writes every entry
+        _lib.check(_lib.lib().gsr_visible_filter(runtime.context(f.dev), f.P, f.W, f.H, f.means.data_ptr(), ptr(f.scales), f.scale_modifier,
+                                                 ptr(f.rots), ptr(f.cov), *f.camera, f.prefiltered, radii.data_ptr(), runtime.stream_ptr(f.dev)))
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
@@ -144,21 +139,10 @@ class GaussianRasterizer(nn.Module):
 
     @torch.no_grad()
     def _forward_inference(self, means3D, opacities, colors_precomp, scales, rotations, cov3D_precomp):
-        rs = self.raster_settings
-        means3D, colors, opac = _f32(means3D), _f32(colors_precomp), _f32(opacities)
-        scales, rotations, cov3D_precomp = _f32(scales), _f32(rotations), _f32(cov3D_precomp)
-        P = means3D.shape[0]
-        dev = means3D.device
-        H, W = int(rs.image_height), int(rs.image_width)
-        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty(P, dtype=torch.int32, device=dev)       # k_preprocess writes every entry
-        view, proj, bg = _f32(rs.viewmatrix), _f32(rs.projmatrix), _f32(rs.bg)
+        f = _Frame(self.raster_settings, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp)
+        color, radii = f.empty(3, f.H, f.W), f.empty(f.P, dtype=torch.int32)       # k_preprocess writes every entry
         n = C.c_int64()
-        _lib.check(_lib.lib().gsr_forward(
-            runtime.context(dev), P, bg.data_ptr(), W, H, means3D.data_ptr(), colors.data_ptr(), opac.data_ptr(),
-            None if scales is None else scales.data_ptr(), float(rs.scale_modifier), None if rotations is None else rotations.data_ptr(),
-            None if cov3D_precomp is None else cov3D_precomp.data_ptr(), view.data_ptr(), proj.data_ptr(), float(rs.tanfovx), float(rs.tanfovy),
-            int(bool(rs.prefiltered)), color.data_ptr(), radii.data_ptr(), C.byref(n), runtime.stream_ptr(dev)))
+        _lib.check(_lib.lib().gsr_forward(runtime.context(f.dev), *f.args, f.prefiltered, color.data_ptr(), radii.data_ptr(), C.byref(n), runtime.stream_ptr(f.dev)))
         self.num_rendered = n.value
         return color, radii
 

@@ -96,6 +96,31 @@ def test_forward_matches_restatement(F, K, bank, mask_after, n):
     assert out[6].dtype == torch.bool and out[5].shape == (ts[0].shape[0] * K, 1)
 
 
+@pytest.mark.parametrize("F,K,bank,n", [(32, 5, False, 15),        # less than one 16-anchor tile
+                                        (32, 10, True, 3001),       # ragged last tile, matrix-pipe path, feature bank
+                                        (50, 17, False, 2000)])     # K > 16: the lane kernels and k_assemble
+def test_training_forward_equals_inference_forward(F, K, bank, n):
+    """HAC's order: the training kernels multiply by a mask of exactly 1.0f and otherwise evaluate the inference kernels' expressions, so the
+    five tensors of neural_gaussians_train equal generate_neural_gaussians' for a decoded model holding the same tensors, bit for bit."""
+    from gauspcc_amd.neural_gaussians import generate_neural_gaussians, neural_gaussians_train
+
+    ts, ps = _fixture(n, F, K, bank, False, seed=F + K + n % 83)
+    n = ts[0].shape[0]
+    if n > 16 and n % 16 == 0:          # the fixture leaves anchors out: keep the last tile ragged
+        n -= 1
+    anchor, feat, off, sc, masks = (t[:n].float() for t in ts[:5])
+    assert (n < 16) if K == 5 else (n > 16 and n % 16)
+    pc = _pc(ps, bank)
+    pc.decoded_version, pc.feat_dim, pc.n_offsets = True, F, K
+    pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, pc.get_mask = anchor, feat, off, sc, masks
+    cam = types.SimpleNamespace(camera_center=ts[5].float())
+    want = generate_neural_gaussians(cam, pc, None)[:5]
+    got = neural_gaussians_train(anchor, feat, off, sc, masks, cam.camera_center, pc)
+    assert 0 < want[0].shape[0] < n * K and int(got[6].sum()) == want[0].shape[0]
+    for name, a, b in zip(("xyz", "color", "opacity", "scaling", "rot"), got[:5], want):
+        assert a.shape == b.shape and torch.equal(a, b), name
+
+
 def _upstream(out, seed):
     g = torch.Generator(device=DEV).manual_seed(seed)
     return [torch.randn(o.shape, device=DEV, generator=g) for o in out[:6]]

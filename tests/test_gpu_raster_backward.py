@@ -135,6 +135,33 @@ def test_inference_unchanged():
     assert img_p.grad_fn is None and torch.equal(img_p, img_i)
 
 
+@pytest.mark.parametrize("P", [0, 200])
+def test_degenerate_training_frames(P):
+    """No Gaussian at all (empty inputs that require grad), and 200 Gaussians behind the camera (no (Gaussian, tile) pair: the pair-sized
+    state is never asked for): the training frame is the inference frame, all background, and the backward returns zeros."""
+    from gauspcc_amd.rasterizer import GaussianRasterizer
+
+    W, H = 48, 32
+    sc = rr.training_scene(200, 5, W, H)
+    sc["means"][:, 2] = -7.0 - np.abs(sc["means"][:, 2])        # view depth z + 6 <= -1
+    bg = np.array([0.2, 0.4, 0.1], np.float32)
+    rast = GaussianRasterizer(_settings(sc, W, H, bg))
+    inp = {k: (None if v is None else v.detach()[:P].clone().requires_grad_(True)) for k, v in _inputs(sc, False, 1.0).items()}
+    img_t, radii_t = rast(shs=None, **inp)
+    nr_t = rast.num_rendered
+    with torch.no_grad():
+        img_i, radii_i = rast(shs=None, **inp)
+    assert img_t.grad_fn is not None and img_i.grad_fn is None
+    assert torch.equal(img_t.detach(), img_i) and torch.equal(radii_t, radii_i) and rast.num_rendered == nr_t
+    assert torch.equal(img_i, torch.tensor(bg).cuda()[:, None, None].expand(3, H, W))
+    assert radii_t.shape == (P,) and not radii_t.any()
+    R = torch.tensor(np.random.RandomState(3).randn(3, H, W).astype(np.float32)).cuda()
+    (img_t * R).sum().backward()
+    for k, v in inp.items():
+        if v is not None:
+            assert v.grad is not None and v.grad.shape == v.shape and torch.count_nonzero(v.grad) == 0, k
+
+
 def test_backward_bitwise_deterministic_small():
     from gauspcc_amd.rasterizer import GaussianRasterizer
 
