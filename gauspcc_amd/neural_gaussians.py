@@ -68,6 +68,11 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     return _generate_inference(viewpoint_camera, pc, visible_mask)
 
 
+def _no_gaussians(dev):
+    """(xyz, color, opacity, scaling, rot) of zero Gaussians."""
+    return tuple(torch.empty(0, c, device=dev) for c in (3, 3, 1, 3, 4))
+
+
 @torch.no_grad()
 def _generate_inference(viewpoint_camera, pc, visible_mask):
     time_sub = 0
@@ -82,6 +87,8 @@ def _generate_inference(viewpoint_camera, pc, visible_mask):
         grid_offsets = pc._offset[visible_mask]
         grid_scaling = pc.get_scaling[visible_mask]
         binary_grid_masks = pc.get_mask[visible_mask]
+        if anchor.shape[0] == 0:
+            return (*_no_gaussians(dev), time_sub)
         torch.cuda.synchronize(); t1 = time.time()
         q_feat, q_scaling, q_offsets = quant_steps(pc, anchor)
         feat = ste_multistep(feat, q_feat, pc._anchor_feat.mean())
@@ -97,6 +104,8 @@ def _generate_inference(viewpoint_camera, pc, visible_mask):
         if visible_mask is not None:
             rows = torch.nonzero(visible_mask).view(-1).to(torch.int32)
             n = rows.numel()
+    if n == 0:                      # no visible anchor: the reference's tensor program runs on empty tensors (:33-38, 115-167); no device buffer to hand over
+        return (*_no_gaussians(dev), time_sub)
     tensors = _linears(pc)
     anchor, feat, grid_offsets, grid_scaling = _f32(anchor), _f32(feat), _f32(grid_offsets), _f32(grid_scaling)
     mask = _f32(binary_grid_masks).view(-1, K)

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from . import b_assembly as ba
+
 pytestmark = pytest.mark.gpu
 
 
@@ -200,13 +202,10 @@ def test_b_files_equal_oracle_written_files(torch_cuda, orc, tmp_path):
     bits = ec.encoder(x, file_name=str(tmp_path / "masks.b"))
     xs = x.view(-1).cpu().numpy()
     p1 = np.float32((x.view(-1).sum() / x.numel()).item())              # the float32 the reference stores (:440, 456)
-    cdf = np.empty((xs.size, 3), np.float32)
-    cdf[:, 0], cdf[:, 1], cdf[:, 2] = 0.0, np.float32(1) - p1, 1.0      # :445-448: [0, 1 - p, 1] in float32
-    payload, cnt = orc.hac_encode(xs.astype(np.int16), cdf, 10000)
-    want = p1.tobytes() + np.array([4 * len(cnt)], np.int32).tobytes() + cnt.astype(np.int32).tobytes() + payload.tobytes()
+    want, want_bits = ba.bernoulli_file(orc, xs, p1)                    # :445-448: every row [0, 1 - p, 1] in float32
     got = (tmp_path / "masks.b").read_bytes()
     assert got == want
-    assert bits == (len(payload) + 4 * len(cnt)) * 8 + 64
+    assert bits == want_bits == (len(got) - 8) * 8 + 64
     assert np.array_equal(ec.decoder(xs.size, file_name=str(tmp_path / "masks.b")).cpu().numpy(), xs.astype(np.int16))
     # Gaussian
     n = 23456
@@ -217,10 +216,9 @@ def test_b_files_equal_oracle_written_files(torch_cuda, orc, tmp_path):
     xi = torch.round(xq / q)
     mn, mx = float(xi.min()), float(xi.max())
     lower = arithmetic.calculate_cdf(mean, scale, q, mn, mx).cpu().numpy()
-    payload, cnt = orc.hac_encode((xi - mn).to(torch.int16).cpu().numpy(), lower, 10000)
-    want = np.float32(mn).tobytes() + np.float32(mx).tobytes() + np.array([4 * len(cnt)], np.int32).tobytes() + cnt.astype(np.int32).tobytes() + payload.tobytes()
+    want, want_bits = ba.gaussian_file(orc, (xi - mn).to(torch.int16).cpu().numpy(), lower, mn, mx)
     assert (tmp_path / "feat.b").read_bytes() == want
-    assert bits == (len(payload) + 4 * len(cnt)) * 8 + 96
+    assert bits == want_bits == (len(want) - 12) * 8 + 96
     assert torch.equal(ec.decoder_gaussian(mean, scale, q, file_name=str(tmp_path / "feat.b")), xq)
 
 
@@ -267,10 +265,10 @@ def test_mixture_coder_matches_table_path_and_oracle_files(torch_cuda, orc, tmp_
     assert np.abs(table.cpu().numpy() - otab).max() < 2e-7
     # (2) whole file == oracle-assembled file
     bits = ec.encoder_gaussian_mixed(xq, mean, scale, prob, q, file_name=str(tmp_path / "feat.b"))
-    payload, cnt = orc.hac_encode((xi - mn).to(torch.int16).cpu().numpy(), table.cpu().numpy(), 10000)
-    want = np.float32(mn).tobytes() + np.float32(mx).tobytes() + np.array([4 * len(cnt)], np.int32).tobytes() + cnt.astype(np.int32).tobytes() + payload.tobytes()
+    want, want_bits = ba.gaussian_file(orc, (xi - mn).to(torch.int16).cpu().numpy(), table.cpu().numpy(), mn, mx)
     assert (tmp_path / "feat.b").read_bytes() == want
-    assert bits == (len(payload) + 4 * len(cnt)) * 8 + 96
+    assert bits == want_bits == (len(want) - 12) * 8 + 96
+    _, _, cnt, payload = ba.parse_gaussian(want)
     # fused == table path on the device as well
     tb, tc = arithmetic.arithmetic_encode((xi - mn).to(torch.int16), table, 10000, n, table.shape[1])
     assert tb.cpu().numpy().tobytes() == payload.tobytes() and np.array_equal(tc.cpu().numpy(), cnt)
@@ -386,9 +384,8 @@ def test_factorized_coder_roundtrip_and_table(torch_cuda, orc, tmp_path):
     mn, mx = float(xi.min()), float(xi.max())
     table = ec._factorized_table(lower_func, Q, mn, mx, Cdim, N, x.device)
     assert table.shape == (N * Cdim, int(mx - mn) + 2) and float(table.min()) >= 0 and float(table.max()) <= 1
-    payload, cnt = orc.hac_encode((xi - mn).to(torch.int16).view(-1).cpu().numpy(), table.cpu().numpy(), 10000)
-    want = np.float32(mn).tobytes() + np.float32(mx).tobytes() + np.array([4 * len(cnt)], np.int32).tobytes() + cnt.astype(np.int32).tobytes() + payload.tobytes()
-    assert (tmp_path / "f.b").read_bytes() == want and bits == (len(payload) + 4 * len(cnt)) * 8 + 96
+    want, want_bits = ba.gaussian_file(orc, (xi - mn).to(torch.int16).view(-1).cpu().numpy(), table.cpu().numpy(), mn, mx)
+    assert (tmp_path / "f.b").read_bytes() == want and bits == want_bits == (len(want) - 12) * 8 + 96
     ec.encoder_factorized_chunk(x, lower_func, Q, file_name=str(tmp_path / "fc.b"), chunk_size=500)
     assert len(list(tmp_path.glob("fc_*.b"))) == 3
     assert torch.equal(ec.decoder_factorized_chunk(lower_func, Q, N, Cdim, file_name=str(tmp_path / "fc.b"), chunk_size=500), x)
