@@ -19,7 +19,8 @@ def _settings(sc, W, H, bg, scale_modifier=1.0):
 
     return GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=sc["tx"], tanfovy=sc["ty"], bg=torch.tensor(bg).cuda(),
                                          scale_modifier=scale_modifier, viewmatrix=torch.tensor(sc["view"]).cuda(),
-                                         projmatrix=torch.tensor(sc["proj"]).cuda(), sh_degree=1, campos=torch.tensor([0.0, 0.0, -6.0]).cuda(),
+                                         projmatrix=torch.tensor(sc["proj"]).cuda(), sh_degree=1,
+                                         campos=torch.tensor(sc.get("campos", [0.0, 0.0, -6.0])).cuda(),
                                          prefiltered=False, debug=False)
 
 
@@ -56,9 +57,27 @@ def _device_grads(rast, inp, R):
     (1200, 83, 45, 4, True, 1.0, 300),        # cov3D_precomp
 ])
 def test_gradients_match_float64_reference(n, W, H, seed, use_cov, sm, cluster):
+    _check_gradients(rr.training_scene(n, seed, W, H, cluster=cluster), n, W, H, seed, use_cov, sm, cluster, rr.project)
+
+
+ROTATED = [c for c in rr.CAMERAS if c != "identity"]
+
+
+@pytest.mark.parametrize("n,W,H,seed,use_cov,sm,cluster", [
+    (1200, 83, 45, 3, False, 1.25, 300),
+    (1200, 83, 45, 4, True, 1.0, 300),
+])
+@pytest.mark.parametrize("camera", ROTATED)
+def test_gradients_match_float64_reference_cameras(camera, n, W, H, seed, use_cov, sm, cluster):
+    """The same bounds under the rotated cameras of tests/golden/cameras.npz, against the reference rendered through the index-free
+    projection (raster_ref.project_matrix_form): k_preprocess_backward's reading of the view matrix and of the two focal lengths."""
+    _check_gradients(rr.scene_for_camera(rr.cameras()[camera], n, seed, W, H, cluster=cluster), n, W, H, seed, use_cov, sm, cluster,
+                     rr.project_matrix_form)
+
+
+def _check_gradients(sc, n, W, H, seed, use_cov, sm, cluster, project):
     from gauspcc_amd.rasterizer import GaussianRasterizer
 
-    sc = rr.training_scene(n, seed, W, H, cluster=cluster)
     bg = np.array([0.2, 0.4, 0.1], np.float32)
     rast = GaussianRasterizer(_settings(sc, W, H, bg, sm))
     inp = _inputs(sc, use_cov, sm)
@@ -70,8 +89,11 @@ def test_gradients_match_float64_reference(n, W, H, seed, use_cov, sm, cluster):
     # the reference, binned with the device's radii
     ref_in = {k: (None if v is None else v.detach().cpu().double().requires_grad_(True)) for k, v in inp.items()}
     ref_img, dec = rr.render(ref_in["means3D"], ref_in["opacities"], ref_in["colors_precomp"], ref_in["scales"], ref_in["rotations"],
-                             ref_in["cov3D_precomp"], sm, torch.tensor(sc["view"]), torch.tensor(sc["proj"]), sc["tx"], sc["ty"], W, H, bg, r)
-    assert np.abs(ref_img.detach().numpy() - img.detach().cpu().numpy()).max() < 1e-4
+                             ref_in["cov3D_precomp"], sm, torch.tensor(sc["view"]), torch.tensor(sc["proj"]), sc["tx"], sc["ty"], W, H, bg, r,
+                             project=project)
+    dimg = np.abs(ref_img.detach().numpy() - img.detach().cpu().numpy()).max()
+    print(f"backward {n} {W}x{H} cov3D_precomp={use_cov}: max |image - float64| {dimg:.3e}")
+    assert dimg < 1e-4
     if cluster:
         assert max(d.shape[1] for d in dec.values()) > 256
     (ref_img * R.cpu().double()).sum().backward()
@@ -85,36 +107,43 @@ def test_gradients_match_float64_reference(n, W, H, seed, use_cov, sm, cluster):
         gr = ref_in[k].grad
         gd = v.cpu().double()
         rel = float((gd - gr).norm() / gr.norm())
-        assert rel <= 1e-4, (k, rel)         # measured <= 3.2e-6 (profiles/r07_raster_backward.txt)
+        print(f"  {k}: {rel:.3e}")
+        assert rel <= 1e-4, (k, rel)         # measured <= 3.2e-6 (profiles/r07_raster_backward.txt), <= 5.0e-6 under the cameras (r09_raster_cameras.txt)
 
 
-def test_means2D_matches_reference_pixel_gradient():
-    """means2D.grad[:, :2] is dL/d(NDC) = dL/d(pixel centre) * (W/2, H/2) of the reference with its centre as a free input."""
+def _check_means2D(sc, n, W, H, project):
     from gauspcc_amd.rasterizer import GaussianRasterizer
 
-    n, W, H, seed = 800, 64, 48, 9
-    sc = rr.training_scene(n, seed, W, H)
     bg = np.zeros(3, np.float32)
     rast = GaussianRasterizer(_settings(sc, W, H, bg))
     inp = _inputs(sc, False, 1.0)
     R = torch.tensor(np.random.RandomState(1).randn(3, H, W).astype(np.float32)).cuda()
     _, radii, g = _device_grads(rast, inp, R)
     # the reference with the centre (ix, iy) replaced by a leaf of the same value
-    import tests.raster_ref as mod
     t = {k: inp[k].detach().cpu().double() for k in ("means3D", "opacities", "colors_precomp", "scales", "rotations")}
-    proj = mod.project
-    ix, iy, *rest = proj(t["means3D"], t["scales"], t["rotations"], None, 1.0, torch.tensor(sc["view"]), torch.tensor(sc["proj"]), sc["tx"], sc["ty"], W, H)
+    ix, iy, *rest = project(t["means3D"], t["scales"], t["rotations"], None, 1.0, torch.tensor(sc["view"]), torch.tensor(sc["proj"]), sc["tx"], sc["ty"], W, H)
     cx, cy = ix.clone().requires_grad_(True), iy.clone().requires_grad_(True)
-    try:
-        mod.project = lambda *a, **k: (cx, cy, *rest)
-        img, _ = mod.render(t["means3D"], t["opacities"], t["colors_precomp"], t["scales"], t["rotations"], None, 1.0, torch.tensor(sc["view"]),
-                            torch.tensor(sc["proj"]), sc["tx"], sc["ty"], W, H, bg, radii.cpu())
-    finally:
-        mod.project = proj
+    img, _ = rr.render(t["means3D"], t["opacities"], t["colors_precomp"], t["scales"], t["rotations"], None, 1.0, torch.tensor(sc["view"]),
+                       torch.tensor(sc["proj"]), sc["tx"], sc["ty"], W, H, bg, radii.cpu(), project=lambda *a: (cx, cy, *rest))
     (img * R.cpu().double()).sum().backward()
     ref = torch.stack([cx.grad * (W / 2), cy.grad * (H / 2)], 1)
     dev = g["means2D"].cpu().double()[:, :2]
-    assert float((dev - ref).norm() / ref.norm()) <= 1e-3
+    rel = float((dev - ref).norm() / ref.norm())
+    print(f"means2D {n} {W}x{H}: {rel:.3e}")
+    assert rel <= 1e-3
+
+
+def test_means2D_matches_reference_pixel_gradient():
+    """means2D.grad[:, :2] is dL/d(NDC) = dL/d(pixel centre) * (W/2, H/2) of the reference with its centre as a free input."""
+    n, W, H, seed = 800, 64, 48, 9
+    _check_means2D(rr.training_scene(n, seed, W, H), n, W, H, rr.project)
+
+
+def test_means2D_matches_reference_pixel_gradient_anisotropic():
+    """The same under `general_anisotropic` (tests/golden/cameras.npz): W / 2 != H / 2 and focal_x != focal_y (70.4 against 41.4 pixels),
+    so neither pair can stand in for the other."""
+    n, W, H, seed = 800, 68, 48, 9
+    _check_means2D(rr.scene_for_camera(rr.cameras()["general_anisotropic"], n, seed, W, H), n, W, H, rr.project_matrix_form)
 
 
 def test_inference_unchanged():
@@ -185,7 +214,13 @@ def test_state_survives_other_calls():
     n, W, H = 1500, 96, 64
     sc = rr.training_scene(n, 31, W, H, cluster=100)
     sc2 = dict(sc)
-    view2 = sc["view"].copy(); view2[3, 0] = 0.4; view2[3, 1] = -0.3          # the camera moved (row-vector matrices: translation in row 3)
+    # the camera turned (0.2 rad about (0.3, 1, 0.2)) and moved; p_view2 = Rot p_view + shift; row-vector matrices: Rot^T on the right, translation in row 3
+    k = np.array([0.3, 1.0, 0.2]) / np.linalg.norm([0.3, 1.0, 0.2])
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    turn = np.eye(4); turn[:3, :3] = (np.eye(3) + math.sin(0.2) * K + (1 - math.cos(0.2)) * (K @ K)).T
+    view2 = sc["view"].astype(np.float64) @ turn; view2[3, 0] += 0.4; view2[3, 1] -= 0.3
+    view2 = view2.astype(np.float32)
+    assert np.abs(view2[:3, :3] - view2[:3, :3].T).max() > 0.1
     sc2["view"] = view2
     Pm = np.linalg.solve(sc["view"].astype(np.float64), sc["proj"].astype(np.float64))
     sc2["proj"] = (view2.astype(np.float64) @ Pm).astype(np.float32)

@@ -36,16 +36,14 @@ def _settings(torch, sc, W, H, bg):
 
     return GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=sc["tx"], tanfovy=sc["ty"], bg=torch.tensor(bg).cuda(), scale_modifier=1.0,
                                          viewmatrix=torch.tensor(sc["view"]).cuda(), projmatrix=torch.tensor(sc["proj"]).cuda(), sh_degree=1,
-                                         campos=torch.tensor([0.0, 0.0, -6.0]).cuda(), prefiltered=False, debug=False)
+                                         campos=torch.tensor(sc.get("campos", [0.0, 0.0, -6.0])).cuda(), prefiltered=False, debug=False)
 
 
-@pytest.mark.parametrize("n,W,H", [(3000, 200, 120), (50, 33, 17), (20000, 320, 240)])
-def test_forward_matches_oracle(orc, n, W, H):
+def _check_forward(orc, sc, n, W, H):
     import torch
 
     from gauspcc_amd.rasterizer import GaussianRasterizer, psnr
 
-    sc = _scene(n, n, W, H)
     bg = np.array([0.1, 0.2, 0.3], np.float32)
     rast = GaussianRasterizer(_settings(torch, sc, W, H, bg))
     t = {k: torch.tensor(v).cuda() for k, v in sc.items() if isinstance(v, np.ndarray)}
@@ -56,6 +54,7 @@ def test_forward_matches_oracle(orc, n, W, H):
     assert np.array_equal(radii.cpu().numpy(), rradii)
     assert rast.num_rendered == L and (rradii > 0).sum() > n // 3
     d = np.abs(img.cpu().numpy() - ref)
+    print(f"forward {n} {W}x{H}: {int((rradii > 0).sum())} visible, {L} pairs, max |image - oracle| {d.max():.3e}")
     assert d.max() < 2e-5, d.max()
     target = torch.tensor(np.clip(ref + np.random.RandomState(1).randn(*ref.shape).astype(np.float32) * 0.05, 0, 1)).cuda()
     p_dev = psnr(img.clamp(0, 1), target).mean().item()
@@ -63,13 +62,31 @@ def test_forward_matches_oracle(orc, n, W, H):
     assert abs(p_dev - p_ref) < 0.01
 
 
-def test_visible_filter_matches_forward_radii(orc):
+@pytest.mark.parametrize("n,W,H", [(3000, 200, 120), (50, 33, 17), (20000, 320, 240)])
+def test_forward_matches_oracle(orc, n, W, H):
+    _check_forward(orc, _scene(n, n, W, H), n, W, H)
+
+
+CAMERA_NAMES = ("identity", "yaw90", "general", "general_anisotropic", "translated_scaled")      # tests/golden/cameras.npz (raster_ref.CAMERAS)
+
+
+@pytest.mark.parametrize("n,W,H", [(3000, 200, 120), (50, 33, 17)])
+@pytest.mark.parametrize("camera", CAMERA_NAMES)
+def test_forward_matches_oracle_cameras(orc, camera, n, W, H):
+    """test_forward_matches_oracle under the cameras the reference's own getWorld2View2 / getProjectionMatrix made
+    (tests/golden/make_cameras.py): rotations, unequal focal lengths, tan(FoVx / 2) < tan(FoVy / 2), the scene normalisation's translate
+    and scale.  33 x 17: partial tiles both ways; 200 x 120: 13 x 8 tiles, with squares of more than 64 (tests/test_raster_ref_cpu.py
+    asserts what each scene holds)."""
+    from tests import raster_ref as rr
+
+    _check_forward(orc, rr.scene_for_camera(rr.cameras()[camera], n, rr.CAMERA_SEED, W, H), n, W, H)
+
+
+def _check_visible_filter(orc, sc, n, W, H):
     import torch
 
     from gauspcc_amd.rasterizer import GaussianRasterizer
 
-    W, H, n = 256, 144, 10000
-    sc = _scene(n, 7, W, H)
     rast = GaussianRasterizer(_settings(torch, sc, W, H, np.zeros(3, np.float32)))
     t = {k: torch.tensor(v).cuda() for k, v in sc.items() if isinstance(v, np.ndarray)}
     scales6 = torch.cat([t["scales"], t["scales"]], 1)     # the reference passes scales[:, :3] of a wider tensor (non-contiguous view)
@@ -77,6 +94,68 @@ def test_visible_filter_matches_forward_radii(orc):
     _, rradii, _ = orc.raster_forward(np.zeros(3, np.float32), W, H, sc["means"], None, None, sc["scales"], 1.0, sc["rots"], sc["view"], sc["proj"], sc["tx"], sc["ty"])
     assert np.array_equal(radii.cpu().numpy(), rradii)
     assert 0 < (rradii > 0).sum() < n
+
+
+def test_visible_filter_matches_forward_radii(orc):
+    _check_visible_filter(orc, _scene(10000, 7, 256, 144), 10000, 256, 144)
+
+
+@pytest.mark.parametrize("camera", CAMERA_NAMES)
+def test_visible_filter_matches_forward_radii_cameras(orc, camera):
+    from tests import raster_ref as rr
+
+    n, W, H = 3000, 200, 120
+    _check_visible_filter(orc, rr.scene_for_camera(rr.cameras()[camera], n, rr.CAMERA_SEED, W, H), n, W, H)
+
+
+def test_chain_under_rotated_camera(orc):
+    """visible_filter -> generate_neural_gaussians -> GaussianRasterizer, as tests/test_gpu_rd_loop.py chains them for its axis-aligned
+    camera, under `general_anisotropic` of tests/golden/cameras.npz: the view matrix, the projection and the camera centre (the reference's
+    world_view_transform.inverse()[3, :3], HAC/scene/cameras.py:57) name one camera all along the chain."""
+    import types
+
+    import torch
+
+    from gauspcc_amd.neural_gaussians import generate_neural_gaussians
+    from gauspcc_amd.rasterizer import GaussianRasterizer, psnr
+    from gauspcc_amd.synth import SyntheticGaussianModel
+    from tests import raster_ref as rr
+
+    W, H = 200, 120
+    cam = rr.cameras()["general_anisotropic"]
+    sc = dict(view=cam["world_view_transform"], proj=cam["full_proj_transform"], tx=float(cam["tanfovx"]), ty=float(cam["tanfovy"]),
+              campos=cam["camera_center"])
+    bg = np.array([0.05, 0.1, 0.15], np.float32)
+    rast = GaussianRasterizer(_settings(torch, sc, W, H, bg))
+    pc = SyntheticGaussianModel(20_000, seed=3)
+    anchors = pc.get_anchor
+    n = anchors.shape[0]
+    # the centre and the view matrix agree: a rigid transform keeps every anchor's distance to the camera
+    pv = torch.cat([anchors.cpu().double(), torch.ones(n, 1, dtype=torch.float64)], 1) @ torch.tensor(sc["view"]).double()
+    dist = (anchors.cpu().double() - torch.tensor(sc["campos"]).double()).norm(dim=1)
+    assert float((pv[:, :3].norm(dim=1) - dist).abs().max()) < 1e-5 and float(pv[:, 2].min()) > 0.2
+    rot_id = torch.zeros(n, 4, device="cuda"); rot_id[:, 0] = 1.0
+    with torch.no_grad():
+        radii_pure = rast.visible_filter(means3D=anchors, scales=pc.get_scaling[:, :3], rotations=rot_id, cov3D_precomp=None)
+        _, rpure, _ = orc.raster_forward(bg, W, H, anchors.cpu().numpy(), None, None, pc.get_scaling[:, :3].cpu().numpy(), 1.0, rot_id.cpu().numpy(),
+                                         sc["view"], sc["proj"], sc["tx"], sc["ty"])
+        assert np.array_equal(radii_pure.cpu().numpy(), rpure)
+        visible = radii_pure > 0
+        assert int(visible.sum()) > n // 2
+        xyz, color, opacity, scaling, rot, _ = generate_neural_gaussians(types.SimpleNamespace(camera_center=torch.tensor(sc["campos"]).cuda()), pc, visible)
+        img, radii = rast(means3D=xyz, means2D=torch.zeros_like(xyz), shs=None, colors_precomp=color, opacities=opacity, scales=scaling,
+                          rotations=rot, cov3D_precomp=None)
+    ref, rradii, L = orc.raster_forward(bg, W, H, xyz.cpu().numpy(), color.cpu().numpy(), opacity.cpu().numpy(), scaling.cpu().numpy(), 1.0,
+                                        rot.cpu().numpy(), sc["view"], sc["proj"], sc["tx"], sc["ty"])
+    assert xyz.shape[0] > n and int((rradii > 0).sum()) > xyz.shape[0] // 2
+    assert np.array_equal(radii.cpu().numpy(), rradii)
+    assert rast.num_rendered == L
+    d = np.abs(img.cpu().numpy() - ref)
+    target = torch.tensor(np.clip(ref + np.random.RandomState(1).randn(*ref.shape).astype(np.float32) * 0.05, 0, 1)).cuda()
+    p_dev = psnr(img.clamp(0, 1), target).mean().item()
+    p_ref = psnr(torch.tensor(ref).cuda().clamp(0, 1), target).mean().item()
+    print(f"chain: {int(visible.sum())} of {n} anchors, {xyz.shape[0]} Gaussians, {L} pairs, max |image - oracle| {d.max():.3e}, PSNR {p_dev:.4f} / {p_ref:.4f}")
+    assert abs(p_dev - p_ref) < 0.01
 
 
 def test_empty_and_background():
