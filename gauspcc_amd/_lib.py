@@ -58,6 +58,9 @@ EXPORTS = [
     "gsge_plane_forward", "gsge_plane_backward",
     "gshac_mlp2_backward", "gshac_mlp2_slab_rows",
 ]
+# the tri-plane ARM's entry points: listed apart because tests/test_abi.py matches EXPORTS against the header with a pattern of the
+# prefixes above; tests/test_arm_ref_cpu.py checks these against the header and the library
+EXPORTS_ARM = ["gsarm_rate_forward", "gsarm_rate_backward"]
 
 
 def lib():
@@ -168,6 +171,8 @@ def lib():
     L.gshac_mlp2_backward.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
     L.gshac_mlp2_slab_rows.argtypes = [i64, i32, i32, i32]
     L.gshac_mlp2_slab_rows.restype = i64
+    L.gsarm_rate_forward.argtypes = [vp, i32, pp, ip, ip, ip, vp, i32, ip, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
+    L.gsarm_rate_backward.argtypes = [vp, i32, pp, ip, ip, ip, vp, i32, ip, vp, i32, pp, vp, GSR_ALLOC, vp, vp]
     _lib = L
     return L
 

@@ -1,0 +1,192 @@
+"""The rate of CAT-3DGS's quantised tri-plane latents under its auto-regressive model, on the device (gsarm_rate_forward /
+gsarm_rate_backward): a drop-in for the unfold / index_select / scripted-MLP / compute_rate sequence of scene/arm.py that
+scene/triplane.py runs once per plane and iteration,
+
+    flat_latent, flat_context = get_flat_latent_and_context(sent_latent, 5, self.non_zero_pixel_ctx_index)
+    raw_proba_param = self.arm(flat_context)
+    rate_y, _, _ = compute_rate(flat_latent, raw_proba_param)        ->   rate_y = arm_rate(sent_latent, self.arm)
+
+`ArmMLP(input_ft, layers_dim)` is a plain nn.Module with the reference's parameter names (`mlp.0.w`, `mlp.0.b`, `mlp.2.w`, ...), shapes
+and initialisation, so state dicts move both ways; its `forward` on a [B, 12] tensor is the torch formula.  `arm_rate` is one autograd
+Function: one fused kernel per level forward, and backward one kernel per level that recomputes the hidden layers, a gather for the
+context part of the latents' gradients and one fixed-order reduction of the parameter gradients.  Nothing but the latents is saved; no
+host synchronisation; bitwise reproducible.  The context is the causal half of a 5 x 5 window (12 entries) inside the latent's own
+channel, zero outside the plane.
+
+Differences from the reference: only the float mode (FPFM = 0) and the 5 x 5 mask; one to eight hidden layers of width at most 32
+(ValueError otherwise); inputs must be float32 (TypeError) CUDA tensors (RuntimeError: there is no CPU path).  The noise and
+straight-through quantisers stay torch in the caller.  The wavefront decode loop and the bitstream are not part of this module.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib, runtime
+from .runtime import ptr, ptrs
+
+N_CONTEXT = 12                    # (5 * 5 - 1) / 2: the only mask the reference instantiates
+MAX_HIDDEN_LAYERS, MAX_WIDTH = 8, 32
+
+
+class _Linear(nn.Module):
+    """CustomLinear (x W^T + b) or, with `residual`, CustomLinearResBlock (x W^T + b + x), float mode."""
+    def __init__(self, in_ft, out_ft, residual):
+        super().__init__()
+        self.residual = residual
+        self.w = nn.Parameter(torch.zeros(out_ft, in_ft) if residual else torch.randn(out_ft, in_ft) / out_ft ** 2)
+        self.b = nn.Parameter(torch.zeros(out_ft))
+
+    def forward(self, x):
+        y = nn.functional.linear(x, self.w, self.b)
+        return y + x if self.residual else y
+
+
+class ArmMLP(nn.Module):
+    def __init__(self, input_ft, layers_dim, fpfm=0):
+        super().__init__()
+        if fpfm != 0:
+            raise NotImplementedError("ArmMLP: the fixed-point mode (FPFM != 0) is not supported")
+        self.FPFM = 0
+        self.dims = [int(input_ft)] + [int(v) for v in layers_dim] + [2]
+        layers = []
+        for i, o in zip(self.dims[:-2], self.dims[1:-1]):
+            layers += [_Linear(i, o, i == o), nn.ReLU()]
+        layers.append(_Linear(self.dims[-2], 2, False))   # the output layer is never a residual block
+        self.mlp = nn.Sequential(*layers)
+
+    def set_quant(self, fpfm=0):
+        if fpfm != 0:
+            raise NotImplementedError("ArmMLP.set_quant: the fixed-point mode (FPFM != 0) is not supported")
+        self.FPFM = 0
+
+    def linears(self):
+        return [m for m in self.mlp if isinstance(m, _Linear)]
+
+    def forward(self, x):
+        return self.mlp(x)
+
+
+def _check_arm(arm):
+    if getattr(arm, "FPFM", 0) != 0:
+        raise NotImplementedError("arm_rate: the fixed-point mode (FPFM != 0) is not supported")
+    if not isinstance(arm, ArmMLP):
+        raise TypeError(f"arm_rate: arm must be a gauspcc_amd.arm.ArmMLP, got {type(arm).__name__}")
+    lin = arm.linears()
+    dims = [lin[0].w.shape[1]] + [m.w.shape[0] for m in lin]
+    hidden = dims[1:-1]
+    if dims[0] != N_CONTEXT or dims[-1] != 2:
+        raise ValueError(f"arm_rate: an ARM of {dims[0]} inputs and {dims[-1]} outputs; 12 (the 5 x 5 mask) and 2 are supported")
+    if not 1 <= len(hidden) <= MAX_HIDDEN_LAYERS or any(not 1 <= v <= MAX_WIDTH for v in hidden):
+        raise ValueError(f"arm_rate: hidden layers {hidden}; 1 to {MAX_HIDDEN_LAYERS} of width 1 to {MAX_WIDTH} are supported")
+    for m, i, o in zip(lin, dims[:-1], dims[1:]):
+        if tuple(m.w.shape) != (o, i) or tuple(m.b.shape) != (o,) or m.residual != (i == o and m is not lin[-1]):
+            raise ValueError("arm_rate: the ARM's layers do not chain")
+    params = [p for m in lin for p in (m.w, m.b)]
+    return dims, params
+
+
+class _Plan:
+    """What one call reads: the levels' shapes, the MLP's widths and which outputs are wanted."""
+    def __init__(self, shapes, dims, reduce, return_params):
+        self.shapes, self.dims, self.reduce, self.return_params = shapes, dims, reduce, return_params
+        self.counts = [c * h * w for c, h, w in shapes]
+        self.total = sum(self.counts)
+
+    def args(self, ys, flat):
+        n = len(ys)
+        ints = lambda vs: (ctypes.c_int * max(len(vs), 1))(*vs)   # noqa: E731
+        return (n, ptrs(ys, max(n, 1)), ints([s[0] for s in self.shapes]), ints([s[1] for s in self.shapes]), ints([s[2] for s in self.shapes]),
+                flat.data_ptr(), len(self.dims) - 1, ints(self.dims))
+
+
+def _forward(plan, ys, flat):
+    dev = flat.device
+    new = lambda n: torch.empty(n, dtype=torch.float32, device=dev)   # noqa: E731
+    rate = new(plan.total) if plan.reduce == "none" else None
+    total = new(1) if plan.reduce == "sum" else None
+    mu = new(plan.total) if plan.return_params else None
+    scale = new(plan.total) if plan.return_params else None
+    _lib.check(_lib.lib().gsarm_rate_forward(runtime.context(dev), *plan.args(ys, flat), ptr(rate), ptr(total), ptr(mu), ptr(scale),
+                                             runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
+    out = total.view(()) if plan.reduce == "sum" else rate
+    if not plan.return_params:
+        return (out,)
+    return (out, mu, scale)
+
+
+class _ArmRate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, n_levels, *tensors):
+        ys = [t.detach().reshape(s).contiguous() for t, s in zip(tensors[:n_levels], plan.shapes)]
+        flat = torch.cat([p.detach().reshape(-1) for p in tensors[n_levels:]])
+        ctx.plan, ctx.n_levels = plan, n_levels
+        ctx.latent_shapes = [t.shape for t in tensors[:n_levels]]
+        ctx.param_shapes = [p.shape for p in tensors[n_levels:]]
+        ctx.save_for_backward(flat, *ys)
+        outs = _forward(plan, ys, flat)
+        ctx.mark_non_differentiable(*outs[1:])
+        return outs
+
+    @staticmethod
+    def backward(ctx, grad, *unused):
+        plan, n = ctx.plan, ctx.n_levels
+        flat, *ys = ctx.saved_tensors
+        dev = flat.device
+        need = ctx.needs_input_grad[2:]
+        gys = [torch.empty_like(y) if need[i] else None for i, y in enumerate(ys)]
+        gflat = torch.empty_like(flat) if any(need[n:]) else None
+        if gflat is not None or any(g is not None for g in gys):
+            g = grad.detach().reshape(-1).contiguous()
+            _lib.check(_lib.lib().gsarm_rate_backward(runtime.context(dev), *plan.args(ys, flat), g.data_ptr(), int(plan.reduce == "sum"),
+                                                      ptrs(gys, max(n, 1)), ptr(gflat), runtime.Workspace(dev).fn(), None,
+                                                      runtime.stream_ptr(dev)))
+        gps = [None] * len(ctx.param_shapes)
+        if gflat is not None:
+            parts = gflat.split([s.numel() for s in ctx.param_shapes])
+            gps = [p.view(s) if need[n + i] else None for i, (p, s) in enumerate(zip(parts, ctx.param_shapes))]
+        return (None, None, *[None if g is None else g.view(s) for g, s in zip(gys, ctx.latent_shapes)], *gps)
+
+
+def arm_rate(sent_latent, arm, reduce="sum", return_params=False):
+    """The bits of the quantised latents under `arm`.  sent_latent: one [1, C, H, W] tensor or a list of them (the levels of one plane, as
+    get_density collects them).  reduce="sum": the total, a 0-d tensor, added in a fixed order; reduce="none": the flat per-latent rate in
+    the reference's (level, c, h, w) order.  With return_params also (mu, scale), each a list of [C, H_i, W_i] maps per level, as
+    grid_encode_forward(get_proba_param=True) shapes them (no gradient flows through these)."""
+    who = "arm_rate"
+    if reduce not in ("sum", "none"):
+        raise ValueError(f"{who}: reduce must be 'sum' or 'none', got {reduce!r}")
+    levels = [sent_latent] if isinstance(sent_latent, torch.Tensor) else list(sent_latent)
+    dims, params = _check_arm(arm)
+    if not levels:
+        raise ValueError(f"{who}: no latent")
+    shapes = []
+    for i, t in enumerate(levels + params):
+        name = f"latent {i}" if i < len(levels) else "an ARM parameter"
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be float32, got {t.dtype}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a CUDA tensor (got {t.device}); gauspcc_amd has no CPU path")
+        if t.device != levels[0].device:
+            raise ValueError(f"{who}: {name} on {t.device}, latent 0 on {levels[0].device}")
+        if i < len(levels):
+            if t.dim() == 4 and t.shape[0] == 1:
+                shapes.append(tuple(t.shape[1:]))
+            elif t.dim() == 3:
+                shapes.append(tuple(t.shape))
+            else:
+                raise ValueError(f"{who}: {name} of shape {tuple(t.shape)}; [1, C, H, W] expected")
+            if min(shapes[-1]) < 1:
+                raise ValueError(f"{who}: {name} of shape {tuple(t.shape)} is empty")
+    plan = _Plan(shapes, dims, reduce, bool(return_params))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in levels + params):
+        outs = _ArmRate.apply(plan, len(levels), *levels, *params)
+    else:
+        outs = _forward(plan, [t.detach().reshape(s).contiguous() for t, s in zip(levels, shapes)],
+                        torch.cat([p.detach().reshape(-1) for p in params]))
+    if not return_params:
+        return outs[0]
+    maps = lambda t: [v.view(s) for v, s in zip(t.split(plan.counts), shapes)]   # noqa: E731
+    return outs[0], maps(outs[1]), maps(outs[2])

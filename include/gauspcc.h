@@ -657,6 +657,34 @@ GPCC_API int gshac_mlp2_backward(gpcc_ctx *ctx, const float *x_dev, const float 
 /* rows per slab of gshac_mlp2_backward for n rows of this layer (0 for sizes it does not take) */
 GPCC_API int64_t gshac_mlp2_slab_rows(int64_t n, int din, int dh, int dout);
 
+/* ================= Tri-plane ARM rate (CAT-3DGS/scene/arm.py: get_neighbor, ArmMLP, compute_rate; scene/triplane.py: get_density) =================
+ * The rate of quantised latents under the auto-regressive model.  y[v]: level v, (channels[v], heights[v], widths[v]) float32 device,
+ * contiguous, any values; n_levels in [0, 64], every level of at most 2^30 latents.  The MLP: dims[0 .. n_layers] are its widths, dims[0] = 12
+ * (the causal half of a 5 x 5 mask), 1 to 8 hidden widths in [1, 32], dims[n_layers] = 2; params holds w (out, in) then b (out) of every
+ * layer in order, one flat float32 device buffer.  Hidden widths 16, 16, 16, 16 take a specialised kernel, anything else a generic one.
+ * Per latent (c, h, w), in float32:
+ *   ctx_i = y[c, h - 2 + i / 5, w - 2 + i % 5], i = 0..11, 0 outside the plane; never another channel
+ *   a layer is x W^T + b (+ x for a hidden layer whose widths agree), a ReLU behind every hidden layer; (mu, ls) = MLP(ctx)
+ *   s = exp(-0.5 clamp(ls, -10, 13.8155)); F(t) = 0.5 - 0.5 sign(t - mu) expm1(-|t - mu| / s)
+ *   rate = -log2(max(F(x + 0.5) - F(x - 0.5), 2^-16))
+ * gsarm_rate_forward writes any of rate, mu, scale (flat over the levels in (level, c, h, w) order; NULL = not wanted) and rate_sum (one
+ * value: per-lane sums in double, a fixed tree per workgroup, the workgroups in order).  alloc is needed for rate_sum only (8 bytes per
+ * workgroup and level, at most 1024 workgroups).
+ * gsarm_rate_backward: grad_rate is shaped as rate, or one device value when grad_is_scalar (the summed form).  OVERWRITES grad_y[v]
+ * (shaped as y[v]; NULL entries, or a NULL array, are skipped) and grad_params (shaped as params; NULL = not wanted).  Nothing but the
+ * latent is read: the hidden layers are recomputed.  autograd's choices at the kinks: the floor passes iff the probability is >= 2^-16
+ * (a latent on it adds exactly 0 to every gradient), the clamp passes iff -10 <= ls <= 13.8155, a ReLU where its output is > 0.
+ * The context part of a latent's gradient is a gather from a scratch of 12 floats per latent of the largest level; parameter gradients
+ * are sums per persistent workgroup (at most 1024, carried across the levels), added in a fixed order.  No atomics: bitwise
+ * reproducible.  Workspace through alloc: 12 x 4 bytes per latent of the largest level (when a grad_y is wanted) plus workgroups x
+ * parameters doubles (when grad_params is).  Both calls are enqueued on `stream` without synchronising. */
+GPCC_API int gsarm_rate_forward(gpcc_ctx *ctx, int n_levels, const float *const *y, const int *channels, const int *heights, const int *widths,
+                                const float *params, int n_layers, const int *dims, float *rate, float *rate_sum, float *mu, float *scale,
+                                gsr_alloc_fn alloc, void *alloc_user, void *stream);
+GPCC_API int gsarm_rate_backward(gpcc_ctx *ctx, int n_levels, const float *const *y, const int *channels, const int *heights, const int *widths,
+                                 const float *params, int n_layers, const int *dims, const float *grad_rate, int grad_is_scalar,
+                                 float *const *grad_y, float *grad_params, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
