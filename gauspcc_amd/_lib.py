@@ -57,6 +57,7 @@ EXPORTS = [
     "gsac_rate_forward", "gsac_rate_backward",
     "gsge_plane_forward", "gsge_plane_backward",
     "gshac_mlp2_backward", "gshac_mlp2_slab_rows",
+    "gsac_arm_encode", "gsac_arm_decode", "gsac_arm_cdf_rows",
 ]
 # the tri-plane ARM's entry points: listed apart because tests/test_abi.py matches EXPORTS against the header with a pattern of the
 # prefixes above; tests/test_arm_ref_cpu.py checks these against the header and the library
@@ -173,6 +174,9 @@ def lib():
     L.gshac_mlp2_slab_rows.restype = i64
     L.gsarm_rate_forward.argtypes = [vp, i32, pp, ip, ip, ip, vp, i32, ip, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
     L.gsarm_rate_backward.argtypes = [vp, i32, pp, ip, ip, ip, vp, i32, ip, vp, i32, pp, vp, GSR_ALLOC, vp, vp]
+    L.gsac_arm_encode.argtypes = [vp, i32, pp, ip, ip, ip, ip, vp, i32, ip, ip, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), vp]
+    L.gsac_arm_decode.argtypes = [vp, i32, pp, ip, ip, ip, ip, ip, vp, i32, ip, vp, i64, vp, i64, vp]
+    L.gsac_arm_cdf_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     _lib = L
     return L
 

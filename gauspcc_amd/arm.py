@@ -15,7 +15,8 @@ channel, zero outside the plane.
 
 Differences from the reference: only the float mode (FPFM = 0) and the 5 x 5 mask; one to eight hidden layers of width at most 32
 (ValueError otherwise); inputs must be float32 (TypeError) CUDA tensors (RuntimeError: there is no CPU path).  The noise and
-straight-through quantisers stay torch in the caller.  The wavefront decode loop and the bitstream are not part of this module.
+straight-through quantisers stay torch in the caller.  The bitstream of the latents under this model (encode_triplane / decode_triplane,
+the wavefront decoder) is gauspcc_amd.arm_codec.
 """
 import ctypes
 

@@ -14,6 +14,7 @@
 #include "octree.hpp"
 #include "primitives.hpp"
 #include "rangecoder.hpp"
+#include "coder_tail.hpp"
 
 using namespace gpcc;
 
@@ -373,18 +374,12 @@ extern "C" int gsac_calculate_cdf(gpcc_ctx *ctx, const float *mean, const float 
     return GPCC_OK;
 }
 
-// where an encoder leaves its result: payload and chunk byte counts in the context's pinned buffers, valid until the context's next call
-struct CoderOut {
-    const uint8_t **bytes; int64_t *nbytes; const int32_t **cnt; int64_t *nchunks;
-    bool null() const { return !bytes || !nbytes || !cnt || !nchunks; }
-};
-
 // The tail of every encoder here, from the packed (low, high) words to the caller's pointers: lane-per-chunk coder, compaction, chunk byte counts
 // and payload into the pinned buffers.  The slices encoder also gets its (min, max) table back between the two synchronisations (mm: 2 * nslices
 // ints on the device; nullptr for a single stream).
-static int encode_tail(gpcc_ctx *ctx, hipStream_t st, const uint32_t *lohi, const RcChunk *dch, int nch, uint8_t *scratch, uint32_t sstride, uint32_t *dcnt,
-                       uint32_t *doff, uint8_t *payload, CoderOut out, const int32_t *mm = nullptr, int nslices = 0, float *min_out = nullptr,
-                       float *max_out = nullptr)
+// (declared in coder_tail.hpp: the latent coder of arm_codec.hip ends in it too)
+int encode_tail(gpcc_ctx *ctx, hipStream_t st, const uint32_t *lohi, const RcChunk *dch, int nch, uint8_t *scratch, uint32_t sstride, uint32_t *dcnt,
+                uint32_t *doff, uint8_t *payload, CoderOut out, const int32_t *mm, int nslices, float *min_out, float *max_out)
 {
     GP_TRY(rc_encode_launch(st, lohi, dch, nch, scratch, sstride, dcnt));
     GP_TRY(exclusive_scan_u32(ctx, st, dcnt, doff, nch, doff + nch));

@@ -685,6 +685,30 @@ GPCC_API int gsarm_rate_backward(gpcc_ctx *ctx, int n_levels, const float *const
                                  const float *params, int n_layers, const int *dims, const float *grad_rate, int grad_is_scalar,
                                  float *const *grad_y, float *grad_params, gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
+/* ================= Tri-plane latent bitstream (CAT-3DGS/scene/gaussian_model.py: encode_triplane / decode_triplane) =================
+ * The levels of one plane, coded under the ARM above (same levels / params / dims arguments; the latents must be integers).  The byte
+ * format is this library's own, not the reference's `constriction` streams.  Per latent (mu, s) are what
+ * gsarm_rate_forward returns, quantised mu_q = rint(16 mu) / 16, s_q = max(rint(16 s) / 16, 1 / 16).  Alphabet of a level:
+ * A = ceil(max |y|) + 2 (at most 1024), L = 2 A + 1 symbols, index y + A.  A CDF row has L + 1 uint16 entries: 0, then
+ * rint(F(j - A - 0.5) (65536 - L)) + j for 0 < j < L, then 2^16 (stored as 0), F the Laplace CDF above in float32.
+ * A channel's plane is cut into K = ceil(W / S) strips of S = strips[v] >= 4 columns (K <= 1024); strip k of channel c is chunk
+ * c K + k: its symbols by row, then by column, one torchac-compatible carry-less stream (== gsac_host_encode_u16 on them).
+ * gsac_arm_encode: finds A per level (alphabet_out[v]), codes every chunk; *bytes_out = the chunks' bytes in (level, channel, strip)
+ *   order, *cnt_out = their byte counts (context-owned host memory, valid until the context's next call).  GPCC_ERR_RANGE when a latent
+ *   is not an integer, an alphabet would exceed 1024, or a mu / scale is not finite (nothing usable is returned).
+ * gsac_arm_decode: the inverse into y_out[v] (device, shaped as the levels); bytes / cnt are HOST pointers as gsac_arm_encode returned
+ *   them.  One workgroup per channel, one lane per strip: at step T lane k decodes the segment of row (T - k) / 2 when T - k is even,
+ *   a workgroup barrier per step, K + 2 H - 2 steps.  Bytes past a chunk's count read as zero and symbols stay inside the alphabet: a
+ *   wrong payload decodes to some grid.  Both calls synchronise `stream`.
+ * gsac_arm_cdf_rows: the integer rows of n (mu_q, s_q) pairs (already quantised, device) -> rows_out (n, 2 A + 2) uint16, device. */
+GPCC_API int gsac_arm_encode(gpcc_ctx *ctx, int n_levels, const float *const *y, const int *channels, const int *heights, const int *widths,
+                             const int *strips, const float *params, int n_layers, const int *dims, int *alphabet_out, const uint8_t **bytes_out,
+                             int64_t *nbytes_out, const int32_t **cnt_out, int64_t *nchunks_out, void *stream);
+GPCC_API int gsac_arm_decode(gpcc_ctx *ctx, int n_levels, float *const *y_out, const int *channels, const int *heights, const int *widths,
+                             const int *strips, const int *alphabets, const float *params, int n_layers, const int *dims, const uint8_t *bytes,
+                             int64_t nbytes, const int32_t *cnt, int64_t nchunks, void *stream);
+GPCC_API int gsac_arm_cdf_rows(gpcc_ctx *ctx, const float *mu, const float *scale, int64_t n, int A, uint16_t *rows_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
