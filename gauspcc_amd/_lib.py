@@ -56,6 +56,7 @@ EXPORTS = [
     "gsr_ssim_forward", "gsr_ssim_backward",
     "gsac_rate_forward", "gsac_rate_backward",
     "gsge_plane_forward", "gsge_plane_backward",
+    "gsge_msplane_forward", "gsge_msplane_backward",
     "gshac_mlp2_backward", "gshac_mlp2_slab_rows",
     "gsac_arm_encode", "gsac_arm_decode", "gsac_arm_cdf_rows",
 ]
@@ -169,6 +170,8 @@ def lib():
     L.gsac_rate_backward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp, pp, pp, pp, vp, GSR_ALLOC, vp, vp]
     L.gsge_plane_forward.argtypes = [vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, GSR_ALLOC, vp, vp]
     L.gsge_plane_backward.argtypes = [vp, vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, vp, GSR_ALLOC, vp, vp]
+    L.gsge_msplane_forward.argtypes = [vp, vp, i64, i32, pp, i32, ip, ip, i32, i32, i32, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
+    L.gsge_msplane_backward.argtypes = [vp, vp, vp, i64, i32, pp, i32, ip, ip, i32, i32, i32, vp, vp, vp, vp, vp, pp, vp, GSR_ALLOC, vp, vp]
     L.gshac_mlp2_backward.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
     L.gshac_mlp2_slab_rows.argtypes = [i64, i32, i32, i32]
     L.gshac_mlp2_slab_rows.restype = i64

@@ -643,6 +643,49 @@ GPCC_API int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const flo
                                  const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
                                  float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
+/* ================= Multi-scale tri-plane features (CAT-3DGS/scene/triplane.py: TriPlaneField.forward / get_density :246-342,
+ * interpolate_ms_features :89-146, grid_sample_wrapper :40-65) =================
+ * pts (n, 3); planes: 3 * n_levels device pointers in (level, plane) order, plane i (C, heights[i], widths[i]) with one C for all
+ * (for a resolution (rx, ry, rz) and a multiplier m the reference's planes are (m ry, m rx), (m rz, m rx), (m rz, m ry) as (H, W));
+ * n_levels in [1, 8]; level: the `level` argument of interpolate_ms_features (get_density passes 2); quantise: read rintf(16 v) / 16 for
+ * a texel v (STEQuantizer(latent * 16) / 16: both scalings are exact and torch.round rounds halves to even, so the fused form has the
+ * materialised one's bits).  The transform, all float32 DEVICE pointers (no host copy, no synchronisation): aabb (2, 3) always; with
+ * contract also pca_mean (3), rotation (3, 3), variance (3), con_aabb (2, 3).  Per point, float32 in the reference's expression order:
+ *   contract:  p = pts - pca_mean; q_j = sum_i p_i rotation[i][j]; q = q / variance; x = ((q + 1) / 2) * 2 - 1; mag = |x|_2
+ *              x = (2 - 1 / mag) (x / mag) where mag > 1, else x, formed as the reference's blend x_c m + x (1 - m) with m = 0 / 1
+ *              x = x / 4 + 0.5; g = (x - con_aabb[0]) * ((aabb[1] - aabb[0]) / (con_aabb[1] - con_aabb[0])) + aabb[0]
+ *   otherwise: g = (pts - aabb[0]) * (2 / (aabb[1] - aabb[0])) - 1
+ *   plane p of every level reads the components (0, 1), (0, 2), (1, 2) of g, the first along W, the second along H
+ *   bilinear grid_sample, align_corners true, padding border: pixel = (g + 1) / 2 * (size - 1) clamped to [0, size - 1]; corners and
+ *   weights as grid_sample forms them; a corner at index `size` has weight 0 and is never read
+ *   T_l = the (3 C) concatenation of level l's three reads; F_0 = T_0; F_l = T_l + F_{l-1} if level > l, else F_{l-1}
+ *   out[n, l * 3 C + p * C + ch] = F_l[p * C + ch]: out (n, n_levels * 3 * C)
+ * contract = 0 / 1 select the two lines above; 2: pts are contract_to_unisphere's output already and only the last line (the reference's
+ * con_normalize_aabb, what get_density applies) runs, reading aabb and con_aabb; 3: g = pts, nothing is read (interpolate_ms_features).
+ * A point whose g is not finite in every component gives a zero row and no gradient, and no index is formed from it.  (The reference
+ * yields NaN there: a point the PCA step maps to the origin has 1 / mag = inf in its blend, which this code reproduces and then drops.)
+ * Limits: C in [1, 256], H and W in [2, 4096], n * 3 * n_levels * 4 < 2^32; a violation returns GPCC_ERR_ARG before any launch.
+ * n = 0 launches nothing (the backward zeroes the plane gradients).
+ * gsge_msplane_backward: grad_out (n, n_levels * 3 * C).  The gradient reaching T_l is the sum, in ascending block order, of the
+ * grad_out blocks l' >= l when level l takes part (l = 0 or level > l), and nothing otherwise.  OVERWRITES grad_planes[i], shaped as
+ * plane i (the straight-through quantiser passes it unchanged) and, when grad_pts is not NULL, grad_pts (n, 3): through the bilinear
+ * weights (quantised texels when quantise), zero along an axis whose pixel coordinate was clamped (as torch's border clipping sets it),
+ * and normalize_aabb's scale (contract = 0; none for 3).  With contract the reference detaches the points: a non-NULL grad_pts with
+ * contract = 1 or 2 is GPCC_ERR_ARG.
+ * `planes` is read only for grad_pts (it may be NULL otherwise).  No gradient for the transform's parameters.
+ * Bitwise reproducible: no float atomics (one (texel row, slot) key per (point, level, plane, corner), the rows of all planes in one
+ * key space (a plane's base row plus y W + x), stable radix sort by row, fixed-order sums).
+ * Workspace through `alloc`: forward C floats per texel of all planes; backward about 28 bytes per (point, level, plane, corner) plus
+ * up to twice the forward's.  Both calls are enqueued on `stream` without synchronising. */
+GPCC_API int gsge_msplane_forward(gpcc_ctx *ctx, const float *pts, int64_t n, int n_levels, const float *const *planes, int channels,
+                                  const int *heights, const int *widths, int level, int quantise, int contract, const float *pca_mean,
+                                  const float *rotation, const float *variance, const float *aabb, const float *con_aabb, float *out,
+                                  gsr_alloc_fn alloc, void *alloc_user, void *stream);
+GPCC_API int gsge_msplane_backward(gpcc_ctx *ctx, const float *grad_out, const float *pts, int64_t n, int n_levels, const float *const *planes,
+                                   int channels, const int *heights, const int *widths, int level, int quantise, int contract,
+                                   const float *pca_mean, const float *rotation, const float *variance, const float *aabb, const float *con_aabb,
+                                   float *const *grad_planes, float *grad_pts, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 /* Backward of gshac_mlp2_act (the training forward IS gshac_mlp2_act: nothing is saved).  Recomputes h = b1 + x W1^T with the forward's chain, so
  * the activation mask is the forward's bit for bit (act' = 0 / slope at h <= 0, as torch), then g = (dy W2) o act'(h), dx = g W1, dW2 = dy^T act(h),
  * db2 = sum dy, dW1 = g^T x, db1 = sum g.  dy (n, dout); OVERWRITES dw1 (dh, din), db1 (dh), dw2 (dout, dh), db2 (dout) and, when it is not NULL,
