@@ -59,6 +59,7 @@ EXPORTS = [
     "gsge_msplane_forward", "gsge_msplane_backward",
     "gshac_mlp2_backward", "gshac_mlp2_slab_rows",
     "gsac_arm_encode", "gsac_arm_decode", "gsac_arm_cdf_rows",
+    "gsac_normal_cdf_rows", "gsac_encode_normal_streams", "gsac_decode_normal_streams",
 ]
 # the tri-plane ARM's entry points: listed apart because tests/test_abi.py matches EXPORTS against the header with a pattern of the
 # prefixes above; tests/test_arm_ref_cpu.py checks these against the header and the library
@@ -180,6 +181,9 @@ def lib():
     L.gsac_arm_encode.argtypes = [vp, i32, pp, ip, ip, ip, ip, vp, i32, ip, ip, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), vp]
     L.gsac_arm_decode.argtypes = [vp, i32, pp, ip, ip, ip, ip, ip, vp, i32, ip, vp, i64, vp, i64, vp]
     L.gsac_arm_cdf_rows.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    L.gsac_normal_cdf_rows.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp]
+    L.gsac_encode_normal_streams.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), vp]
+    L.gsac_decode_normal_streams.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]
     _lib = L
     return L
 

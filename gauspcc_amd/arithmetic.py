@@ -257,3 +257,49 @@ def encode_gaussian_mixed_slices(x, mean_list, scale_list, prob_list, Q, slice_s
 def decode_gaussian_mixed_slices(mean_list, scale_list, prob_list, Q, slice_start, mins, maxs, data, cnt, chunk_size):
     """Inverse of encode_gaussian_mixed_slices."""
     return _decode_slices(_mix_args(mean_list, scale_list, prob_list, Q), slice_start, mins, maxs, data, cnt, chunk_size, "decode_gaussian_mixed_slices")
+
+
+# ---------------------------------------------------------------- TC-GS / CAT-3DGS: one torchac stream per slice (torch.distributions' Normal.cdf rows)
+def normal_cdf_rows(mean, scale, Q, min_value, max_value):
+    """int16 rows (n, max - min + 2) of `Normal(mean, scale).cdf((samples - 0.5) * Q)` integerised as torchac does (gsac_normal_cdf_rows):
+    the table the stream coders below evaluate entry by entry, never building it."""
+    _, args, keep, n, device = _gauss_args(mean, scale, Q)
+    mn, mx = int(min_value), int(max_value)
+    rows = torch.zeros((n, mx - mn + 2), dtype=torch.int16, device=device)
+    if n:
+        _lib.check(_lib.lib().gsac_normal_cdf_rows(runtime.context(device), *args, n, mn, mx, rows.data_ptr(), runtime.stream_ptr(device)))
+    return rows
+
+
+def encode_normal_streams(x, mean, scale, Q, slice_start):
+    """Every slice [slice_start[s], slice_start[s+1]) as ONE torchac stream with its own min / max (gsac_encode_normal_streams); slices may be empty.
+    Returns (mins, maxs, bytes, cnt) as numpy arrays: float32 (nslices) x 2, uint8 (the streams in slice order), int32 (nslices) byte counts."""
+    _chk(x, "x")
+    _, args, keep, _, device = _gauss_args(mean, scale, Q)
+    (x32,) = _f32(x)
+    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
+    ns = ss.size - 1
+    mins, maxs = np.zeros(ns, dtype=np.float32), np.zeros(ns, dtype=np.float32)
+    if ns <= 0 or int(ss[-1]) == 0:
+        return mins, maxs, np.empty(0, dtype=np.uint8), np.zeros(max(ns, 0), dtype=np.int32)
+    pb, nb, pc = C.c_void_p(), C.c_int64(), C.c_void_p()
+    _lib.check(_lib.lib().gsac_encode_normal_streams(runtime.context(device), x32.data_ptr(), *args, ss.ctypes.data, ns, mins.ctypes.data, maxs.ctypes.data,
+                                                     C.byref(pb), C.byref(nb), C.byref(pc), runtime.stream_ptr(device)))
+    return mins, maxs, _owned(pb, nb.value, np.uint8), _owned(pc, ns, np.int32)
+
+
+def decode_normal_streams(mean, scale, Q, slice_start, mins, maxs, data, cnt):
+    """Inverse of encode_normal_streams; data / cnt: the concatenated streams and one byte count per slice (numpy).  float32 (n) on mean's device."""
+    _, args, keep, _, device = _gauss_args(mean, scale, Q)
+    ss = np.ascontiguousarray(np.asarray(slice_start, dtype=np.int64))
+    ns = ss.size - 1
+    mins = np.ascontiguousarray(mins, dtype=np.float32); maxs = np.ascontiguousarray(maxs, dtype=np.float32)
+    data = np.ascontiguousarray(data, dtype=np.uint8); cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+    if mins.size != ns or maxs.size != ns or cnt.size != ns:
+        raise ValueError("decode_normal_streams: one (min, max, byte count) per slice")
+    out = torch.empty(int(ss[-1]), dtype=torch.float32, device=device)
+    if ns > 0 and int(ss[-1]) > 0:
+        _lib.check(_lib.lib().gsac_decode_normal_streams(runtime.context(device), *args, ss.ctypes.data, ns, mins.ctypes.data, maxs.ctypes.data,
+                                                         data.ctypes.data if data.size else None, data.size, cnt.ctypes.data, out.data_ptr(),
+                                                         runtime.stream_ptr(device)))
+    return out

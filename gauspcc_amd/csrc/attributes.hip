@@ -2,6 +2,7 @@
 //   gsac_calculate_cdf   arithmetic.calculate_cdf      arithmetic.zip!arithmetic/arithmetic_kernel.cu:7-54
 //   gsac_encode/_decode  arithmetic.arithmetic_encode / arithmetic_decode   ...:94-232, 265-403
 //   gsac_*_gaussian*     the same without the CDF table: plain Gaussian or HAC++'s mixture, one stream or every slice of an attribute
+//   gsac_*_normal_*      TC-GS / CAT-3DGS's torchac files (TC-GS/utils/encodings.py:84-146): the slice form with chunk = slice, Normal.cdf's entries
 // (the hash-grid encoder is gridencoder.hip, the context MLP mlp2.hip)
 // Same byte format as the reference's CUDA coder (chunks of `chunk_size` symbols, per-chunk byte
 // counts), same integerisation of the float CDF rows (rint(cdf * (65536 - (Lp-1))) + index).
@@ -42,12 +43,41 @@ __global__ __launch_bounds__(TB) void k_gaussian_cdf(const float *__restrict__ m
     lower[t] = gaussian_cdf_entry(mean[idx], scale[idx], Q[idx], min_value, (int)(t - idx * lp));
 }
 
+// lower[idx][j] of TC-GS / CAT-3DGS's encoder_gaussian (TC-GS/utils/encodings.py:92-99):
+//     Normal(mean, scale).cdf((samples - 0.5) * Q),   samples = arange(min, max + 2).to(float)
+// torch.distributions.Normal.cdf is 0.5 * (1 + erf((value - loc) * scale.reciprocal() / sqrt(2))).  ONE definition, as gaussian_cdf_entry above: the
+// table kernel, the encoder's pre-pass and the decoder's windows all call it.  The float32 steps, in the order torch's device kernels take them (every one
+// rounded on its own: the intrinsics below are never contracted into a fused multiply-add):
+//   1  sample = (float(min + j) - 0.5f) * Q         the caller's `samples - 0.5` (exact) and its product with Q
+//   2  d      = sample - mean                       the subtraction
+//   3  r      = 1.0f / scale                        Tensor.reciprocal: a correctly rounded division
+//   4  t      = d * r                               the product
+//   5  u      = t * (1.0f / float(sqrt(2.0)))       ATen divides a device tensor by a host scalar as a product with the scalar's reciprocal
+//                                                   (BinaryDivTrueKernel.cu: `inv_b = accscalar_t(1.0) / b`, accscalar_t = float): 0x3F3504F3
+//   6  e      = erff(u)                             the device library's erff, the function torch's erf kernel calls
+//   7  a      = 1.0f + e                            the add
+//   8  entry  = 0.5f * a                            the halving (exact)
+// No clamp on scale: TC-GS clamps to 1e-9 before the call, as its callers here do.
+__device__ __forceinline__ float normal_cdf_entry(float mean, float scale, float q, int min_value, int j)
+{
+    const float inv_sqrt2 = __fdiv_rn(1.0f, (float)1.4142135623730951);
+    const float sample = __fmul_rn(__fsub_rn((float)(min_value + j), 0.5f), q);
+    const float d = __fsub_rn(sample, mean);
+    const float r = __fdiv_rn(1.0f, scale);
+    const float t = __fmul_rn(d, r);
+    const float u = __fmul_rn(t, inv_sqrt2);
+    return __fmul_rn(0.5f, __fadd_rn(1.0f, erff(u)));
+}
+
 // Row sources of the coder: a float table row, a uint16 table row (torchac's *_int16_normalized_cdf), or the Gaussian
 // parameters of the element -- the table-free path of encoder_gaussian / decoder_gaussian (the reference writes and
 // re-reads n x (max - min + 2) floats per slice; here the two entries an encoded symbol needs, or the <= 64 entries a
 // decoding wave compares, are evaluated in registers).
 struct GaussTable { const float *mean, *scale, *q; int min_value; };
 struct GaussRow { float mean, scale, q; int min_value; };
+// the same parameters under TC-GS / CAT-3DGS's entry formula (normal_cdf_entry above)
+struct NormalTable { const float *mean, *scale, *q; int min_value; };
+struct NormalRow { float mean, scale, q; int min_value; };
 // HAC++'s mixture (HAC-plus/utils/encodings_cuda.py:205-225, 285-299): lower = clamp(sum_i calculate_cdf(mean_i, scale_i, Q) *
 // prob_i, 0, 1), the components added in list order in fp32 (a product, then a sum: no fused multiply-add)
 constexpr int MIX_MAX = 4;
@@ -60,11 +90,13 @@ struct ConstRow { float c0, c1, c2, c3; };
 template <typename CT> struct RowOf { typedef const CT *type; };
 template <> struct RowOf<ConstTable> { typedef ConstRow type; };
 template <> struct RowOf<GaussTable> { typedef GaussRow type; };
+template <> struct RowOf<NormalTable> { typedef NormalRow type; };
 template <> struct RowOf<MixTable> { typedef MixRow type; };
 __device__ __forceinline__ const float *row_of(const float *t, int64_t idx, int lp) { return t + idx * lp; }
 __device__ __forceinline__ const uint16_t *row_of(const uint16_t *t, int64_t idx, int lp) { return t + idx * lp; }
 __device__ __forceinline__ ConstRow row_of(const ConstTable &t, int64_t, int) { return ConstRow{t.c[0], t.c[1], t.c[2], t.c[3]}; }
 __device__ __forceinline__ GaussRow row_of(const GaussTable &t, int64_t idx, int) { return GaussRow{t.mean[idx], t.scale[idx], t.q[idx], t.min_value}; }
+__device__ __forceinline__ NormalRow row_of(const NormalTable &t, int64_t idx, int) { return NormalRow{t.mean[idx], t.scale[idx], t.q[idx], t.min_value}; }
 __device__ __forceinline__ MixRow row_of(const MixTable &t, int64_t idx, int)
 {
     MixRow r;
@@ -105,6 +137,10 @@ __device__ __forceinline__ uint32_t cdf_int(const ConstRow &row, int m, float sc
 __device__ __forceinline__ uint32_t cdf_int(const GaussRow &row, int m, float scale)
 {
     return (uint32_t)((int)__builtin_rintf(gaussian_cdf_entry(row.mean, row.scale, row.q, row.min_value, m) * scale) + m);
+}
+__device__ __forceinline__ uint32_t cdf_int(const NormalRow &row, int m, float scale)
+{
+    return (uint32_t)((int)__builtin_rintf(normal_cdf_entry(row.mean, row.scale, row.q, row.min_value, m) * scale) + m);
 }
 __device__ __forceinline__ uint32_t cdf_int(const MixRow &row, int m, float scale) { return (uint32_t)((int)__builtin_rintf(mix_cdf_entry(row, m) * scale) + m); }
 
@@ -191,21 +227,24 @@ template <typename CT> struct RowLoader {
     template <typename R> __device__ __forceinline__ static int centre(const R &, int max_symbol) { return max_symbol / 2; }
     template <typename R> __device__ __forceinline__ static int estimate(const R &, float p, int max_symbol) { return (int)(p * (float)max_symbol); }
 };
-template <> struct RowLoader<GaussTable> {
-    __device__ __forceinline__ static GaussRow load(const GaussTable &t, int64_t idx, int lp) { return row_of(t, idx, lp); }
-    __device__ __forceinline__ static GaussRow get(const GaussTable &, const GaussRow &mine, int64_t, int, int u)
+// (GaussTable / GaussRow, and NormalTable / NormalRow: the same three parameters per element)
+template <typename T, typename R> struct ParamRowLoader {
+    __device__ __forceinline__ static R load(const T &t, int64_t idx, int lp) { return row_of(t, idx, lp); }
+    __device__ __forceinline__ static R get(const T &, const R &mine, int64_t, int, int u)
     {
-        return GaussRow{__shfl(mine.mean, u), __shfl(mine.scale, u), __shfl(mine.q, u), mine.min_value};
+        return R{__shfl(mine.mean, u), __shfl(mine.scale, u), __shfl(mine.q, u), mine.min_value};
     }
     // index of the symbol nearest the mean: where a window of 64 candidates is put when the alphabet is wider than a wave
-    __device__ __forceinline__ static int centre(const GaussRow &r, int) { return (int)__builtin_rintf(r.mean / r.q) - r.min_value; }
+    __device__ __forceinline__ static int centre(const R &r, int) { return (int)__builtin_rintf(r.mean / r.q) - r.min_value; }
     // index whose CDF entry is about p: the Gaussian's quantile (an ESTIMATE: the window put around it is checked like any other)
-    __device__ __forceinline__ static int estimate(const GaussRow &r, float p, int)
+    __device__ __forceinline__ static int estimate(const R &r, float p, int)
     {
         const float z = normcdfinvf(fminf(fmaxf(p, 1e-7f), 1.0f - 1e-7f));
         return (int)__builtin_rintf((r.mean + fmaxf(r.scale, 1e-9f) * z) / r.q) - r.min_value;
     }
 };
+template <> struct RowLoader<GaussTable> : ParamRowLoader<GaussTable, GaussRow> {};
+template <> struct RowLoader<NormalTable> : ParamRowLoader<NormalTable, NormalRow> {};
 template <> struct RowLoader<MixTable> {
     __device__ __forceinline__ static MixRow load(const MixTable &t, int64_t idx, int lp) { return row_of(t, idx, lp); }
     __device__ __forceinline__ static MixRow get(const MixTable &, const MixRow &mine, int64_t, int, int u)
@@ -729,16 +768,41 @@ __global__ __launch_bounds__(TB) void k_hac_pack_slices(CT table, const int32_t 
 }
 }  // namespace
 
+// STREAM_MAX_SYMS: the longest slice of the stream form below (chunk = slice).  What depends on a chunk's length: RcChunk::n and SliceChunk::n
+// (32 bits), rc_scratch_stride (2 n + 47 in 32 bits), the chunk's byte count and offset (uint32) and WaveBits::rem (int32) -- all hold below 2^30 symbols.
+constexpr int64_t STREAM_MAX_SYMS = (int64_t)1 << 30;
+
+// streams: the slice form whose unit is ONE carry-less stream per slice (TC-GS / CAT-3DGS's torchac files).  chunk_size is ignored and set to the
+// longest slice, so every non-empty slice is one chunk: the packed-word buffer holds `longest` words per slice and the scratch stride is the longest
+// slice's.  A slice may be empty: it gets no chunk, min = max = 0 and a byte count of 0; cnt has ONE entry per slice.
 template <typename CT>
 static int encode_slices_impl(gpcc_ctx *ctx, const float *x, CT table, const float *Q, const int64_t *slice_start,
-                              int nslices, int chunk_size, float *min_out, float *max_out, CoderOut out, void *stream)
+                              int nslices, int chunk_size, float *min_out, float *max_out, CoderOut out, void *stream, bool streams = false)
 {
     if (!ctx || !x || !Q || !slice_start || !min_out || !max_out || out.null()) return fail(GPCC_ERR_ARG, "null argument");
-    if (nslices <= 0 || chunk_size <= 0) return fail(GPCC_ERR_ARG, "bad size");
+    if (nslices <= 0 || (!streams && chunk_size <= 0)) return fail(GPCC_ERR_ARG, "bad size");
     for (int s = 0; s < nslices; ++s)
-        if (slice_start[s + 1] <= slice_start[s]) return fail(GPCC_ERR_ARG, "slice %d is empty", s);
+        if (streams ? slice_start[s + 1] < slice_start[s] : slice_start[s + 1] <= slice_start[s]) return fail(GPCC_ERR_ARG, "slice %d is empty", s);
     if (slice_start[0] != 0) return fail(GPCC_ERR_ARG, "slices must start at element 0");
     const int64_t n = slice_start[nslices];
+    if (streams) {
+        int64_t longest = 1;
+        for (int s = 0; s < nslices; ++s) longest = std::max(longest, slice_start[s + 1] - slice_start[s]);
+        if (longest >= STREAM_MAX_SYMS) return fail(GPCC_ERR_ARG, "a stream of %lld symbols (at most 2^30 - 1)", (long long)longest);
+        if (nslices > 65535) return fail(GPCC_ERR_ARG, "%d streams in one call (at most 65535: a grid row per slice): split the call", nslices);
+        // the payload's offsets are uint32 (exclusive_scan_u32, RcChunk): a call whose streams could exceed 4 GiB is split by the caller
+        // (gauspcc_amd.torchac_encodings.encoder_gaussian_slices cuts the slice list); 3 000 streams of 50 000 symbols are bounded by 0.3 GB
+        if ((uint64_t)nslices * rc_scratch_stride((uint32_t)longest) >= ((uint64_t)1 << 32))
+            return fail(GPCC_ERR_ARG, "%d streams of up to %lld symbols may exceed 4 GiB: split the call", nslices, (long long)longest);
+        chunk_size = (int)longest;
+        if (n == 0) {   // nothing but empty slices
+            ctx->stream_cnt.assign((size_t)nslices, 0);
+            for (int s = 0; s < nslices; ++s) min_out[s] = max_out[s] = 0.0f;
+            GP_TRY(ctx->hbytes.reserve(16));
+            *out.bytes = ctx->hbytes.p; *out.nbytes = 0; *out.cnt = ctx->stream_cnt.data(); *out.nchunks = nslices;
+            return GPCC_OK;
+        }
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     // chunk descriptors: slice by slice, the chunks of a slice interleaved among themselves
@@ -767,7 +831,10 @@ static int encode_slices_impl(gpcc_ctx *ctx, const float *x, CT table, const flo
     TAKE(lohi, uint32_t, slots); TAKE(dch, RcChunk, nch); TAKE(dcnt, uint32_t, nch + 1); TAKE(doff, uint32_t, nch + 1);
     TAKE(scratch, uint8_t, (size_t)nch * sstride); TAKE(payload, uint8_t, (size_t)nch * sstride);
     std::vector<int32_t> init((size_t)2 * nslices);
-    for (int s = 0; s < nslices; ++s) { init[(size_t)2 * s] = INT32_MAX; init[(size_t)2 * s + 1] = INT32_MIN; }
+    for (int s = 0; s < nslices; ++s) {
+        const bool empty = slice_start[s + 1] == slice_start[s];    // (stream form only) no element touches the pair: min = max = 0
+        init[(size_t)2 * s] = empty ? 0 : INT32_MAX; init[(size_t)2 * s + 1] = empty ? 0 : INT32_MIN;
+    }
     HIP_TRY(hipMemcpyAsync(mm, init.data(), 8 * (size_t)nslices, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dstart, slice_start, 8 * ((size_t)nslices + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dlbase, lbase.data(), 8 * (size_t)nslices, hipMemcpyHostToDevice, st));
@@ -778,7 +845,14 @@ static int encode_slices_impl(gpcc_ctx *ctx, const float *x, CT table, const flo
     LAUNCH_CHECK();
     k_hac_pack_slices<CT><<<(unsigned)cdiv(n, TB), TB, 0, st>>>(table, xi, n, dstart, nslices, mm, dlbase, dsnch, chunk_size, lohi);
     LAUNCH_CHECK();
-    return encode_tail(ctx, st, lohi, dch, nch, scratch, sstride, dcnt, doff, payload, out, mm, nslices, min_out, max_out);
+    if (!streams) return encode_tail(ctx, st, lohi, dch, nch, scratch, sstride, dcnt, doff, payload, out, mm, nslices, min_out, max_out);
+    // the tail counts the chunks, that is the non-empty slices; one count per SLICE goes into a buffer of the context's own
+    GP_TRY(encode_tail(ctx, st, lohi, dch, nch, scratch, sstride, dcnt, doff, payload, out, mm, nslices, min_out, max_out));
+    const int32_t *per_chunk = *out.cnt;
+    ctx->stream_cnt.resize((size_t)nslices);
+    for (int s = 0, c = 0; s < nslices; ++s) ctx->stream_cnt[(size_t)s] = slice_start[s + 1] > slice_start[s] ? per_chunk[c++] : 0;
+    *out.cnt = ctx->stream_cnt.data(); *out.nchunks = nslices;
+    return GPCC_OK;
 }
 
 extern "C" int gsac_encode_gaussian_slices(gpcc_ctx *ctx, const float *x, const float *mean, const float *scale, const float *Q, const int64_t *slice_start,
@@ -802,10 +876,11 @@ extern "C" int gsac_encode_gaussian_mixed_slices(gpcc_ctx *ctx, const float *x, 
 template <typename CT>
 static int decode_slices_impl(gpcc_ctx *ctx, CT table, const float *Q, const int64_t *slice_start, int nslices,
                               const float *min_value, const float *max_value, const uint8_t *bytes, int64_t nbytes, const int32_t *cnt,
-                              int chunk_size, float *x_out, void *stream)
+                              int chunk_size, float *x_out, void *stream, bool streams = false)
 {
-    if (!ctx || !Q || !slice_start || !min_value || !max_value || !bytes || !cnt || !x_out) return fail(GPCC_ERR_ARG, "null argument");
-    if (nslices <= 0 || chunk_size <= 0 || slice_start[0] != 0) return fail(GPCC_ERR_ARG, "bad size");
+    // (streams: one chunk per slice whatever its length, ONE count per slice, empty slices allowed -- see encode_slices_impl; the bytes may be empty)
+    if (!ctx || !Q || !slice_start || !min_value || !max_value || (!bytes && !(streams && nbytes == 0)) || !cnt || !x_out) return fail(GPCC_ERR_ARG, "null argument");
+    if (nslices <= 0 || (!streams && chunk_size <= 0) || slice_start[0] != 0 || nbytes < 0) return fail(GPCC_ERR_ARG, "bad size");
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     std::vector<SliceChunk> chunks;
@@ -813,6 +888,18 @@ static int decode_slices_impl(gpcc_ctx *ctx, CT table, const float *Q, const int
     uint64_t off = 0;
     for (int s = 0; s < nslices; ++s) {
         const int64_t len = slice_start[s + 1] - slice_start[s];
+        if (streams) {
+            if (len < 0 || len >= STREAM_MAX_SYMS) return fail(GPCC_ERR_ARG, "slice %d: %lld symbols", s, (long long)len);
+            if (cnt[s] < 0) return fail(GPCC_ERR_FORMAT, "negative stream size");
+            smin[(size_t)s] = 0; slp[(size_t)s] = 2;
+            if (len > 0) {
+                if (symbol_range(min_value[s], max_value[s], &smin[(size_t)s], &slp[(size_t)s]) != GPCC_OK) return fail(GPCC_ERR_FORMAT, "slice %d: bad symbol range", s);
+                chunks.push_back(SliceChunk{slice_start[s], (int32_t)len, s, (uint32_t)off, (uint32_t)cnt[s]});
+            }
+            off += (uint32_t)cnt[s];
+            if ((int64_t)off > nbytes || off >= ((uint64_t)1 << 32)) return fail(GPCC_ERR_FORMAT, "stream sizes exceed the byte stream");
+            continue;
+        }
         if (len <= 0) return fail(GPCC_ERR_ARG, "slice %d is empty", s);
         if (symbol_range(min_value[s], max_value[s], &smin[(size_t)s], &slp[(size_t)s]) != GPCC_OK) return fail(GPCC_ERR_FORMAT, "slice %d: bad symbol range", s);
         const int nch = (int)cdiv(len, chunk_size);
@@ -826,10 +913,11 @@ static int decode_slices_impl(gpcc_ctx *ctx, CT table, const float *Q, const int
         }
     }
     const size_t nch = chunks.size();
+    if (nch == 0) return GPCC_OK;   // (stream form: nothing but empty slices)
     GP_TRY(ctx->arena.reserve((size_t)nbytes + sizeof(SliceChunk) * nch + 8 * (size_t)nslices + ((size_t)4 << 20)));
     ctx->arena.reset();
     TAKE(db, uint8_t, nbytes + 16); TAKE(dch, SliceChunk, nch); TAKE(dmin, int32_t, nslices); TAKE(dlp, int32_t, nslices);
-    HIP_TRY(hipMemcpyAsync(db, bytes, (size_t)nbytes, hipMemcpyHostToDevice, st));
+    if (nbytes) HIP_TRY(hipMemcpyAsync(db, bytes, (size_t)nbytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dch, chunks.data(), sizeof(SliceChunk) * nch, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dmin, smin.data(), 4 * (size_t)nslices, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dlp, slp.data(), 4 * (size_t)nslices, hipMemcpyHostToDevice, st));
@@ -855,4 +943,77 @@ extern "C" int gsac_decode_gaussian_mixed_slices(gpcc_ctx *ctx, const float *con
     MixTable t;
     GP_TRY(mix_table(mean, scale, prob, k, Q, 0, &t));
     return decode_slices_impl(ctx, t, Q, slice_start, nslices, min_value, max_value, bytes, nbytes, cnt, chunk_size, x_out, stream);
+}
+
+// ------------------------------------------------------------------ TC-GS / CAT-3DGS: one torchac stream per slice, no table
+namespace {
+// the integer rows themselves: torchac's _convert_to_int_and_normalize of the float table, all lp entries (the coder never reads the last one)
+__global__ __launch_bounds__(TB) void k_normal_rows(NormalTable t, int64_t n, int lp, uint16_t *__restrict__ rows)
+{
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n * lp) return;
+    const int64_t idx = i / lp;
+    rows[i] = (uint16_t)cdf_int(row_of(t, idx, lp), (int)(i - idx * lp), (float)(65536 - (lp - 1)));
+}
+// parameters no Normal takes: bit 0 a mean that is not finite, bit 1 a scale that is not finite or not positive, bit 2 a step that is not finite or zero
+__global__ __launch_bounds__(TB) void k_normal_check(NormalTable t, int64_t n, uint32_t *__restrict__ flags)
+{
+    uint32_t f = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+        const float m = t.mean[i], s = t.scale[i], q = t.q[i];
+        f |= (isfinite(m) ? 0u : 1u) | (isfinite(s) && s > 0.0f ? 0u : 2u) | (isfinite(q) && q != 0.0f ? 0u : 4u);
+    }
+    if (f) atomicOr(flags, f);
+}
+}  // namespace
+
+extern "C" int gsac_normal_cdf_rows(gpcc_ctx *ctx, const float *mean, const float *scale, const float *Q, int64_t n, int min_value, int max_value,
+                                    uint16_t *rows, void *stream)
+{
+    if (!ctx || !mean || !scale || !Q || !rows) return fail(GPCC_ERR_ARG, "null argument");
+    const int64_t lp = (int64_t)max_value - min_value + 2;
+    if (n < 0 || lp < 2 || lp > 32767) return fail(GPCC_ERR_ARG, "bad size");
+    if (n == 0) return GPCC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    k_normal_rows<<<(unsigned)cdiv(n * lp, TB), TB, 0, (hipStream_t)stream>>>(NormalTable{mean, scale, Q, min_value}, n, (int)lp, rows);
+    LAUNCH_CHECK();
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return GPCC_OK;
+}
+
+extern "C" int gsac_encode_normal_streams(gpcc_ctx *ctx, const float *x, const float *mean, const float *scale, const float *Q, const int64_t *slice_start,
+                                          int nslices, float *min_out, float *max_out, const uint8_t **bytes_out, int64_t *nbytes_out,
+                                          const int32_t **cnt_out, void *stream)
+{
+    if (!ctx || !mean || !scale || !Q || !slice_start || !cnt_out) return fail(GPCC_ERR_ARG, "null argument");
+    if (nslices <= 0 || slice_start[0] != 0 || slice_start[nslices] < 0) return fail(GPCC_ERR_ARG, "bad size");
+    const int64_t n = slice_start[nslices];
+    const NormalTable t{mean, scale, Q, 0};
+    if (n > 0) {
+        // the entry function divides by scale and the quantiser by Q: what they cannot take is refused here, before any kernel computes with it
+        HIP_TRY(hipSetDevice(ctx->device));
+        hipStream_t st = (hipStream_t)stream;
+        GP_TRY(ctx->arena.reserve((size_t)4 << 20));
+        ctx->arena.reset();
+        TAKE(dflags, uint32_t, 1);
+        GP_TRY(ctx->hstage.reserve(64));
+        uint32_t *hflags = reinterpret_cast<uint32_t *>(ctx->hstage.p);
+        HIP_TRY(hipMemsetAsync(dflags, 0, 4, st));
+        k_normal_check<<<(unsigned)std::min<int64_t>(cdiv(n, TB), 1024), TB, 0, st>>>(t, n, dflags);
+        LAUNCH_CHECK();
+        HIP_TRY(hipMemcpyAsync(hflags, dflags, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (*hflags) return fail(GPCC_ERR_ARG, "normal streams:%s%s%s", (*hflags & 1u) ? " a mean is not finite;" : "", (*hflags & 2u) ? " a scale is not finite or not positive;" : "",
+                                 (*hflags & 4u) ? " a step Q is not finite or zero;" : "");
+    }
+    int64_t nstreams = 0;
+    return encode_slices_impl(ctx, x, t, Q, slice_start, nslices, 0, min_out, max_out, CoderOut{bytes_out, nbytes_out, cnt_out, &nstreams}, stream, true);
+}
+
+extern "C" int gsac_decode_normal_streams(gpcc_ctx *ctx, const float *mean, const float *scale, const float *Q, const int64_t *slice_start, int nslices,
+                                          const float *min_value, const float *max_value, const uint8_t *bytes, int64_t nbytes, const int32_t *cnt,
+                                          float *x_out, void *stream)
+{
+    if (!mean || !scale) return fail(GPCC_ERR_ARG, "null argument");
+    return decode_slices_impl(ctx, NormalTable{mean, scale, Q, 0}, Q, slice_start, nslices, min_value, max_value, bytes, nbytes, cnt, 0, x_out, stream, true);
 }

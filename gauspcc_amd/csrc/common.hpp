@@ -228,6 +228,7 @@ struct gpcc_ctx {
     gpcc::HostBuf<uint8_t> hstage;  // pinned small staging (counts, flags, descriptors)
     gpcc::HostBuf<uint8_t> hcoder;  // pinned: what the host coder of the reference layout reads / writes (coder words, CDF rows, symbols; hostcoder.hpp)
     gpcc::HostBuf<uint8_t> hbatch;  // pinned staging of the batched calls (forest.hpp: per-scene tables); reserved once per call, before anything reads it asynchronously
+    std::vector<int32_t> stream_cnt;  // gsac_encode_normal_streams: one byte count per slice, written by the host after the call's last synchronisation
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // second stream of the codec: octree / tile-list work of the next step runs beside the convolutions of this one
     hipStream_t side = nullptr, xfer = nullptr;   // xfer: the container's host -> device copy of a decode, beside both

@@ -228,6 +228,113 @@ static int mlp2_mfma_launch(gpcc_ctx *ctx, const float *x, const float *w1, cons
     return GPCC_OK;
 }
 
+// ------------------------------------------------------------------ wide first layers: TC-GS's mlp_triplane, 603-100-175
+// (TC-GS/scene/gaussian_model.py: Linear(K * 3 * tri_feat_dim + 3, 2 * feat_dim) - ReLU - Linear(2 * feat_dim, (50 + 6 + 30) * 2 + 3).)  W1 is 100 x 603 floats,
+// 241 KB: it does not fit the CU's LDS, so the resident-weights layout above cannot be instantiated.  Here no weight is staged at all: both matrices stay in
+// L2 (311 KB together) and a wave reads its B operands from there, one dword per lane and k-step -- W1[16 t + e][4 kk + g] is the 16-byte piece of 16
+// consecutive rows -- while it carries FOUR 16-row tiles through the first layer at once (4 x 7 accumulator tiles, 112 registers), so a B operand fetched
+// once feeds four MFMAs and W1 crosses the L2 once per 64 rows.  The chain of every output is the specified one: the bias as the initial accumulator, then
+// MFMA kk covers k = 4 kk .. 4 kk + 3 in ascending order; k >= din, hidden units >= dh and rows >= n are supplied as zeros (fmaf(0, 0, acc) leaves acc
+// unchanged).  Loop bounds follow the layer's own din / dh / dout, so a narrower layer of the class does a narrower layer's work.  The hidden layer of one
+// row tile at a time goes through 6.5 KB of the wave's LDS to become the second layer's A operands.
+// What this form is not: k-slabs of W1 and of the input rows staged in LDS (a 100 x 64 slab of W1 double-buffered behind a block barrier per slab, the rows'
+// slabs beside it), which would turn the 16-byte pieces the x and W1 reads are now (16 rows 4 din bytes apart) into whole lines and let a second wave
+// per SIMD cover the loads.  That kernel has not been built or measured.  This one was chosen because it needs no barrier and no LDS for weights and
+// is the specified chain by construction; it leaves the pipe at 0.17 of its fp32 peak (27 TFLOP/s at 603-100-175: one wave per SIMD at 189 VGPRs +
+// 112 AGPRs waits on every k-step's L2 loads) and is 2.6 x slower than torch's GEMM on the same layer, so slab staging is the known next step.
+// Against the plain k_mlp2 it is faster on every shape measured (a million rows, profiles/r07_tcgs_codec.txt): 4.1 x at 603-100-175, 7.4 x at 300-100-175,
+// 6.3 x at 128-100-175, 5.8 x at 256-64-32, 2.6 x at 100-64-20, 4.3 x at 64-64-64 -- layers the resident-weights classes miss ran on k_mlp2 before.
+template <int DH, int DOUT>
+__global__ __launch_bounds__(256) void k_mlp2_mfma_wide(const float *__restrict__ x, const float *__restrict__ w1, const float *__restrict__ b1,
+                                                        const float *__restrict__ w2, const float *__restrict__ b2, int64_t n, int din, int dh, int dout,
+                                                        float slope, float *__restrict__ y)
+{
+    static_assert(DH % 4 == 0, "whole MFMA k-steps");
+    constexpr int RT = 4, NT1 = (DH + 15) / 16, NT2 = (DOUT + 15) / 16, PH = DH + 2;
+    __shared__ float hs_all[4][16 * PH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, e = lane & 15, g = lane >> 4;
+    float *hs = hs_all[wave];
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * RT);
+    if (row0 >= n) return;                                  // (no block barrier below: a wave that has no rows leaves)
+    f32x4m acc[RT][NT1];
+#pragma unroll
+    for (int t = 0; t < NT1; ++t) {
+        const float bias = 16 * t + e < dh ? b1[16 * t + e] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < RT; ++r) acc[r][t] = f32x4m{bias, bias, bias, bias};
+    }
+    const float *xr[RT];
+    bool rin[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        const int64_t row = row0 + 16 * r + e;
+        rin[r] = row < n;
+        xr[r] = x + (size_t)(rin[r] ? row : row0) * din;    // (a row past the end reads nothing: its operand is zero)
+    }
+    const int nkk = (din + 3) / 4;
+    for (int kk = 0; kk < nkk; ++kk) {
+        const int k = 4 * kk + g;
+        const bool kin = k < din;
+        float a[RT], bw[NT1];
+#pragma unroll
+        for (int r = 0; r < RT; ++r) a[r] = kin && rin[r] ? xr[r][k] : 0.0f;
+#pragma unroll
+        for (int t = 0; t < NT1; ++t) bw[t] = kin && 16 * t + e < dh ? w1[(size_t)(16 * t + e) * din + k] : 0.0f;
+#pragma unroll
+        for (int t = 0; t < NT1; ++t) {
+            if (16 * t >= dh) break;                        // (wave-uniform)
+#pragma unroll
+            for (int r = 0; r < RT; ++r) acc[r][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], bw[t], acc[r][t], 0, 0, 0);
+        }
+    }
+    const int nk2 = (dh + 3) / 4;
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        if (row0 + 16 * r >= n) break;                      // (wave-uniform)
+        // hidden = relu(...) of this row tile: lane (g, e) holds rows 4 g .. 4 g + 3 of unit 16 t + e; units >= dh are exact zeros
+#pragma unroll
+        for (int t = 0; t < NT1; ++t)
+            if (16 * t + e < DH) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { const float h = acc[r][t][i]; hs[(4 * g + i) * PH + 16 * t + e] = h > 0.0f ? h : (slope != 0.0f ? h * slope : 0.0f); }
+            }
+        __builtin_amdgcn_wave_barrier();
+        float a2[DH / 4];
+#pragma unroll
+        for (int kk = 0; kk < DH / 4; ++kk) a2[kk] = hs[e * PH + 4 * kk + g];
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+        for (int t = 0; t < NT2; ++t) {
+            if (16 * t >= dout) break;                      // (wave-uniform)
+            const int c = 16 * t + e;
+            const bool cin = c < dout;
+            const float bias = cin ? b2[c] : 0.0f;
+            f32x4m o = {bias, bias, bias, bias};
+            const float *wr = w2 + (size_t)(cin ? c : 0) * dh;
+            float bw2[DH / 4];
+#pragma unroll
+            for (int kk = 0; kk < DH / 4; ++kk) bw2[kk] = cin && 4 * kk + g < dh ? wr[4 * kk + g] : 0.0f;
+#pragma unroll
+            for (int kk = 0; kk < DH / 4; ++kk)
+                if (kk < nk2) o = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[kk], bw2[kk], o, 0, 0, 0);
+            if (cin) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (row0 + 16 * r + 4 * g + i < n) y[(size_t)(row0 + 16 * r + 4 * g + i) * dout + c] = o[i];
+            }
+        }
+    }
+}
+
+template <int DH, int DOUT>
+static int mlp2_wide_launch(gpcc_ctx *, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, int64_t n, int din, int dh, int dout,
+                            float slope, float *y, hipStream_t st)
+{
+    k_mlp2_mfma_wide<DH, DOUT><<<(unsigned)cdiv(cdiv(n, 64), 4), 256, 0, st>>>(x, w1, b1, w2, b2, n, din, dh, dout, slope, y);
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
+
 // act: 0 = ReLU, 1 = LeakyReLU(slope) between the two layers
 extern "C" int gshac_mlp2_act(gpcc_ctx *ctx, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, int64_t n, int din, int dh,
                               int dout, int act, float slope, float *y, void *stream)
@@ -245,6 +352,8 @@ extern "C" int gshac_mlp2_act(gpcc_ctx *ctx, const float *x, const float *w1, co
         if (din == 96 && dh == 100 && dout == 175) return mlp2_mfma_launch<96, 100, 175>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
         if (din <= 192 && dh <= 40 && dout <= 32) return mlp2_mfma_launch<192, 40, 32>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
         if (din <= 48 && dh <= 100 && dout <= 240) return mlp2_mfma_launch<48, 100, 240>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
+        // TC-GS's mlp_triplane (603-100-175) and what else has a first layer too wide for the resident-weights classes
+        if (din <= 608 && dh <= 100 && dout <= 176) return mlp2_wide_launch<100, 176>(ctx, x, w1, b1, w2, b2, n, din, dh, dout, sl, y, st);
     }
     k_mlp2<<<(unsigned)cdiv(n, MLP_ROWS), TB, (size_t)MLP_ROWS * (size_t)(din + dh) * 4, st>>>(x, w1, b1, w2, b2, n, din, dh, dout, sl, y);
     LAUNCH_CHECK();

@@ -351,7 +351,9 @@ class SyntheticGaussianModelTC(SyntheticGaussianModel):
     """What TC-GS puts in place of the hash grid in the slice of GaussianModel its rate estimate touches
     (src/gs_compress/TC-GS/scene/gaussian_model.py:170-176, 322-323, 368, 1052-1059, 1084-1096): the `triplane` context sampler,
     `mlp_triplane` behind `get_tri_mlp` on [K * 3 * tri_feat_dim plane features | anchor], the bounds as flat (3,) tensors and
-    `knnanchor` (N, K, 3), each anchor with its K - 1 nearest anchors.  Seeded random planes and weights, as the base class."""
+    `knnanchor` (N, K, 3), each anchor with its K - 1 nearest anchors.  Seeded random planes and weights, as the base class.  For
+    conduct_encoding / conduct_decoding (:1135-1465; gauspcc_amd.tcgs_codec): `ste_binary` False, TC-GS's default, and
+    `get_encoding_params` returning `triplane.get_encode()` (:176-180)."""
 
     def __init__(self, n_anchors, seed=0, knn=4, tri_feat_dim=50, resolution=256, spatial_lr_scale=5.0, **kw):
         import torch
@@ -369,5 +371,9 @@ class SyntheticGaussianModelTC(SyntheticGaussianModel):
         self.mlp_triplane = nn.Sequential(nn.Linear(knn * 3 * tri_feat_dim + 3, F * 2), nn.ReLU(True), nn.Linear(F * 2, (F + 6 + 3 * K) * 2 + 3)).to(dev)
         self.knn_indices = kneighbors(self._anchor, knn)
         self.knnanchor = self._anchor[self.knn_indices].detach()
+        self.ste_binary = False                                       # TC-GS's default: the planes travel with the model, no hash.b
 
     get_tri_mlp = property(lambda self: self.mlp_triplane)
+
+    def get_encoding_params(self):
+        return self.triplane.get_encode()                             # (:176-180) what conduct_encoding counts as the planes' side information

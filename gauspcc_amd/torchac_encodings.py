@@ -132,6 +132,126 @@ def decoder_gaussian(mean, scale, Q, file_name='tmp.b', min_value=-100, max_valu
     return x * Q
 
 
+# ---------------------------------------------------------------- all slices of an attribute at once
+# limits of one gsac_encode_normal_streams call (include/gauspcc.h): slices per call, and count x (2 longest + 48) bytes below 4 GiB.  The call's
+# workspace is sized by count x LONGEST slice (4 bytes of packed words and twice 2 bytes of coder scratch per symbol slot), so many short slices beside
+# one long one reserve far more than their symbols: the split below keeps a call's workspace under 4 GiB whatever the mix of lengths
+_STREAMS_PER_CALL = 65535
+_STREAM_BYTES_PER_CALL = 1 << 30
+
+
+def _slice_groups(lens):
+    """Consecutive runs [a, b) of slices that one device call takes."""
+    groups, a, longest = [], 0, 0
+    for i, ln in enumerate(lens):
+        new_longest = max(longest, int(ln))
+        if i > a and ((i + 1 - a) > _STREAMS_PER_CALL or (i + 1 - a) * (2 * new_longest + 48) >= _STREAM_BYTES_PER_CALL):
+            groups.append((a, i))
+            a, new_longest = i, int(ln)
+        longest = new_longest
+    groups.append((a, len(lens)))
+    return groups
+
+
+def _slice_lens(slice_start, n):
+    ss = [int(v) for v in slice_start]
+    assert len(ss) >= 1 and ss[0] == 0 and ss[-1] == n and all(b >= a for a, b in zip(ss, ss[1:])), "slice_start: 0 = s[0] <= s[1] <= ... <= s[-1] = len(x)"
+    return ss, [b - a for a, b in zip(ss, ss[1:])]
+
+
+def encoder_gaussian_slices(x, mean, scale, Q, slice_start, file_names):
+    """encoder_gaussian for MANY slices of one attribute: slice s = elements [slice_start[s], slice_start[s + 1]) goes to file_names[s] as ONE raw
+    torchac stream with its own min / max, as TC-GS's loop writes it per 1 000-anchor slice (TC-GS/scene/gaussian_model.py:1197-1271).  Returns
+    (bit_lens, min_values, max_values): three lists with one entry per slice, the bounds as 0-d tensors (what the reference collects into
+    `patched_infos`).  A slice of length 0 writes an empty file and reports min = max = 0.
+
+    CUDA tensors: all slices are coded concurrently on the device (gsac_encode_normal_streams), CDF entries evaluated inside the coder, no table; the
+    files are written on native threads (inside `encodings_cuda.deferred_writes()` in the background).  CPU tensors: the per-file encoder_gaussian
+    above, slice by slice -- the same files as calling it yourself.
+
+    The pair encoder_gaussian_slices / decoder_gaussian_slices reads only its own files: on the device the table is the library's entry function
+    (csrc/attributes.hip: normal_cdf_entry, the float32 steps of `Normal.cdf` spelled out), which may differ from a torch-built table in rare entries
+    (tests/test_gpu_normal_streams.py prints the share) -- the reference's own files are tied to one `erf` implementation in the same way."""
+    assert len(x.shape) == 1
+    Q = _as_q(Q, mean)
+    assert x.shape == mean.shape == scale.shape == Q.shape
+    ss, lens = _slice_lens(slice_start, x.shape[0])
+    assert len(file_names) == len(lens) and all(f.endswith('.b') for f in file_names)
+    if not x.is_cuda:
+        bits, mins, maxs = [], [], []
+        for a, b, fn in zip(ss, ss[1:], file_names):
+            if b == a:
+                open(fn, 'wb').close()
+                bl, mn, mx = 0, torch.zeros((), dtype=x.dtype), torch.zeros((), dtype=x.dtype)
+            else:
+                bl, mn, mx = encoder_gaussian(x[a:b], mean[a:b], scale[a:b], Q[a:b], file_name=fn)
+            bits.append(bl); mins.append(mn); maxs.append(mx)
+        return bits, mins, maxs
+    import numpy as np
+
+    from . import arithmetic
+    from .encodings_cuda import _write_files
+    bits, mins, maxs, jobs = [], [], [], []
+    cont = lambda t, a, b: t[a:b].detach().contiguous()
+    for ga, gb in _slice_groups(lens):
+        a, b = ss[ga], ss[gb]
+        mn, mx, data, cnt = arithmetic.encode_normal_streams(cont(x, a, b), cont(mean, a, b), cont(scale, a, b), cont(Q, a, b), [v - a for v in ss[ga:gb + 1]])
+        off = np.concatenate([[0], np.cumsum(cnt, dtype=np.int64)])
+        blob = data.tobytes()
+        jobs += [(file_names[ga + i], blob[int(off[i]):int(off[i + 1])]) for i in range(gb - ga)]
+        bits += [int(c) * 8 for c in cnt]
+        mins.append(mn); maxs.append(mx)
+    _write_files(jobs)
+    as_list = lambda parts: list(torch.from_numpy(np.concatenate(parts)).to(x.device).unbind(0))
+    return bits, as_list(mins), as_list(maxs)
+
+
+def decoder_gaussian_slices(mean, scale, Q, slice_start, file_names, min_values, max_values):
+    """Inverse of encoder_gaussian_slices: the values of all slices, concatenated in slice order, on mean's device.  min_values / max_values: the
+    lists the encoder returned (tensors or numbers).  CUDA tensors: every stream is decoded by a wave of its own in one device call
+    (gsac_decode_normal_streams); CPU tensors: decoder_gaussian per file.  Reads only files of encoder_gaussian_slices (see there)."""
+    Q = _as_q(Q, mean)
+    assert len(mean.shape) == 1 and mean.shape == scale.shape == Q.shape
+    ss, lens = _slice_lens(slice_start, mean.shape[0])
+    assert len(file_names) == len(lens) == len(min_values) == len(max_values) and all(f.endswith('.b') for f in file_names)
+    if not mean.is_cuda:
+        parts = [decoder_gaussian(mean[a:b], scale[a:b], Q[a:b], file_name=fn, min_value=mn, max_value=mx)
+                 for a, b, fn, mn, mx in zip(ss, ss[1:], file_names, min_values, max_values) if b > a]
+        return torch.cat(parts, dim=0) if parts else torch.zeros(0, dtype=torch.float32)
+    import ctypes as C
+    import os
+
+    import numpy as np
+
+    from . import _lib, arithmetic
+
+    def host(vals):
+        if all(isinstance(v, torch.Tensor) for v in vals):
+            return torch.stack([v.detach().reshape(()) for v in vals]).to(torch.float32).cpu().numpy()
+        return np.array([float(v) for v in vals], dtype=np.float32)
+
+    mins, maxs = host(min_values), host(max_values)
+    n = len(file_names)
+    cp = (C.c_char_p * n)(*[os.fsencode(p) for p in file_names])
+    offs = (C.c_int64 * (n + 1))()
+    pb = C.c_void_p()
+    _lib.check(_lib.lib().gpcc_read_files(cp, n, 8, C.byref(pb), offs))         # one blob, valid until this thread's next call: decoded at once
+    offs = np.frombuffer(offs, dtype=np.int64)
+    blob = np.frombuffer((C.c_ubyte * max(int(offs[n]), 1)).from_address(pb.value), dtype=np.uint8)[:int(offs[n])]
+    cnt = np.diff(offs)
+    if cnt.size and int(cnt.max()) >= 1 << 31:
+        raise ValueError("decoder_gaussian_slices: a stream of 2 GiB or more")
+    cont = lambda t, a, b: t[a:b].detach().contiguous()
+    out = []
+    for ga, gb in _slice_groups(lens):
+        a, b = ss[ga], ss[gb]
+        if int(offs[gb] - offs[ga]) >= 1 << 32:
+            raise ValueError("decoder_gaussian_slices: the files of one device call exceed 4 GiB (not written by encoder_gaussian_slices)")
+        out.append(arithmetic.decode_normal_streams(cont(mean, a, b), cont(scale, a, b), cont(Q, a, b), [v - a for v in ss[ga:gb + 1]], mins[ga:gb], maxs[ga:gb],
+                                                    blob[int(offs[ga]):int(offs[gb])], cnt[ga:gb].astype(np.int32)))
+    return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+
+
 def _binary_cdf(p):
     p_u = 1 - p.unsqueeze(-1)
     return torch.cat([torch.zeros_like(p_u), p_u, torch.ones_like(p_u)], dim=-1)      # encodings.py:153-157

@@ -371,6 +371,34 @@ GPCC_API int gsac_decode_gaussian_mixed_slices(gpcc_ctx *ctx, const float *const
                                                const float *q_dev, const int64_t *slice_start, int nslices, const float *min_value, const float *max_value,
                                                const uint8_t *bytes, int64_t nbytes, const int32_t *cnt, int chunk_size, float *x_out_dev, void *stream);
 
+/* TC-GS / CAT-3DGS's attribute files: ONE torchac stream per file, no chunk table (TC-GS/utils/encodings.py:84-146; the loop that calls it per
+ * 1 000-anchor slice: TC-GS/scene/gaussian_model.py:1197-1271, 1358-1420).  The CDF row of element i is the reference's
+ *     lower[i][j] = Normal(mean[i], scale[i]).cdf((min + j - 0.5) * Q[i]),   j = 0 .. max - min + 1,
+ * 0.5 (1 + erf((v - mean) (1 / scale) / sqrt(2))) in float32 steps (csrc/attributes.hip: normal_cdf_entry) -- torch.distributions' formula, not the
+ * erfc form of arithmetic.calculate_cdf above -- integerised as torchac does: rint(entry * (65536 - (lp - 1))) + j; c_high of the last symbol is 2^16.
+ *   gsac_normal_cdf_rows        the integer rows (n, max - min + 2) uint16 on the device (tests; callers that want torchac's two-step form).
+ *   gsac_encode_normal_streams  every slice [slice_start[s], slice_start[s + 1]) (nslices + 1 host entries, slice_start[0] = 0) is quantised,
+ *       x_int = round(x / Q) (float32 division, ties to even), gets its own min / max, and is coded as ONE carry-less stream: the bytes of
+ *       gsac_host_encode_u16 on the slice's rows from gsac_normal_cdf_rows.  min_out / max_out (nslices, host); *cnt_out: nslices byte counts,
+ *       *bytes_out: the streams concatenated in slice order (context-owned host buffers, valid until the context's next call).  A slice of
+ *       length 0 gives an empty stream and min = max = 0.  No CDF table is built: an encoded symbol needs two entries, evaluated in registers.
+ *       GPCC_ERR_RANGE when a slice spans more than int16 symbols; GPCC_ERR_ARG when a mean is not finite, a scale not finite or not positive,
+ *       a Q not finite or zero (checked on the device before anything computes with them), or when the call must be split: at most 65 535 slices
+ *       whose count times (2 longest + 47) bytes stays below 4 GiB (byte offsets are 32 bits), a slice below 2^30 symbols.  Workspace: the
+ *       context's arena grows to about 8 bytes x (non-empty slices x LONGEST slice) + 4 bytes per symbol -- every stream gets the longest one's
+ *       slots -- so slices of very unequal lengths cost far more than their symbols; callers with such slices group them by length or split the call.
+ *   gsac_decode_normal_streams  the reverse, one wave per stream: x_out[i] = (sym + min) * Q[i].  bytes / cnt host, as the encoder returned them;
+ *       bytes past a stream's count read as zero and symbols stay inside the alphabet, so a short or foreign file gives some values, never a fault.
+ * mean / scale / Q / x device (n = slice_start[nslices]). */
+GPCC_API int gsac_normal_cdf_rows(gpcc_ctx *ctx, const float *mean_dev, const float *scale_dev, const float *q_dev, int64_t n, int min_value,
+                                  int max_value, uint16_t *rows_dev, void *stream);
+GPCC_API int gsac_encode_normal_streams(gpcc_ctx *ctx, const float *x_dev, const float *mean_dev, const float *scale_dev, const float *q_dev,
+                                        const int64_t *slice_start, int nslices, float *min_out, float *max_out, const uint8_t **bytes_out,
+                                        int64_t *nbytes_out, const int32_t **cnt_out, void *stream);
+GPCC_API int gsac_decode_normal_streams(gpcc_ctx *ctx, const float *mean_dev, const float *scale_dev, const float *q_dev, const int64_t *slice_start,
+                                        int nslices, const float *min_value, const float *max_value, const uint8_t *bytes, int64_t nbytes,
+                                        const int32_t *cnt, float *x_out_dev, void *stream);
+
 /* GaussianModel.mlp_grid = nn.Sequential(Linear(din, dh), ReLU, Linear(dh, dout)) (src/gs_compress/HAC/scene/gaussian_model.py:258-262,
  * called through get_grid_mlp at :1152-1153 and :1281-1282): y = W2 relu(W1 x + b1) + b2 for n rows.
  * w1 (dh, din), w2 (dout, dh) row-major as nn.Linear stores them; all pointers device.  Specified fp32 order
@@ -380,7 +408,9 @@ GPCC_API int gshac_mlp2(gpcc_ctx *ctx, const float *x_dev, const float *w1_dev, 
 /* The same with the activation as an argument: act 0 = ReLU, 1 = LeakyReLU(slope) -- HAC++'s channel-context MLPs
  * (Channel_CTX_fea.MLP_d0..4: Linear(150 + 10 c, 40) - LeakyReLU - Linear(40, 30), HAC-plus/scene/gaussian_model.py:117-168, called through
  * get_deform_mlp.forward(feat, mean_scale, to_dec=c) at :1306 and :1490): context MLPs too -- encoder and decoder must obtain the same
- * bits, hence the same specified fp32 order. */
+ * bits, hence the same specified fp32 order.  TC-GS's mlp_triplane (Linear(603, 100) - ReLU - Linear(100, 175), called through get_tri_mlp at
+ * TC-GS/scene/gaussian_model.py:1223 and :1386) and any layer with din <= 608, dh <= 100, dout <= 176 run on the matrix pipe as well, with the
+ * weights read from L2 (W1 alone is larger than a CU's LDS): the same chains, the same bits. */
 GPCC_API int gshac_mlp2_act(gpcc_ctx *ctx, const float *x_dev, const float *w1_dev, const float *b1_dev, const float *w2_dev, const float *b2_dev,
                             int64_t n, int din, int dh, int dout, int act, float slope, float *y_dev, void *stream);
 
