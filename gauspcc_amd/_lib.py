@@ -41,6 +41,13 @@ class Stage(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("bytes", C.c_double), ("brackets", C.c_int64), ("critical_ms", C.c_double)]
 
 
+class ChainStage(C.Structure):
+    """gsac_chain_stage (include/gauspcc.h): one stage of gsac_decode_normal_chain"""
+    _fields_ = [(k, C.c_int32) for k in ("ch", "dep_ch", "dh", "lag", "mean_col", "scale_col", "feat_col", "out_col", "out_pitch", "keep_group")] + \
+               [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "q_dev", "out_dev", "keep_dev", "bytes")] + \
+               [("nbytes", C.c_int64), ("cnt", C.c_void_p), ("min_value", C.c_void_p), ("max_value", C.c_void_p)]
+
+
 GSR_STATE_WORDS = 16                                       # include/gauspcc.h
 GPCC_TRAIN_STATE_WORDS = 256                               # include/gauspcc.h
 GSR_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)   # gsr_alloc_fn: device memory for the training paths (frame state, backward workspace)
@@ -59,7 +66,7 @@ EXPORTS = [
     "gsge_msplane_forward", "gsge_msplane_backward",
     "gshac_mlp2_backward", "gshac_mlp2_slab_rows",
     "gsac_arm_encode", "gsac_arm_decode", "gsac_arm_cdf_rows",
-    "gsac_normal_cdf_rows", "gsac_encode_normal_streams", "gsac_decode_normal_streams",
+    "gsac_normal_cdf_rows", "gsac_encode_normal_streams", "gsac_decode_normal_streams", "gsac_decode_normal_chain",
 ]
 # the tri-plane ARM's entry points: listed apart because tests/test_abi.py matches EXPORTS against the header with a pattern of the
 # prefixes above; tests/test_arm_ref_cpu.py checks these against the header and the library
@@ -184,6 +191,7 @@ def lib():
     L.gsac_normal_cdf_rows.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp]
     L.gsac_encode_normal_streams.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), vp]
     L.gsac_decode_normal_streams.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp]
+    L.gsac_decode_normal_chain.argtypes = [vp, C.POINTER(ChainStage), i32, vp, i32, i64, i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -377,3 +377,126 @@ class SyntheticGaussianModelTC(SyntheticGaussianModel):
 
     def get_encoding_params(self):
         return self.triplane.get_encode()                             # (:176-180) what conduct_encoding counts as the planes' side information
+
+
+class SyntheticGaussianModelCAT(SyntheticGaussianModel):
+    """What CAT-3DGS puts in place of the hash grid in the slice of GaussianModel its codec and rate estimate touch
+    (src/gs_compress/CAT-3DGS/scene/gaussian_model.py:178-232, 293-313, 1056-1616): `feature_net` (scene/attribute.py: `attribute_net.grid` a
+    TriPlaneField, `feature_out` + `net` = Linear(grid.feat_dim, 100) - ReLU - Linear(100, 175) at net_depth 0, called as
+    feature_net(anchor, itr=-1) -> (context, tri-plane rate)), the channel-context MLPs `mlp_chcm_list` (Linear(sum of the groups before, 2 F) -
+    ReLU - Linear(2 F, 2 ch_i)) and, with `chcm_for_scaling` / `chcm_for_offsets`, `mlp_chcm_scaling` / `mlp_chcm_offsets` on all F channels,
+    `chcm_slices_list`, `num_feat_slices`, `get_mlp_size`, `entropy_gaussian`, and `get_mask` / `get_mask_anchor` as METHODS that take
+    `weighted_mask`.  Seeded random planes (latents of a few quantiser steps) and weights, as the base class.  `scaling_spread`: the scaling
+    attribute is the context's mean_scaling (about exp(-1)) plus noise of that relative size (0.05: exp(-1) x 0.05 / Q_scaling ~ 17 levels of sigma,
+    alphabets wider than a wave); None keeps the base class's attribute."""
+
+    def __init__(self, n_anchors, seed=0, chcm_slices_list=(12, 12, 13, 13), chcm_for_scaling=False, chcm_for_offsets=False, n_offsets=10,
+                 resolution=32, tri_channels=72, multires=(1, 2), net_width=100, scaling_spread=None, **kw):
+        import torch
+        from . import entropy_models
+        from .cat_triplane import TriPlaneField
+
+        super().__init__(n_anchors, seed=seed, n_offsets=n_offsets, **kw)
+        nn = torch.nn
+        dev = self._anchor.device
+        F, K = self.feat_dim, self.n_offsets
+        self.chcm_slices_list = list(chcm_slices_list)
+        assert sum(self.chcm_slices_list) == F, "chcm_slices_list must add up to feat_dim"
+        self.num_feat_slices = len(self.chcm_slices_list)
+        self.chcm_for_scaling, self.chcm_for_offsets = bool(chcm_for_scaling), bool(chcm_for_offsets)
+        g = torch.Generator(device="cpu").manual_seed(seed + 2000)
+        torch.manual_seed(seed + 3)
+        final_dim = (F + 6 + 3 * K) * 2 + 3
+
+        class Attribute(nn.Module):
+            def __init__(self):
+                super().__init__()
+                config = {"grid_dimensions": 2, "input_coordinate_dim": 3, "output_coordinate_dim": tri_channels, "resolution": [resolution] * 3}
+                self.grid = TriPlaneField(1.0, config, list(multires), False, 0, device=dev)
+                self.feature_out = nn.Sequential(nn.Linear(self.grid.feat_dim, net_width))
+                self.net = nn.Sequential(nn.ReLU(), nn.Linear(net_width, final_dim))
+
+            def forward(self, pts, itr=-1):
+                feat, rate = self.grid(pts, itr=itr)
+                return self.net(self.feature_out(feat)), rate
+
+            def get_mlp_parameters(self):
+                return [p for n, p in self.named_parameters() if "grid" not in n]
+
+        class AttributeNetwork(nn.Module):
+            def __init__(self):
+                super().__init__()
+                self.attribute_net = Attribute()
+
+            def forward(self, point, scales=None, rotations=None, opacity=None, times_sel=None, itr=-1):
+                return self.attribute_net(point, itr=itr)
+
+            def get_mlp_parameters(self):
+                return self.attribute_net.get_mlp_parameters()
+
+        self.feature_net = AttributeNetwork().to(dev)
+        grid = self.feature_net.attribute_net.grid
+        for level in grid.grids:
+            for p in level:
+                p.data = (torch.randn(p.shape, generator=g) * 0.15).to(dev)
+        grid.set_aabb(self._anchor, self.x_bound_max.reshape(3), self.x_bound_min.reshape(3))
+        for m in self.feature_net.modules():
+            if isinstance(m, nn.Linear):                         # attribute.py:105-109 leaves the biases at nn.Linear's initialiser
+                nn.init.xavier_uniform_(m.weight, gain=1)
+        self.mlp_chcm_list = nn.ModuleList()
+        din = 0
+        for i in range(self.num_feat_slices - 1):
+            din += self.chcm_slices_list[i]
+            self.mlp_chcm_list.append(nn.Sequential(nn.Linear(din, 2 * F), nn.ReLU(True), nn.Linear(2 * F, 2 * self.chcm_slices_list[i + 1])))
+        self.mlp_chcm_list.to(dev)
+        if self.chcm_for_offsets:
+            self.mlp_chcm_offsets = nn.Sequential(nn.Linear(F, 2 * F), nn.ReLU(True), nn.Linear(2 * F, 6 * K)).to(dev)
+        if self.chcm_for_scaling:
+            self.mlp_chcm_scaling = nn.Sequential(nn.Linear(F, 2 * F), nn.ReLU(True), nn.Linear(2 * F, 12)).to(dev)
+        # The head's scale outputs are the BASE scales of the chain, and mean_scaling is where the (positive) scaling attribute lies: these rows get
+        # non-negative weights, |w| rescaled so that the row's mean output over this model's anchors is the target, and no bias -- the value comes
+        # from the products, as in a trained head, not from a bias that the products merely perturb.
+        with torch.no_grad():
+            net = self.feature_net.attribute_net
+            last = net.net[1]
+            last.bias.zero_()
+            anchors = self.get_anchor
+            hidden = torch.relu(net.feature_out(net.grid(anchors, itr=-1)[0]))
+            hbar = hidden.mean(dim=0)
+            centre = float(torch.exp(self._scaling).mean()) if scaling_spread is None else float(np.exp(-1.0))
+            width = float(torch.exp(self._scaling).std()) if scaling_spread is None else float(scaling_spread) * centre
+            for rows, target in ((slice(0, F), 0.8), (slice(2 * F, 2 * F + 6), centre), (slice(2 * F + 6, 2 * F + 12), width),
+                                 (slice(2 * F + 12 + 3 * K, 2 * F + 12 + 6 * K), 0.3)):
+                w = last.weight[rows].abs()
+                last.weight[rows] = w * (target / (w @ hbar)).unsqueeze(1)
+            if scaling_spread is not None:       # the scaling attribute scatters around the context's own prediction: `scaling_spread` of its size
+                mean_scaling = last(hidden)[:, 2 * F:2 * F + 6]
+                noise = torch.randn(mean_scaling.shape, generator=g).to(dev) * width
+                self._scaling = torch.log(torch.clamp(mean_scaling + noise, min=1e-3))
+            for m in list(self.mlp_chcm_list) + [getattr(self, "mlp_chcm_scaling", None), getattr(self, "mlp_chcm_offsets", None)]:
+                if m is not None:
+                    m[2].weight.mul_(0.1); m[2].bias.mul_(0.1)
+            if self.chcm_for_scaling:
+                self.mlp_chcm_scaling[2].weight.mul_(0.05); self.mlp_chcm_scaling[2].bias.mul_(0.05)
+        self.entropy_gaussian = entropy_models.Entropy_gaussian(Q=1)
+
+    def get_mask(self, weighted_mask=None):
+        import torch
+        if self.decoded_version:
+            return self._mask
+        s = torch.sigmoid(self._mask)
+        if weighted_mask is not None:
+            s = s * weighted_mask
+        return ((s > 0.01).float() - s).detach() + s
+
+    def get_mask_anchor(self, weighted_mask=None):
+        import torch
+        with torch.no_grad():
+            return (torch.sum(self.get_mask(weighted_mask), dim=1)[:, 0]) > 0
+
+    def get_mlp_size(self, digit=32):
+        grid = self.feature_net.attribute_net.grid
+        mods = [self.mlp_opacity, self.mlp_cov, self.mlp_color, grid.arm, grid.arm2, grid.arm3, self.mlp_chcm_list]
+        mods += [getattr(self, n) for n in ("mlp_chcm_offsets", "mlp_chcm_scaling") if hasattr(self, n)]
+        total = sum(p.numel() for m in mods for p in m.parameters()) + sum(p.numel() for p in self.feature_net.get_mlp_parameters())
+        return total * digit, total * digit / 8 / 1024 / 1024

@@ -399,6 +399,41 @@ GPCC_API int gsac_decode_normal_streams(gpcc_ctx *ctx, const float *mean_dev, co
                                         int nslices, const float *min_value, const float *max_value, const uint8_t *bytes, int64_t nbytes,
                                         const int32_t *cnt, float *x_out_dev, void *stream);
 
+/* CAT-3DGS's channel-wise context chain (CAT-3DGS/scene/gaussian_model.py:1451-1552): the attribute streams of a slice of anchors depend on one
+ * another PER ANCHOR -- feat group i is coded under mean_i + dmean, clamp(scale_i + dscale, 1e-9) with (dmean | dscale) =
+ * Linear(dep_ch, dh) - ReLU - Linear(dh, 2 ch) of the channels [0, dep_ch) already decoded, and scaling / offsets may depend the same way on all
+ * of feat.  gsac_decode_normal_chain decodes every stage of every slice in ONE launch: a workgroup per slice, a wave per stage, the slice's anchors
+ * in blocks of block_anchors; in step t the wave of stage k works on block t - lag, so what its MLP reads was decoded in an earlier step (waves meet
+ * at one workgroup barrier per step; nblocks + max lag steps).  The files are gsac_encode_normal_streams' (one stream per stage and slice), the rows
+ * normal_cdf_entry's, the MLP gshac_mlp2's specified fp32 order (bias, then fmaf over k ascending; ReLU x > 0 ? x : 0), mean = ctx + dmean one
+ * rounded add, scale = fmaxf(ctx + dscale, 1e-9f): the values equal those of gshac_mlp2 + gsac_decode_normal_streams run stage after stage.
+ * One record per stage (at most 8): */
+typedef struct {
+    int32_t ch;                    /* symbols per anchor, 1..64 */
+    int32_t dep_ch;                /* the MLP reads the decoded feat channels [0, dep_ch), <= 64; 0: no MLP (w1..b2 NULL) */
+    int32_t dh;                    /* hidden units, <= 128 */
+    int32_t lag;                   /* 0 without an MLP; otherwise larger than the lag of every stage that publishes a channel below dep_ch */
+    int32_t mean_col, scale_col;   /* first columns of the stage's base mean / scale in a row of ctx_dev */
+    int32_t feat_col;              /* >= 0: a feat stage, its values are channels [feat_col, feat_col + ch) for the later stages' MLPs; -1 otherwise */
+    int32_t out_col, out_pitch;    /* the stage writes out_dev[a * out_pitch + out_col + c], a = 0 .. n - 1, c = 0 .. ch - 1 */
+    int32_t keep_group;            /* with keep_dev: element c of anchor a is coded when keep_dev[a * (ch / keep_group) + c / keep_group] != 0 (offsets: 3);
+                                      the others are written as 0 and take no symbol */
+    const float *w1, *b1, *w2, *b2;   /* device: (dh, dep_ch), (dh), (2 ch, dh), (2 ch) row-major as nn.Linear stores them */
+    const float *q_dev;            /* (n) the step size of every anchor, computed by the caller with the encoder's expression */
+    float *out_dev;
+    const uint8_t *keep_dev;       /* or NULL */
+    const uint8_t *bytes;          /* host: the stage's streams, slice after slice */
+    int64_t nbytes;
+    const int32_t *cnt;            /* host (nslices): byte count of every stream */
+    const float *min_value, *max_value;   /* host (nslices) */
+} gsac_chain_stage;
+/* ctx_dev (n, ctx_pitch) device; slice s holds the anchors [s * slice_anchors, min(n, (s + 1) * slice_anchors)), nslices = ceil(n / slice_anchors);
+ * block_anchors 0 = the default, 1..64 otherwise.  GPCC_ERR_ARG outside the class (more than 8 stages, dh > 128, ch or dep_ch > 64, lags that
+ * let a stage read what is not yet decoded); GPCC_ERR_FORMAT for a min / max no stream can have or counts beyond nbytes.  Bytes past a stream's
+ * count read as zero and symbols stay inside the alphabet: a short or foreign file gives some finite values, never a fault. */
+GPCC_API int gsac_decode_normal_chain(gpcc_ctx *ctx, const gsac_chain_stage *stages, int nstages, const float *ctx_dev, int ctx_pitch, int64_t n,
+                                      int slice_anchors, int nslices, int block_anchors, void *stream);
+
 /* GaussianModel.mlp_grid = nn.Sequential(Linear(din, dh), ReLU, Linear(dh, dout)) (src/gs_compress/HAC/scene/gaussian_model.py:258-262,
  * called through get_grid_mlp at :1152-1153 and :1281-1282): y = W2 relu(W1 x + b1) + b2 for n rows.
  * w1 (dh, din), w2 (dout, dh) row-major as nn.Linear stores them; all pointers device.  Specified fp32 order
