@@ -30,23 +30,24 @@ The decoder samples the context from the planes decode_triplane RETURNED (multip
 what the model's grids hold.  The attribute files are raw torchac streams written and read by this pair only (torchac_encodings.
 encoder_gaussian_slices has the reason); byte compatibility with the reference's files is out of scope (its planes need `constriction`).
 `ckpt_path`: the GausPcgc checkpoint (the reference looks beside its own sources; here the argument or $GAUSPCGC_CKPT).
+The steps shared with HAC, HAC++ and TC-GS (slice geometry, xyz_pcc.bin, masks.b, fill back and parameter replacement, the MLP dispatch) are
+gauspcc_amd.anchor_codec's.
 """
-import ctypes as C
 import os
 import time
 
 import torch
 
-from . import arm_codec
-from .encodings_cuda import deferred_writes
-from .hac_codec import default_ckpt_path, mlp2, ste_multistep
-from .pcc_utils import calculate_morton_order, compress_point_cloud, decompress_point_cloud
-from .torchac_encodings import decoder, decoder_gaussian_slices, encoder, encoder_gaussian_slices
+from . import anchor_codec, arm_codec
+from .anchor_codec import (Q_FEAT, Q_OFFSETS, Q_SCALING, bit2MB_scale, decode_anchors, decode_mask_stream, encode_anchors, encode_mask_stream,
+                           install_decoded, mlp2_parts, n_slices, offset_bounds, offsets_mask, run_mlp2, slice_file_names, ste_multistep,
+                           zero_filled)
+from .encodings_cuda import _read_files, deferred_writes
+from .mlp import mlp2_forward
+from .torchac_encodings import decoder_gaussian_slices, encoder_gaussian_slices, host
 
-bit2MB_scale = 8 * 1024 * 1024     # CAT-3DGS/scene/gaussian_model.py:51
 anchor_round_digits = 16           # CAT-3DGS/utils/encodings.py:12
-MAX_BATCH_SIZE = 500               # :1178
-Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2   # :1216-1218
+MAX_BATCH_SIZE = 500               # CAT-3DGS/scene/gaussian_model.py:1178
 _CONTEXT_ROWS = 1 << 17            # anchors per pass of the context (432 floats of features each)
 # the class of gsac_decode_normal_chain (include/gauspcc.h)
 CHAIN_MAX_STAGES, CHAIN_MAX_CH, CHAIN_MAX_DH, CHAIN_DEFAULT_BLOCK = 8, 64, 128, 8
@@ -90,30 +91,9 @@ def chain_schedule(n_anchors, block_anchors, lags):
     return [[t - lag if 0 <= t - lag < nblocks else None for lag in lags] for t in range(chain_steps(n_anchors, block_anchors, lags))]
 
 
-def _steps(N, max_batch):
-    return (N // max_batch) if (N % max_batch) == 0 else (N // max_batch + 1)
-
-
 def slice_bounds(N, max_batch=MAX_BATCH_SIZE):
-    """anchor index at every slice boundary: steps + 1 entries"""
-    return [min(s * max_batch, N) for s in range(_steps(N, max_batch) + 1)]
-
-
-def _names(pre_path_name, stem, steps):
-    return [os.path.join(pre_path_name, f'{stem}.b').replace('.b', f'_{s}.b') for s in range(steps)]
-
-
-def _offset_bounds(mask, N, bounds):
-    """kept (masked-in) offset elements up to each slice boundary: only the sums at the boundaries leave the device"""
-    if N == 0:
-        return [0] * len(bounds)
-    kept = torch.cumsum(mask.view(N, -1).sum(dim=1), dim=0)
-    return [0] + kept[torch.tensor([b - 1 for b in bounds[1:]], dtype=torch.long, device=kept.device)].cpu().tolist()
-
-
-def _is_mlp2(m):
-    mods = list(m) if isinstance(m, torch.nn.Sequential) else []
-    return len(mods) == 3 and isinstance(mods[0], torch.nn.Linear) and isinstance(mods[1], torch.nn.ReLU) and isinstance(mods[2], torch.nn.Linear)
+    """anchor_codec.slice_bounds at CAT-3DGS's slice size"""
+    return anchor_codec.slice_bounds(N, max_batch)
 
 
 def chain_eligible(stages):
@@ -123,8 +103,10 @@ def chain_eligible(stages):
     for st in stages:
         if st["ch"] > CHAIN_MAX_CH or st["dep_ch"] > CHAIN_MAX_CH:
             return False
-        if st["mlp"] is not None and (not _is_mlp2(st["mlp"]) or st["mlp"][0].out_features > CHAIN_MAX_DH):
-            return False
+        if st["mlp"] is not None:
+            parts = mlp2_parts(st["mlp"])
+            if parts is None or parts[4] != "relu" or parts[0].shape[0] > CHAIN_MAX_DH:
+                return False
     return True
 
 
@@ -132,7 +114,7 @@ def _use_chain(chain, stages, N):
     if os.environ.get("GAUSPCC_DEV") == "1" and os.environ.get("GAUSPCC_CAT_CHAIN") in ("0", "1"):      # developer switch, as the kernel switches
         chain = os.environ["GAUSPCC_CAT_CHAIN"] == "1"
     if chain is None:
-        return N > 0 and chain_eligible(stages) and _steps(N, MAX_BATCH_SIZE) < CHAIN_AUTO_MAX_SLICES
+        return N > 0 and chain_eligible(stages) and n_slices(N, MAX_BATCH_SIZE) < CHAIN_AUTO_MAX_SLICES
     if chain and not chain_eligible(stages):
         raise ValueError("cat_codec: chain=True, but this model's stages are outside gsac_decode_normal_chain's class (at most 8 stages of at most 64 "
                          "channels, Linear - ReLU - Linear context MLPs of at most 128 hidden units)")
@@ -154,7 +136,7 @@ def _head(net, feat):
     fo, tail = net.feature_out, net.net
     fo_l, tail_l = (list(m) if isinstance(m, torch.nn.Sequential) else [] for m in (fo, tail))
     if len(fo_l) == 1 and isinstance(fo_l[0], torch.nn.Linear) and len(tail_l) == 2 and isinstance(tail_l[0], torch.nn.ReLU) and isinstance(tail_l[1], torch.nn.Linear):
-        return mlp2(feat, fo_l[0].weight, fo_l[0].bias, tail_l[1].weight, tail_l[1].bias)
+        return mlp2_forward(feat, fo_l[0].weight, fo_l[0].bias, tail_l[1].weight, tail_l[1].bias)
     return tail(fo(feat))
 
 
@@ -182,9 +164,7 @@ def _stage_params(st, ctx, feat_decoded):
     ch = st["ch"]
     mean, scale = ctx[:, st["mean_col"]:st["mean_col"] + ch], ctx[:, st["scale_col"]:st["scale_col"] + ch]
     if st["mlp"] is not None:
-        x = feat_decoded[:, :st["dep_ch"]].contiguous()
-        m = st["mlp"]
-        d = mlp2(x, m[0].weight, m[0].bias, m[2].weight, m[2].bias) if _is_mlp2(m) else m(x)
+        d = run_mlp2(st["mlp"], feat_decoded[:, :st["dep_ch"]].contiguous())
         mean, scale = mean + d[:, :ch], scale + d[:, ch:]
     return mean.contiguous(), torch.clamp(scale, min=1e-9).contiguous()
 
@@ -205,10 +185,10 @@ def encode_stages(stages, ctx, Q, x, mask, bounds, pre_path_name, steps):
             mean, scale = _stage_params(st, ctx, x["feat"])
             xs = x[st["attr"]][:, st["out_col"]:st["out_col"] + ch].contiguous()
             q = _flat_q(Q[st["attr"]], ch)
-            names = _names(pre_path_name, st["stem"], steps)
+            names = slice_file_names(pre_path_name, st["stem"], steps)
             if st["attr"] == "offsets":
                 m = mask.reshape(-1)
-                res = encoder_gaussian_slices(xs.reshape(-1)[m], mean.reshape(-1)[m], scale.reshape(-1)[m], q[m], _offset_bounds(m, N, bounds), names)
+                res = encoder_gaussian_slices(xs.reshape(-1)[m], mean.reshape(-1)[m], scale.reshape(-1)[m], q[m], offset_bounds(m, N, bounds), names)
             else:
                 res = encoder_gaussian_slices(xs.reshape(-1), mean.reshape(-1), scale.reshape(-1), q, [b * ch for b in bounds], names)
             bits[st["name"]], mins[st["name"]], maxs[st["name"]] = res
@@ -229,21 +209,14 @@ def conduct_encoding(self, pre_path_name, weighted_mask, ckpt_path=None):
     N = _anchor.shape[0]
 
     # AI-PCC (:1156-1169)
-    _anchor_int = torch.round(_anchor / self.voxel_size)
-    sorted_indices = calculate_morton_order(_anchor_int)
-    _anchor_int = _anchor_int[sorted_indices]
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    out = compress_point_cloud(_anchor_int, ckpt_path or default_ckpt_path(), npz_path)
-    bits_xyz = out['file_size_bits']
-
-    _anchor = _anchor_int * self.voxel_size
+    _anchor, sorted_indices, bits_xyz = encode_anchors(_anchor, self.voxel_size, ckpt_path, pre_path_name)
     _feat = _feat[sorted_indices]
     _grid_offsets = _grid_offsets[sorted_indices]
     _scaling = _scaling[sorted_indices]
     _mask = _mask[sorted_indices]
 
     MAX_batch_size = MAX_BATCH_SIZE
-    steps = _steps(N, MAX_batch_size)
+    steps = n_slices(N, MAX_batch_size)
     n_off = self.n_offsets
     anchor_infos_list = [None] * steps                                   # (:1221-1222)
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
@@ -255,7 +228,7 @@ def conduct_encoding(self, pre_path_name, weighted_mask, ckpt_path=None):
     # the rate of the quantised planes does not depend on the points (:1226: the reference's value of the last slice)
     feat_rate = self.feature_net(_anchor[:1], itr=-1)[1]
     # the three attributes as they are coded (:1245, :1333, :1345: STE_multistep with the GLOBAL means)
-    mask = _mask.repeat(1, 1, 3).view(-1, 3 * n_off).to(torch.bool)                      # [N, K*3]
+    mask = offsets_mask(_mask).view(N, 3 * n_off)                      # [N, K*3]
     x = {"feat": ste_multistep(_feat, Q["feat"], _feat.mean()),
          "scaling": ste_multistep(_scaling, Q["scaling"], self.get_scaling.mean()),
          "offsets": ste_multistep(_grid_offsets.reshape(-1, 3 * n_off), Q["offsets"], self._offset.mean())}
@@ -272,10 +245,7 @@ def conduct_encoding(self, pre_path_name, weighted_mask, ckpt_path=None):
     bit_scaling = sum(bits["scaling"])
     bit_offsets = sum(bits["offsets"])
 
-    p = torch.zeros_like(_mask).to(torch.float32)
-    prob_masks = (_mask.sum() / _mask.numel()).item()
-    p[...] = prob_masks
-    bit_masks = encoder((_mask * 2 - 1).view(-1), p.view(-1), file_name=masks_b_name)
+    bit_masks, prob_masks = encode_mask_stream(_mask, masks_b_name)      # (:1370-1375)
 
     show_feat_bits = ' '
     for i in range(G):
@@ -314,10 +284,10 @@ def decode_staged(stages, ctx, Q, keep, bounds, pre_path_name, steps, mins, maxs
         ch = st["ch"]
         mean, scale = _stage_params(st, ctx, outs["feat"])
         q = _flat_q(Q[st["attr"]], ch)
-        names = _names(pre_path_name, st["stem"], steps)
+        names = slice_file_names(pre_path_name, st["stem"], steps)
         if st["attr"] == "offsets":
             m = keep.reshape(-1)
-            vals = decoder_gaussian_slices(mean.reshape(-1)[m], scale.reshape(-1)[m], q[m], _offset_bounds(m, N, bounds), names, mins[st["name"]], maxs[st["name"]])
+            vals = decoder_gaussian_slices(mean.reshape(-1)[m], scale.reshape(-1)[m], q[m], offset_bounds(m, N, bounds), names, mins[st["name"]], maxs[st["name"]])
             outs["offsets"].view(-1)[m] = vals
         else:
             vals = decoder_gaussian_slices(mean.reshape(-1), scale.reshape(-1), q, [b * ch for b in bounds], names, mins[st["name"]], maxs[st["name"]])
@@ -328,24 +298,12 @@ def decode_staged(stages, ctx, Q, keep, bounds, pre_path_name, steps, mins, maxs
 def _read_streams(file_names):
     """(bytes, cnt): the files' contents back to back (a copy: the library's blob lives until this thread's next call) and their sizes"""
     import numpy as np
-    from . import _lib
-    n = len(file_names)
-    cp = (C.c_char_p * n)(*[os.fsencode(p) for p in file_names])
-    offs = (C.c_int64 * (n + 1))()
-    pb = C.c_void_p()
-    _lib.check(_lib.lib().gpcc_read_files(cp, n, 8, C.byref(pb), offs))
-    offs = np.frombuffer(offs, dtype=np.int64)
-    total = int(offs[n])
-    blob = np.frombuffer((C.c_ubyte * max(total, 1)).from_address(pb.value), dtype=np.uint8)[:total].copy()
-    cnt = np.diff(offs)
-    if cnt.size and int(cnt.max()) >= 1 << 31:
-        raise ValueError("cat_codec: a stream of 2 GiB or more")
-    return blob, cnt.astype(np.int32)
+    blob, offs = _read_files(file_names)
+    return blob.copy(), np.diff(offs).astype(np.int32)
 
 
 def decode_chain(stages, ctx, Q, keep, pre_path_name, steps, mins, maxs, N, F, n_off, max_batch=MAX_BATCH_SIZE, block_anchors=0):
     """gsac_decode_normal_chain on the files of conduct_encoding: the three attribute matrices.  keep: (N, K) bool, the offsets a stream holds."""
-    import numpy as np
     from . import _lib, runtime
     dev = ctx.device
     outs = {"feat": torch.zeros(N, F, device=dev), "scaling": torch.zeros(N, 6, device=dev), "offsets": torch.zeros(N, 3 * n_off, device=dev)}
@@ -355,27 +313,21 @@ def decode_chain(stages, ctx, Q, keep, pre_path_name, steps, mins, maxs, N, F, n
     alive = []                                              # what the records point to
     keep_u8 = keep.to(torch.uint8).contiguous()
 
-    def host(vals):
-        if all(isinstance(v, torch.Tensor) for v in vals):
-            return torch.stack([v.detach().reshape(()) for v in vals]).to(torch.float32).cpu().numpy()
-        return np.array([float(v) for v in vals], dtype=np.float32)
-
     for r, st in zip(recs, stages):
-        m = st["mlp"]
         for k in ("ch", "dep_ch", "lag", "mean_col", "scale_col", "feat_col", "out_col"):
             setattr(r, k, st[k])
         out = outs[st["attr"]]
         r.out_pitch, r.out_dev = out.shape[1], out.data_ptr()
         q = Q[st["attr"]].reshape(-1).contiguous()
         r.q_dev = q.data_ptr()
-        if m is not None:
-            w = [t.detach().contiguous().float() for t in (m[0].weight, m[0].bias, m[2].weight, m[2].bias)]
-            r.dh = m[0].out_features
+        if st["mlp"] is not None:
+            w = [t.detach().contiguous().float() for t in mlp2_parts(st["mlp"])[:4]]
+            r.dh = w[0].shape[0]
             r.w1, r.b1, r.w2, r.b2 = (t.data_ptr() for t in w)
             alive.append(w)
         if st["attr"] == "offsets":
             r.keep_dev, r.keep_group = keep_u8.data_ptr(), 3
-        blob, cnt = _read_streams(_names(pre_path_name, st["stem"], steps))
+        blob, cnt = _read_streams(slice_file_names(pre_path_name, st["stem"], steps))
         mn, mx = host(mins[st["name"]]), host(maxs[st["name"]])
         if mn.size != steps or mx.size != steps:
             raise ValueError("cat_codec: one (min, max) per slice and stage")
@@ -394,26 +346,16 @@ def conduct_decoding(self, pre_path_name, patched_infos, weighted_mask, ckpt_pat
     print('Start decoding ...')
     [N_full, N, MAX_batch_size, anchor_infos_list, min_feat_lists, max_feat_lists, min_scaling_list, max_scaling_list, min_offsets_list, max_offsets_list,
      prob_masks, triplane_coder_list] = patched_infos
-    steps = _steps(N, MAX_batch_size)
+    steps = n_slices(N, MAX_batch_size)
     n_off, F = self.n_offsets, self.feat_dim
     dev = self._anchor_feat.device
-    nn = torch.nn
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
 
     planes = arm_codec.decode_triplane(self.feature_net.attribute_net.grid, pre_path_name, triplane_coder_list)       # (:1414)
 
-    p = torch.zeros(size=[N, n_off, 1], device=dev).to(torch.float32)
-    p[...] = prob_masks
-    masks_decoded = decoder(p.view(-1), masks_b_name)  # {-1, 1}
-    masks_decoded = (masks_decoded + 1) / 2  # {0, 1}
-    masks_decoded = masks_decoded.view(-1, n_off, 1)
+    masks_decoded = decode_mask_stream(N, n_off, prob_masks, masks_b_name, dev)      # (:1417-1422) {0, 1}
 
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    anchor_decoded = decompress_point_cloud(npz_path, ckpt_path or default_ckpt_path())
-    _anchor_int_dec = anchor_decoded['point_cloud'].to(dev)
-    sorted_indices = calculate_morton_order(_anchor_int_dec)
-    _anchor_int_dec = _anchor_int_dec[sorted_indices]
-    anchor_decoded = _anchor_int_dec * self.voxel_size
+    anchor_decoded = decode_anchors(pre_path_name, ckpt_path, self.voxel_size, dev)      # (:1440-1447)
     N = anchor_decoded.shape[0]
 
     stages = stage_table(self)
@@ -428,7 +370,7 @@ def conduct_decoding(self, pre_path_name, patched_infos, weighted_mask, ckpt_pat
     if _use_chain(chain, stages, N):
         outs = decode_chain(stages, ctx, Q, keep, pre_path_name, steps, mins, maxs, N, F, n_off, MAX_batch_size)
     else:
-        outs = decode_staged(stages, ctx, Q, keep.unsqueeze(-1).repeat(1, 1, 3).view(N, 3 * n_off), bounds, pre_path_name, steps, mins, maxs, N, F, n_off)
+        outs = decode_staged(stages, ctx, Q, offsets_mask(masks_decoded).view(N, 3 * n_off), bounds, pre_path_name, steps, mins, maxs, N, F, n_off)
     feat_decoded, scaling_decoded = outs["feat"], outs["scaling"]
     offsets_decoded = outs["offsets"].view(N, n_off, 3)  # [N, K, 3]
 
@@ -436,24 +378,10 @@ def conduct_decoding(self, pre_path_name, patched_infos, weighted_mask, ckpt_pat
     print('decoding time:', t2 - t1)
 
     # fill back N_full (:1581-1592)
-    _anchor = torch.zeros(size=[N, 3], device=dev)
-    _anchor_feat = torch.zeros(size=[N, F], device=dev)
-    _offset = torch.zeros(size=[N, n_off, 3], device=dev)
-    _scaling = torch.zeros(size=[N, 6], device=dev)
-    _mask = torch.zeros(size=[N, n_off, 1], device=dev)
-    _anchor[:N] = anchor_decoded
-    _anchor_feat[:N] = feat_decoded
-    _offset[:N] = offsets_decoded
-    _scaling[:N] = scaling_decoded
-    _mask[:N] = masks_decoded
+    filled = [zero_filled(t) for t in (anchor_decoded, feat_decoded, offsets_decoded, scaling_decoded, masks_decoded)]
 
     print('Start replacing parameters with decoded ones...')
-    self._anchor_feat = nn.Parameter(_anchor_feat)
-    self._offset = nn.Parameter(_offset)
-    self.decoded_version = True      # the accessors stop applying activations / quantisers (:1602)
-    self._anchor = nn.Parameter(_anchor)
-    self._scaling = nn.Parameter(_scaling)
-    self._mask = nn.Parameter(_mask)
+    install_decoded(self, *filled)      # (:1598-1608)
     print('Parameters are successfully replaced by decoded ones!')
     return f"\nDecTime {round(t2 - t1, 4)}"
 

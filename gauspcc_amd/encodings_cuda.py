@@ -58,12 +58,10 @@ def _write_files(jobs):
         _write_files_now(jobs)
 
 
-def _read_slice_files(paths, lens=None):
-    """lens: the symbol count of every slice -- a file whose chunk table is not exactly ceil(len / chunk_size_cuda) int32 entries is rejected here
-    (the library reads one count per chunk: a shorter table would be read past its end, a longer one would shift every later slice's counts).
-    The `[min, max, len(cnt) * 4, cnt..., payload]` files of many slices (encoder_gaussian*_slices) read by libgauspcc on native threads
-    (gpcc_read_files: 2 343 files cost ~27 ms of open / read / frombuffer in Python): (mins, maxs, cnts, datas) with numpy views into one blob that
-    is valid until this thread's next call -- callers concatenate them at once."""
+def _read_files(paths):
+    """The contents of many files read by libgauspcc on native threads (gpcc_read_files: 2 343 files cost ~27 ms of open / read / frombuffer in Python):
+    (blob, offsets) -- a uint8 numpy VIEW of the files back to back and the n + 1 int64 offsets of their starts in it.  The blob is the library's and
+    lives until this thread's next call: use it at once, or copy.  A file of 2 GiB or more is refused (the coders take int32 byte counts)."""
     import ctypes as C
     from . import _lib
     n = len(paths)
@@ -71,10 +69,21 @@ def _read_slice_files(paths, lens=None):
     offs = (C.c_int64 * (n + 1))()
     pb = C.c_void_p()
     _lib.check(_lib.lib().gpcc_read_files(cp, n, 8, C.byref(pb), offs))
-    total = offs[n]
-    blob = np.frombuffer((C.c_ubyte * max(int(total), 1)).from_address(pb.value), dtype=np.uint8)
+    offs = np.frombuffer(offs, dtype=np.int64)
+    total = int(offs[n])
+    if n and int(np.diff(offs).max()) >= 1 << 31:
+        raise ValueError(f"{os.fsdecode(paths[int(np.diff(offs).argmax())])}: a file of 2 GiB or more")
+    return np.frombuffer((C.c_ubyte * max(total, 1)).from_address(pb.value), dtype=np.uint8)[:total], offs
+
+
+def _read_slice_files(paths, lens=None):
+    """lens: the symbol count of every slice -- a file whose chunk table is not exactly ceil(len / chunk_size_cuda) int32 entries is rejected here
+    (the library reads one count per chunk: a shorter table would be read past its end, a longer one would shift every later slice's counts).
+    The `[min, max, len(cnt) * 4, cnt..., payload]` files of many slices (encoder_gaussian*_slices) read in one _read_files call: (mins, maxs, cnts,
+    datas) with numpy views into its blob, valid until this thread's next call -- callers concatenate them at once."""
+    blob, offs = _read_files(paths)
     mins, maxs, cnts, datas = [], [], [], []
-    for i in range(n):
+    for i in range(len(paths)):
         a, b = int(offs[i]), int(offs[i + 1])
         if b - a < 12:
             raise RuntimeError(f"{paths[i]}: truncated slice file")

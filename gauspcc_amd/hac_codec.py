@@ -22,57 +22,31 @@ The context MLP runs ONCE over all anchors instead of once per 3000-anchor slice
 the result are the per-slice results), and all slices of an attribute are coded in ONE device call
 (gsac_encode_gaussian_slices / gsac_decode_gaussian_slices): the slices only decide which elements share a `.b` file and
 its min / max.  Per million anchors the reference issues ~1000 coder calls, each a serial chain of 10000-symbol chunks.
+
+The steps this loop shares with HAC++, TC-GS and CAT-3DGS (slice geometry, xyz_pcc.bin, parameter replacement, the MLP
+dispatch) are gauspcc_amd.anchor_codec's; `mlp2` stays here as the name tests and tools call.
 """
 import os
 import time
 
 import torch
 
-from . import _lib, runtime
-from .encodings_cuda import decoder, decoder_gaussian_slices, decoder_gaussian_slices_multi, deferred_writes, encoder, encoder_gaussian_slices
-from .pcc_utils import calculate_morton_order, compress_point_cloud, decompress_point_cloud
+from .anchor_codec import (Q_FEAT, Q_OFFSETS, Q_SCALING, bit2MB_scale, decode_anchors, encode_anchors, install_decoded, n_slices, offset_bounds,
+                           offsets_mask, run_mlp2, slice_bounds, slice_file_names, ste_multistep)
+from .encodings_cuda import decoder, decoder_gaussian_slices_multi, deferred_writes, encoder, encoder_gaussian_slices
+from .mlp import mlp2_forward
 
-bit2MB_scale = 8 * 1024 * 1024     # HAC/scene/gaussian_model.py:30
-MAX_BATCH_SIZE = 3_000             # :1123
-Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2   # :1147-1149
-USE_CLAMP = True                   # HAC/utils/encodings.py:11 (use_clamp)
-
-
-def default_ckpt_path():
-    """HAC looks for <repo>/GausPcgc/best_model_ue_4stage_conv.pt (gaussian_model.py:1110-1112); here: $GAUSPCGC_CKPT."""
-    p = os.environ.get("GAUSPCGC_CKPT")
-    if not p:
-        raise FileNotFoundError("pass ckpt_path=... or set GAUSPCGC_CKPT to best_model_ue_4stage_conv.pt (the reference ships no checkpoint)")
-    return p
+MAX_BATCH_SIZE = 3_000             # HAC/scene/gaussian_model.py:1123
 
 
 def mlp2(x, w1, b1, w2, b2):
-    """Linear - ReLU - Linear on the device, specified fp32 order (gshac_mlp2).  x (n, din) -> (n, dout)."""
-    x = x.contiguous().float()
-    w1, b1, w2, b2 = (t.detach().contiguous().float() for t in (w1, b1, w2, b2))
-    n, din = x.shape
-    dh, dout = w1.shape[0], w2.shape[0]
-    y = torch.empty(n, dout, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().gshac_mlp2(runtime.context(x.device), x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                     n, din, dh, dout, y.data_ptr(), runtime.stream_ptr(x.device)))
-    return y
+    """Linear - ReLU - Linear on the device, specified fp32 order (gshac_mlp2_act).  x (n, din) -> (n, dout)."""
+    return mlp2_forward(x, w1, b1, w2, b2, "relu", 0.0)
 
 
 def grid_mlp(model, feat_context):
-    """model.get_grid_mlp(feat_context).  An nn.Sequential(Linear, ReLU, Linear) -- what HAC builds (:258-262) -- goes through
-    gshac_mlp2; anything else is called as it is."""
-    m = model.get_grid_mlp
-    mods = list(m) if isinstance(m, torch.nn.Sequential) else []
-    if len(mods) == 3 and isinstance(mods[0], torch.nn.Linear) and isinstance(mods[1], torch.nn.ReLU) and isinstance(mods[2], torch.nn.Linear):
-        return mlp2(feat_context, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias)
-    return m(feat_context)
-
-
-def ste_multistep(x, Q, input_mean):
-    """STE_multistep.forward (HAC/utils/encodings.py:55-67)."""
-    if USE_CLAMP:
-        x = torch.clamp(x, min=(input_mean - 15_000 * Q).detach(), max=(input_mean + 15_000 * Q).detach())
-    return torch.round(x / Q) * Q
+    """model.get_grid_mlp(feat_context): the nn.Sequential(Linear, ReLU, Linear) HAC builds (:258-262) on the device kernel (anchor_codec.run_mlp2)."""
+    return run_mlp2(model.get_grid_mlp, feat_context)
 
 
 def _context(model, anchor):
@@ -105,29 +79,22 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
     _scaling = self.get_scaling[mask_anchor]
     _mask = self.get_mask[mask_anchor]
 
-    # AI-PCC (:1106-1114)
-    _anchor_int = torch.round(_anchor / self.voxel_size)
-    sorted_indices = calculate_morton_order(_anchor_int)
-    _anchor_int = _anchor_int[sorted_indices]
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    out = compress_point_cloud(_anchor_int, ckpt_path or default_ckpt_path(), npz_path)
-    bits_xyz = out['file_size_bits']
-
-    _anchor = _anchor_int * self.voxel_size
+    # AI-PCC (:1106-1117)
+    _anchor, sorted_indices, bits_xyz = encode_anchors(_anchor, self.voxel_size, ckpt_path, pre_path_name)
     _feat = _feat[sorted_indices]
     _grid_offsets = _grid_offsets[sorted_indices]
     _scaling = _scaling[sorted_indices]
     _mask = _mask[sorted_indices]
 
     N = _anchor.shape[0]
-    steps = (N // MAX_BATCH_SIZE) if (N % MAX_BATCH_SIZE) == 0 else (N // MAX_BATCH_SIZE + 1)
+    steps = n_slices(N, MAX_BATCH_SIZE)
     n_off = self.n_offsets
     c = _context(self, _anchor)
     feat_mean, scaling_mean, offsets_mean = _feat.mean(), _scaling.mean(), _grid_offsets.mean()
     hash_b_name = os.path.join(pre_path_name, 'hash.b')
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
-    names = lambda stem: [os.path.join(pre_path_name, f'{stem}.b').replace('.b', f'_{s}.b') for s in range(steps)]
-    bounds = [min(s * MAX_BATCH_SIZE, N) for s in range(steps + 1)]
+    names = lambda stem: slice_file_names(pre_path_name, stem, steps)
+    bounds = slice_bounds(N, MAX_BATCH_SIZE)
 
     torch.cuda.synchronize(); t0 = time.time()
     with deferred_writes():      # the 3 x 334 slice files are written while the next attribute is coded; all on disk when the block ends
@@ -139,14 +106,11 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
         scaling = ste_multistep(_scaling.reshape(-1), Q, scaling_mean)
         bit_scaling_list = encoder_gaussian_slices(scaling, c["mean_scaling"].reshape(-1), c["scale_scaling"].reshape(-1), Q, [b * 6 for b in bounds], names('scaling'))
 
-        mask = _mask.repeat(1, 1, 3).view(-1, 3 * n_off).view(-1).to(torch.bool)        # [N*K*3]
+        mask = offsets_mask(_mask)        # [N*K*3]
         Q = c["Q_offsets"].reshape(-1)
         offsets = ste_multistep(_grid_offsets.reshape(-1, 3 * n_off).reshape(-1), Q, offsets_mean)
-        # masked elements up to each slice boundary: only the sums at the slice boundaries leave the device (a million-entry .tolist() was 10 ms)
-        kept = torch.cumsum(mask.view(N, -1).sum(dim=1), dim=0)
-        off_bounds = [0] + kept[torch.tensor([b - 1 for b in bounds[1:]], dtype=torch.long, device=kept.device)].cpu().tolist()   # (dtype: an empty list is float32 otherwise and cannot index)
         bit_offsets_list = encoder_gaussian_slices(offsets[mask], c["mean_offsets"].reshape(-1)[mask], c["scale_offsets"].reshape(-1)[mask], Q[mask],
-                                                   off_bounds, names('offsets'))
+                                                   offset_bounds(mask, N, bounds), names('offsets'))
     torch.cuda.synchronize(); t_codec += time.time() - t0
 
     bit_anchor = bits_xyz
@@ -180,7 +144,7 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
     torch.cuda.synchronize(); t1 = time.time()
     print('Start decoding ...')
     [N_full, N, max_batch] = patched_infos
-    steps = (N // max_batch) if (N % max_batch) == 0 else (N // max_batch + 1)
+    steps = n_slices(N, max_batch)
     n_off = self.n_offsets
     dev = self._anchor_feat.device
     hash_b_name = os.path.join(pre_path_name, 'hash.b')
@@ -194,28 +158,20 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
         hash_embeddings = (hash_embeddings * 2 - 1).to(torch.float32).view(-1, self.n_features_per_level)
         _install_hash(self, hash_embeddings)      # the context below must run on the decoded tables (bit-identical for {-1, 1})
 
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    anchor_decoded = decompress_point_cloud(npz_path, ckpt_path or default_ckpt_path())
-    _anchor_int_dec = anchor_decoded['point_cloud'].to(dev)
-    sorted_indices = calculate_morton_order(_anchor_int_dec)
-    _anchor_int_dec = _anchor_int_dec[sorted_indices]
-    anchor_decoded = _anchor_int_dec * self.voxel_size
+    anchor_decoded = decode_anchors(pre_path_name, ckpt_path, self.voxel_size, dev)      # (:1250-1256)
     N = anchor_decoded.shape[0]
 
     c = _context(self, anchor_decoded)
-    names = lambda stem: [os.path.join(pre_path_name, f'{stem}.b').replace('.b', f'_{s}.b') for s in range(steps)]
-    bounds = [min(s * max_batch, N) for s in range(steps + 1)]
-    mask = masks_decoded.repeat(1, 1, 3).view(-1, 3 * n_off).view(-1).to(torch.bool)
-    # masked elements up to each slice boundary: only the sums at the slice boundaries leave the device (a million-entry .tolist() was 10 ms)
-    kept = torch.cumsum(mask.view(N, -1).sum(dim=1), dim=0)
-    off_bounds = [0] + kept[torch.tensor([b - 1 for b in bounds[1:]], dtype=torch.long, device=kept.device)].cpu().tolist()   # (dtype: an empty list is float32 otherwise and cannot index)
+    names = lambda stem: slice_file_names(pre_path_name, stem, steps)
+    bounds = slice_bounds(N, max_batch)
+    mask = offsets_mask(masks_decoded)
     mo = c["mean_offsets"].reshape(-1)
     # the three attributes in ONE device call: their chunks side by side (encodings_cuda.decoder_gaussian_slices_multi); the reference decodes
     # slice after slice, attribute after attribute (:1304-1331)
     feat_decoded, scaling_decoded, offs = decoder_gaussian_slices_multi([
         (c["mean"].reshape(-1), c["scale"].reshape(-1), c["Q_feat"].reshape(-1), [b * self.feat_dim for b in bounds], names('feat')),
         (c["mean_scaling"].reshape(-1), c["scale_scaling"].reshape(-1), c["Q_scaling"].reshape(-1), [b * 6 for b in bounds], names('scaling')),
-        (mo[mask], c["scale_offsets"].reshape(-1)[mask], c["Q_offsets"].reshape(-1)[mask], off_bounds, names('offsets'))])
+        (mo[mask], c["scale_offsets"].reshape(-1)[mask], c["Q_offsets"].reshape(-1)[mask], offset_bounds(mask, N, bounds), names('offsets'))])
     feat_decoded = feat_decoded.view(N, self.feat_dim)
     scaling_decoded = scaling_decoded.view(N, 6)
     offsets_decoded = torch.zeros_like(mo)
@@ -226,13 +182,7 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
     print('decoding time:', t2 - t1)
 
     print('Start replacing parameters with decoded ones...')
-    nn = torch.nn
-    self._anchor_feat = nn.Parameter(feat_decoded)
-    self._offset = nn.Parameter(offsets_decoded)
-    self.decoded_version = True                      # (:1336) the accessors stop applying activations / quantisers
-    self._anchor = nn.Parameter(anchor_decoded)
-    self._scaling = nn.Parameter(scaling_decoded)
-    self._mask = nn.Parameter(masks_decoded)
+    install_decoded(self, anchor_decoded, feat_decoded, offsets_decoded, scaling_decoded, masks_decoded)      # (:1342-1348)
     print('Parameters are successfully replaced by decoded ones!')
     return f"\nDecTime {round(t2 - t1, 4)}"
 

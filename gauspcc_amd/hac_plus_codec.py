@@ -23,33 +23,28 @@ What HAC++ adds to HAC's loop, and how it runs here:
     offsets
     anchors     calculate_morton_order + compress / decompress_point_cloud (gpcc_encode / gpcc_decode)
     context     calc_interp_feat (3-D + three 2-D hash grids) -> mlp_grid (gshac_mlp2), once over all anchors
+
+The steps shared with the other Scaffold-family codecs are gauspcc_amd.anchor_codec's; the timing spans around them stay here.
 """
 import os
 import time
 
 import torch
 
+from .anchor_codec import (Q_FEAT, Q_OFFSETS, Q_SCALING, bit2MB_scale, decode_anchors, encode_anchors, install_decoded, mlp2_parts, n_slices,
+                           offset_bounds, offsets_mask, slice_bounds, slice_file_names, ste_multistep)
 from .encodings_cuda import (decoder, decoder_gaussian_mixed_slices, decoder_gaussian_slices, deferred_writes, encoder, encoder_gaussian_mixed_slices,
                              encoder_gaussian_slices)
-from .hac_codec import _install_hash, bit2MB_scale, default_ckpt_path, grid_mlp, ste_multistep
-from .pcc_utils import calculate_morton_order, compress_point_cloud, decompress_point_cloud
-from . import _lib, runtime
+from .hac_codec import _install_hash, grid_mlp
+from .mlp import mlp2_forward
 
 MAX_BATCH_SIZE = 3_000                         # HAC-plus/scene/gaussian_model.py:42
-Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2   # :1277-1279
 N_GROUPS, GROUP = 5, 10                        # feat_dim = 50 coded as five groups of ten channels (:1305, Channel_CTX_fea)
 
 
 def mlp2_act(x, w1, b1, w2, b2, slope):
     """Linear - LeakyReLU(slope) - Linear on the device, specified fp32 order (gshac_mlp2_act).  x (n, din) -> (n, dout)."""
-    x = x.contiguous().float()
-    w1, b1, w2, b2 = (t.detach().contiguous().float() for t in (w1, b1, w2, b2))
-    n, din = x.shape
-    dh, dout = w1.shape[0], w2.shape[0]
-    y = torch.empty(n, dout, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().gshac_mlp2_act(runtime.context(x.device), x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                         n, din, dh, dout, 1, float(slope), y.data_ptr(), runtime.stream_ptr(x.device)))
-    return y
+    return mlp2_forward(x, w1, b1, w2, b2, "leaky_relu", slope)
 
 
 def deform_group(model, feat_q, mean_scale, cc):
@@ -57,19 +52,16 @@ def deform_group(model, feat_q, mean_scale, cc):
     MLP_d{cc} = Sequential(Linear(150 + 10 cc, 40), LeakyReLU, Linear(40, 30)) on cat([d0 .. d(cc-1), mean_scale]) (:117-168) goes
     through gshac_mlp2_act; the `tiny` variant's MLPs (inputs d0 .. d(cc-1) only, :170-220) too; anything else is called as it is."""
     m = model.get_deform_mlp
-    sub = getattr(m, f"MLP_d{cc}", None)
-    mods = list(sub) if isinstance(sub, torch.nn.Sequential) else []
-    if len(mods) == 3 and isinstance(mods[0], torch.nn.Linear) and isinstance(mods[1], torch.nn.LeakyReLU) and isinstance(mods[2], torch.nn.Linear) \
-            and mods[2].out_features == 3 * GROUP:
-        prev = feat_q[:, :GROUP * cc]
-        if mods[0].in_features == GROUP * cc + mean_scale.shape[1]:
+    parts = mlp2_parts(getattr(m, f"MLP_d{cc}", None))
+    if parts is not None and parts[2].shape[0] == 3 * GROUP:
+        prev, din = feat_q[:, :GROUP * cc], parts[0].shape[1]
+        if din == GROUP * cc + mean_scale.shape[1]:
             x = torch.cat([prev, mean_scale], dim=-1)
-        elif mods[0].in_features == GROUP * cc and cc > 0:
+        elif din == GROUP * cc and cc > 0:
             x = prev
         else:
             return m.forward(feat_q, mean_scale, to_dec=cc)
-        y = mlp2_act(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, mods[1].negative_slope)
-        return torch.chunk(y, chunks=3, dim=-1)
+        return torch.chunk(mlp2_forward(x, *parts), chunks=3, dim=-1)
     return m.forward(feat_q, mean_scale, to_dec=cc)
 
 
@@ -101,10 +93,6 @@ def _group_mixture(model, c, feat_q, cc):
             flat(c["Q_feat"][:, sl]))
 
 
-def _names(pre_path_name, stem, steps):
-    return [os.path.join(pre_path_name, f'{stem}.b').replace('.b', f'_{s}.b') for s in range(steps)]
-
-
 def get_time():
     """(:43-46) a device-wide sync, then the wall clock: the spans of the `Encoded time in s:` / `Decoded time in s:` lines."""
     torch.cuda.synchronize()
@@ -126,15 +114,9 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
     N = _anchor.shape[0]
 
     t_anchor_0 = get_time()     # (:1234-1248) `anchor` = the order + compress_point_cloud: the in-pipeline timing of the geometry codec
-    _anchor_int = torch.round(_anchor / self.voxel_size)
-    sorted_indices = calculate_morton_order(_anchor_int)
-    _anchor_int = _anchor_int[sorted_indices]
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    out = compress_point_cloud(_anchor_int, ckpt_path or default_ckpt_path(), npz_path)
-    bits_xyz = out['file_size_bits']
+    _anchor, sorted_indices, bits_xyz = encode_anchors(_anchor, self.voxel_size, ckpt_path, pre_path_name)
     t_anchor = get_time() - t_anchor_0
 
-    _anchor = _anchor_int * self.voxel_size
     _feat = _feat[sorted_indices]
     _grid_offsets = _grid_offsets[sorted_indices]
     _scaling = _scaling[sorted_indices]
@@ -143,10 +125,10 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
     torch.save(self.x_bound_min, os.path.join(pre_path_name, 'x_bound_min.pkl'))
     torch.save(self.x_bound_max, os.path.join(pre_path_name, 'x_bound_max.pkl'))
 
-    steps = (N // MAX_BATCH_SIZE) if (N % MAX_BATCH_SIZE) == 0 else (N // MAX_BATCH_SIZE + 1)
+    steps = n_slices(N, MAX_BATCH_SIZE)
     n_off = self.n_offsets
     c = _context(self, _anchor)
-    bounds = [min(s * MAX_BATCH_SIZE, N) for s in range(steps + 1)]
+    bounds = slice_bounds(N, MAX_BATCH_SIZE)
     hash_b_name = os.path.join(pre_path_name, 'hash.b')
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
 
@@ -159,7 +141,7 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
         for cc in range(N_GROUPS):
             means, scales, probs, q = _group_mixture(self, c, feat, cc)
             x = feat[:, cc * GROUP:cc * GROUP + GROUP].contiguous().view(-1)
-            names = [fn.replace('.b', f'_{cc}.b') for fn in _names(pre_path_name, 'feat', steps)]
+            names = [fn.replace('.b', f'_{cc}.b') for fn in slice_file_names(pre_path_name, 'feat', steps)]
             bit_feat += sum(encoder_gaussian_mixed_slices(x, means, scales, probs, q, [b * GROUP for b in bounds], names, chunk_size=50_0000))
         t_feature = get_time() - t_feature_0
 
@@ -167,18 +149,15 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
         Q = c["Q_scaling"].reshape(-1)
         scaling = ste_multistep(_scaling.reshape(-1), Q, self.get_scaling.mean())
         bit_scaling = sum(encoder_gaussian_slices(scaling, c["mean_scaling"].reshape(-1), c["scale_scaling"].reshape(-1), Q, [b * 6 for b in bounds],
-                                                  _names(pre_path_name, 'scaling', steps), chunk_size=10_0000))
+                                                  slice_file_names(pre_path_name, 'scaling', steps), chunk_size=10_0000))
         t_scaling = get_time() - t_scaling_0
 
         t_offset_0 = get_time()
-        mask = _mask.repeat(1, 1, 3).view(-1, 3 * n_off).view(-1).to(torch.bool)        # [N*K*3]
+        mask = offsets_mask(_mask)        # [N*K*3]
         Q = c["Q_offsets"].reshape(-1)
         offsets = ste_multistep(_grid_offsets.reshape(-1, 3 * n_off).reshape(-1), Q, self._offset.mean())
-        # masked elements up to each slice boundary: only the sums at the slice boundaries leave the device (a million-entry .tolist() was 10 ms)
-        kept = torch.cumsum(mask.view(N, -1).sum(dim=1), dim=0)
-        off_bounds = [0] + kept[torch.tensor([b - 1 for b in bounds[1:]], dtype=torch.long, device=kept.device)].cpu().tolist()   # (dtype: an empty list is float32 otherwise and cannot index)
-        bit_offsets = sum(encoder_gaussian_slices(offsets[mask], c["mean_offsets"].reshape(-1)[mask], c["scale_offsets"].reshape(-1)[mask], Q[mask], off_bounds,
-                                                  _names(pre_path_name, 'offsets', steps), chunk_size=10_0000))
+        bit_offsets = sum(encoder_gaussian_slices(offsets[mask], c["mean_offsets"].reshape(-1)[mask], c["scale_offsets"].reshape(-1)[mask], Q[mask],
+                                                  offset_bounds(mask, N, bounds), slice_file_names(pre_path_name, 'offsets', steps), chunk_size=10_0000))
         t_offset = get_time() - t_offset_0
     torch.cuda.synchronize(); t_codec += time.time() - t0
 
@@ -237,15 +216,10 @@ def conduct_decoding(self, pre_path_name, ckpt_path=None):
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
 
     t_anchor_0 = get_time()     # (:1422-1438) decompress_point_cloud + the order
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    anchor_decoded = decompress_point_cloud(npz_path, ckpt_path or default_ckpt_path())
-    _anchor_int_dec = anchor_decoded['point_cloud'].to(dev)
-    sorted_indices = calculate_morton_order(_anchor_int_dec)
-    _anchor_int_dec = _anchor_int_dec[sorted_indices]
-    anchor_decoded = _anchor_int_dec * self.voxel_size
+    anchor_decoded = decode_anchors(pre_path_name, ckpt_path, self.voxel_size, dev)
     t_anchor = get_time() - t_anchor_0
     N = anchor_decoded.shape[0]
-    steps = (N // MAX_BATCH_SIZE) if (N % MAX_BATCH_SIZE) == 0 else (N // MAX_BATCH_SIZE + 1)
+    steps = n_slices(N, MAX_BATCH_SIZE)
 
     t_mask_0 = get_time()
     masks_decoded = decoder(N * n_off, masks_b_name, device=dev).to(torch.float32).view(-1, n_off, 1)   # {0, 1}
@@ -259,30 +233,27 @@ def conduct_decoding(self, pre_path_name, ckpt_path=None):
     t_hash = get_time() - t_hash_0
 
     c = _context(self, anchor_decoded)
-    bounds = [min(s * MAX_BATCH_SIZE, N) for s in range(steps + 1)]
+    bounds = slice_bounds(N, MAX_BATCH_SIZE)
     # feat: the autoregressive chain over the five channel groups (:1484-1504) -- group cc of every anchor at once
     t_feature_0 = get_time()
     feat_decoded = torch.zeros(size=[N, self.feat_dim], device=dev, dtype=torch.float32)
     for cc in range(N_GROUPS):
         means, scales, probs, q = _group_mixture(self, c, feat_decoded, cc)
-        names = [fn.replace('.b', f'_{cc}.b') for fn in _names(pre_path_name, 'feat', steps)]
+        names = [fn.replace('.b', f'_{cc}.b') for fn in slice_file_names(pre_path_name, 'feat', steps)]
         dec = decoder_gaussian_mixed_slices(means, scales, probs, q, [b * GROUP for b in bounds], names)
         feat_decoded[:, cc * GROUP:cc * GROUP + GROUP] = dec.view(N, GROUP)
     t_feature = get_time() - t_feature_0
 
     t_scaling_0 = get_time()
     scaling_decoded = decoder_gaussian_slices(c["mean_scaling"].reshape(-1), c["scale_scaling"].reshape(-1), c["Q_scaling"].reshape(-1),
-                                              [b * 6 for b in bounds], _names(pre_path_name, 'scaling', steps)).view(N, 6)
+                                              [b * 6 for b in bounds], slice_file_names(pre_path_name, 'scaling', steps)).view(N, 6)
     t_scaling = get_time() - t_scaling_0
     t_offset_0 = get_time()
-    mask = masks_decoded.repeat(1, 1, 3).view(-1, 3 * n_off).view(-1).to(torch.bool)
-    # masked elements up to each slice boundary: only the sums at the slice boundaries leave the device (a million-entry .tolist() was 10 ms)
-    kept = torch.cumsum(mask.view(N, -1).sum(dim=1), dim=0)
-    off_bounds = [0] + kept[torch.tensor([b - 1 for b in bounds[1:]], dtype=torch.long, device=kept.device)].cpu().tolist()   # (dtype: an empty list is float32 otherwise and cannot index)
+    mask = offsets_mask(masks_decoded)
     mo = c["mean_offsets"].reshape(-1)
     offsets_decoded = torch.zeros_like(mo)
-    offsets_decoded[mask] = decoder_gaussian_slices(mo[mask], c["scale_offsets"].reshape(-1)[mask], c["Q_offsets"].reshape(-1)[mask], off_bounds,
-                                                    _names(pre_path_name, 'offsets', steps))
+    offsets_decoded[mask] = decoder_gaussian_slices(mo[mask], c["scale_offsets"].reshape(-1)[mask], c["Q_offsets"].reshape(-1)[mask],
+                                                    offset_bounds(mask, N, bounds), slice_file_names(pre_path_name, 'offsets', steps))
     offsets_decoded = offsets_decoded.view(N, n_off, 3)
     t_offset = get_time() - t_offset_0
     t_total = get_time() - t_total_0
@@ -291,15 +262,9 @@ def conduct_decoding(self, pre_path_name, ckpt_path=None):
     print('decoding time:', t2 - t1)
 
     print('Start replacing parameters with decoded ones...')
-    nn = torch.nn
     _mask = torch.zeros(size=[N, n_off + 1, 1], device=dev)      # (:1545) HAC++ keeps one more mask slot per anchor than it codes
     _mask[:N, :n_off] = masks_decoded
-    self._anchor_feat = nn.Parameter(feat_decoded)
-    self._offset = nn.Parameter(offsets_decoded)
-    self.decoded_version = True
-    self._anchor = nn.Parameter(anchor_decoded)
-    self._scaling = nn.Parameter(scaling_decoded)
-    self._mask = nn.Parameter(_mask)
+    install_decoded(self, anchor_decoded, feat_decoded, offsets_decoded, scaling_decoded, _mask)      # (:1554-1559)
     print('Parameters are successfully replaced by decoded ones!')
     log_info = f"\nDecTime {round(t2 - t1, 4)}"
     log_info_time = f"\nDecoded time in s: " \

@@ -5,10 +5,10 @@
     Channel_CTX_fea, Channel_CTX_fea_tiny       ->   from gauspcc_amd.mlp import Channel_CTX_fea, Channel_CTX_fea_tiny
                                                 (HAC-plus/scene/gaussian_model.py:117-220, built at :377-380)
 
-The forward is the codec's: the bit-specified chain (bias, then fmaf over k ascending) that `hac_codec` / `hac_plus_codec` evaluate when
-they encode and decode, so the rate model is trained on exactly the means, scales and step sizes the coder will compute.  Nothing is
-saved for the backward except the inputs: it recomputes the hidden layer with the same chain.  Weight and bias gradients are summed in a
-fixed order (no atomics): bitwise reproducible from run to run and across streams.
+The forward is the codecs': `mlp2_forward`, the bit-specified chain (bias, then fmaf over k ascending) that the conduct_encoding / conduct_decoding
+drop-ins evaluate when they encode and decode (anchor_codec.run_mlp2), so the rate model is trained on exactly the means, scales and step sizes
+the coder will compute.  Nothing is saved for the backward except the inputs: it recomputes the hidden layer with the same chain.  Weight and bias
+gradients are summed in a fixed order (no atomics): bitwise reproducible from run to run and across streams.
 
 `ContextMLP` IS an nn.Sequential(Linear, ReLU | LeakyReLU, Linear): state-dict keys 0.weight, 0.bias, 2.weight, 2.bias, code that walks
 it for nn.Linear and the codecs' own recognition of the pattern keep working.  Only float32 CUDA input takes the fused path; anything
@@ -29,13 +29,16 @@ def slab_rows(n, din, dh, dout):
     return int(_lib.lib().gshac_mlp2_slab_rows(int(n), int(din), int(dh), int(dout)))
 
 
-def _forward(x, w1, b1, w2, b2, act, slope):
+def mlp2_forward(x, w1, b1, w2, b2, act="relu", slope=0.0):
+    """W2 act(W1 x + b1) + b2 without autograd, x (n, din) -> (n, dout): the ONE call of gshac_mlp2_act from Python -- the codecs' context MLPs
+    (anchor_codec.run_mlp2, hac_codec.mlp2, hac_plus_codec.mlp2_act) and `mlp2` below end here.  Any float dtype and strides."""
+    x, w1, b1, w2, b2 = (t.detach().contiguous().float() for t in (x, w1, b1, w2, b2))
     n, din = x.shape
     dh, dout = w1.shape[0], w2.shape[0]
     y = torch.empty(n, dout, device=x.device, dtype=torch.float32)
     if n == 0:          # nothing to launch (and an empty tensor has no address to pass)
         return y
-    _lib.check(_lib.lib().gshac_mlp2_act(runtime.context(x.device), ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), n, din, dh, dout, act, slope,
+    _lib.check(_lib.lib().gshac_mlp2_act(runtime.context(x.device), ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), n, din, dh, dout, _ACTS[act], float(slope),
                                          ptr(y), runtime.stream_ptr(x.device)))
     return y
 
@@ -45,8 +48,8 @@ class _MLP2(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2, act, slope):
         t = tuple(v.detach().contiguous() for v in (x, w1, b1, w2, b2))
         ctx.save_for_backward(*t)
-        ctx.act = (act, slope)
-        return _forward(*t, act, slope)
+        ctx.act = (_ACTS[act], slope)
+        return mlp2_forward(*t, act, slope)
 
     @staticmethod
     @once_differentiable
@@ -80,11 +83,10 @@ def mlp2(x, w1, b1, w2, b2, act="relu", slope=0.01):
         raise ValueError(f"mlp2: shapes x {tuple(x.shape)}, w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, w2 {tuple(w2.shape)}, b2 {tuple(b2.shape)}")
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
-    code, sl = _ACTS[act], float(slope)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, w1, b1, w2, b2)):
-        y = _MLP2.apply(x2, w1, b1, w2, b2, code, sl)
+        y = _MLP2.apply(x2, w1, b1, w2, b2, act, float(slope))
     else:
-        y = _forward(*(t.detach().contiguous() for t in (x2, w1, b1, w2, b2)), code, sl)
+        y = mlp2_forward(x2, w1, b1, w2, b2, act, slope)
     return y.view(*lead, w2.shape[0])
 
 

@@ -25,7 +25,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
 from .runtime import ptr, ptrs
-from .hac_codec import Q_FEAT, Q_OFFSETS, Q_SCALING, grid_mlp, ste_multistep
+from .anchor_codec import Q_FEAT, Q_OFFSETS, Q_SCALING, run_mlp2, ste_multistep
 
 
 def quant_steps(pc, anchor):
@@ -33,7 +33,7 @@ def quant_steps(pc, anchor):
     columns of mlp_grid's output whatever heads sit in front of them -- nine-way split (HAC: mean, scale, 2 x scaling, 2 x offsets) or
     ten-way (HAC++: + prob).  Returns (Q_feat (N, F), Q_scaling (N, 6), Q_offsets (N, 3 K)); HAC++ views the last as (N, K, 3), the same values."""
     F, K = pc.feat_dim, pc.n_offsets
-    out = grid_mlp(pc, pc.calc_interp_feat(anchor))
+    out = run_mlp2(pc.get_grid_mlp, pc.calc_interp_feat(anchor))
     nine, ten = 2 * F + 12 + 6 * K + 3, 3 * F + 12 + 6 * K + 3
     if out.shape[1] not in (nine, ten):
         raise ValueError(f"mlp_grid returns {out.shape[1]} columns; HAC has {nine} (feat_dim {F}, {K} offsets), HAC++ {ten}")

@@ -22,32 +22,27 @@ The reference's loop samples the planes, runs the MLP and builds, integerises an
 (3 000 tables and 3 000 serial host chains per million anchors); rows are independent, so the slices of the one context pass are the per-slice
 results.  The attribute files are written and read by this pair (torchac_encodings.encoder_gaussian_slices has the reason).
 `ckpt_path`: the GausPcgc checkpoint (the reference looks beside its own sources; here the argument or $GAUSPCGC_CKPT).
+The steps shared with HAC, HAC++ and CAT-3DGS (slice geometry, xyz_pcc.bin, masks.b, fill back and parameter replacement, the MLP dispatch) are
+gauspcc_amd.anchor_codec's.
 """
 import os
 import time
 
 import torch
 
+from .anchor_codec import (Q_FEAT, Q_OFFSETS, Q_SCALING, bit2MB_scale, decode_anchors, decode_mask_stream, encode_anchors, encode_mask_stream,
+                           install_decoded, n_slices, offset_bounds, offsets_mask, run_mlp2, slice_bounds, slice_file_names, ste_multistep, zero_filled)
 from .encodings_cuda import deferred_writes
-from .hac_codec import default_ckpt_path, mlp2, ste_multistep
-from .pcc_utils import calculate_morton_order, compress_point_cloud, decompress_point_cloud
 from .torchac_encodings import decoder, decoder_gaussian_slices, encoder, encoder_gaussian_slices
 
 K = 4                              # TC-GS/scene/gaussian_model.py:32
-bit2MB_scale = 8 * 1024 * 1024     # :33
 MAX_BATCH_SIZE = 1_000             # :1173
-Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2   # :1206-1208
 _CONTEXT_ROWS = 1 << 17            # anchors per pass of the context (603 floats of features each: 0.3 GB at a time, whatever the scene's size)
 
 
 def tri_mlp(model, feat_context):
-    """model.get_tri_mlp(feat_context).  An nn.Sequential(Linear, ReLU, Linear) -- what TC-GS builds -- goes through gshac_mlp2; anything else is
-    called as it is."""
-    m = model.get_tri_mlp
-    mods = list(m) if isinstance(m, torch.nn.Sequential) else []
-    if len(mods) == 3 and isinstance(mods[0], torch.nn.Linear) and isinstance(mods[1], torch.nn.ReLU) and isinstance(mods[2], torch.nn.Linear):
-        return mlp2(feat_context, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias)
-    return m(feat_context)
+    """model.get_tri_mlp(feat_context): the nn.Sequential(Linear, ReLU, Linear) TC-GS builds on the device kernel (anchor_codec.run_mlp2)."""
+    return run_mlp2(model.get_tri_mlp, feat_context)
 
 
 def _context(model, anchor):
@@ -73,22 +68,6 @@ def _context(model, anchor):
     }
 
 
-def _steps(N, max_batch):
-    return (N // max_batch) if (N % max_batch) == 0 else (N // max_batch + 1)
-
-
-def _names(pre_path_name, stem, steps):
-    return [os.path.join(pre_path_name, f'{stem}.b').replace('.b', f'_{s}.b') for s in range(steps)]
-
-
-def _offset_bounds(mask, N, bounds):
-    """kept (masked-in) offset elements up to each slice boundary: only the sums at the boundaries leave the device"""
-    if N == 0:
-        return [0] * len(bounds)
-    kept = torch.cumsum(mask.view(N, -1).sum(dim=1), dim=0)
-    return [0] + kept[torch.tensor([b - 1 for b in bounds[1:]], dtype=torch.long, device=kept.device)].cpu().tolist()
-
-
 @torch.no_grad()
 def conduct_encoding(self, pre_path_name, ckpt_path=None):
     t_codec = 0
@@ -103,26 +82,19 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
     N = _anchor.shape[0]
 
     # AI-PCC (:1155-1169)
-    _anchor_int = torch.round(_anchor / self.voxel_size)
-    sorted_indices = calculate_morton_order(_anchor_int)
-    _anchor_int = _anchor_int[sorted_indices]
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    out = compress_point_cloud(_anchor_int, ckpt_path or default_ckpt_path(), npz_path)
-    bits_xyz = out['file_size_bits']
-
-    _anchor = _anchor_int * self.voxel_size
+    _anchor, sorted_indices, bits_xyz = encode_anchors(_anchor, self.voxel_size, ckpt_path, pre_path_name)
     _feat = _feat[sorted_indices]
     _grid_offsets = _grid_offsets[sorted_indices]
     _scaling = _scaling[sorted_indices]
     _mask = _mask[sorted_indices]
 
     MAX_batch_size = MAX_BATCH_SIZE
-    steps = _steps(N, MAX_batch_size)
+    steps = n_slices(N, MAX_batch_size)
     n_off = self.n_offsets
     anchor_infos_list = [None] * steps                                   # (:1211-1212)
     hash_b_name = os.path.join(pre_path_name, 'hash.b')
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
-    bounds = [min(s * MAX_batch_size, N) for s in range(steps + 1)]
+    bounds = slice_bounds(N, MAX_batch_size)
 
     c = _context(self, _anchor)
     torch.cuda.synchronize(); t0 = time.time()
@@ -130,19 +102,20 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
         Q = c["Q_feat"]
         feat = ste_multistep(_feat.reshape(-1), Q, _feat.mean())
         bit_feat_list, min_feat_list, max_feat_list = encoder_gaussian_slices(
-            feat, c["mean"], c["scale"], Q, [b * self.feat_dim for b in bounds], _names(pre_path_name, 'feat', steps))
+            feat, c["mean"], c["scale"], Q, [b * self.feat_dim for b in bounds], slice_file_names(pre_path_name, 'feat', steps))
 
         Q = c["Q_scaling"]
         scaling = ste_multistep(_scaling.reshape(-1), Q, _scaling.mean())
         bit_scaling_list, min_scaling_list, max_scaling_list = encoder_gaussian_slices(
-            scaling, c["mean_scaling"], c["scale_scaling"], Q, [b * 6 for b in bounds], _names(pre_path_name, 'scaling', steps))
+            scaling, c["mean_scaling"], c["scale_scaling"], Q, [b * 6 for b in bounds], slice_file_names(pre_path_name, 'scaling', steps))
 
-        mask = _mask.repeat(1, 1, 3).view(-1, 3 * n_off).view(-1).to(torch.bool)   # [N*K*3]
+        mask = offsets_mask(_mask)   # [N*K*3]
         Q = c["Q_offsets"]
         offsets = ste_multistep(_grid_offsets.reshape(-1, 3 * n_off).reshape(-1), Q, _grid_offsets.mean())
         offsets[~mask] = 0.0
         bit_offsets_list, min_offsets_list, max_offsets_list = encoder_gaussian_slices(
-            offsets[mask], c["mean_offsets"][mask], c["scale_offsets"][mask], Q[mask], _offset_bounds(mask, N, bounds), _names(pre_path_name, 'offsets', steps))
+            offsets[mask], c["mean_offsets"][mask], c["scale_offsets"][mask], Q[mask], offset_bounds(mask, N, bounds),
+            slice_file_names(pre_path_name, 'offsets', steps))
     torch.cuda.synchronize(); t_codec += time.time() - t0
 
     bit_anchor = bits_xyz
@@ -160,11 +133,7 @@ def conduct_encoding(self, pre_path_name, ckpt_path=None):
         prob_hash = 0
         bit_hash = hash_embeddings.numel() * 32
 
-    mask = _mask  # {0, 1}; the slices' indices concatenated are 0 .. N - 1 (:1289-1291)
-    p = torch.zeros_like(mask).to(torch.float32)
-    prob_masks = (mask.sum() / mask.numel()).item()
-    p[...] = prob_masks
-    bit_masks = encoder((mask * 2 - 1).view(-1), p.view(-1), file_name=masks_b_name)
+    bit_masks, prob_masks = encode_mask_stream(_mask, masks_b_name)      # {0, 1}; the slices' indices concatenated are 0 .. N - 1 (:1289-1296)
 
     torch.cuda.synchronize(); t2 = time.time()
     print('encoding time:', t2 - t1)
@@ -190,18 +159,13 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
     print('Start decoding ...')
     [N_full, N, MAX_batch_size, anchor_infos_list, min_feat_list, max_feat_list, min_scaling_list, max_scaling_list, min_offsets_list, max_offsets_list,
      prob_hash, prob_masks] = patched_infos
-    steps = _steps(N, MAX_batch_size)
+    steps = n_slices(N, MAX_batch_size)
     n_off = self.n_offsets
     dev = self._anchor_feat.device
-    nn = torch.nn
     hash_b_name = os.path.join(pre_path_name, 'hash.b')
     masks_b_name = os.path.join(pre_path_name, 'masks.b')
 
-    p = torch.zeros(size=[N, n_off, 1], device=dev).to(torch.float32)
-    p[...] = prob_masks
-    masks_decoded = decoder(p.view(-1), masks_b_name)  # {-1, 1}
-    masks_decoded = (masks_decoded + 1) / 2  # {0, 1}
-    masks_decoded = masks_decoded.view(-1, n_off, 1)
+    masks_decoded = decode_mask_stream(N, n_off, prob_masks, masks_b_name, dev)      # (:1326-1331) {0, 1}
 
     if self.ste_binary:
         p = torch.zeros_like(self.get_encoding_params()).to(torch.float32)
@@ -209,24 +173,19 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
         hash_embeddings = decoder(p.view(-1), hash_b_name)  # {-1, 1}
         hash_embeddings = hash_embeddings.view(-1, self.feat_dim, self.resolution, self.resolution)
 
-    npz_path = os.path.join(pre_path_name, 'xyz_pcc.bin')
-    anchor_decoded = decompress_point_cloud(npz_path, ckpt_path or default_ckpt_path())
-    _anchor_int_dec = anchor_decoded['point_cloud'].to(dev)
-    sorted_indices = calculate_morton_order(_anchor_int_dec)
-    _anchor_int_dec = _anchor_int_dec[sorted_indices]
-    anchor_decoded = _anchor_int_dec * self.voxel_size
+    anchor_decoded = decode_anchors(pre_path_name, ckpt_path, self.voxel_size, dev)      # (:1347-1354)
     N = anchor_decoded.shape[0]
 
     c = _context(self, anchor_decoded)
-    bounds = [min(s * MAX_batch_size, N) for s in range(steps + 1)]
-    feat_decoded = decoder_gaussian_slices(c["mean"], c["scale"], c["Q_feat"], [b * self.feat_dim for b in bounds], _names(pre_path_name, 'feat', steps),
+    bounds = slice_bounds(N, MAX_batch_size)
+    feat_decoded = decoder_gaussian_slices(c["mean"], c["scale"], c["Q_feat"], [b * self.feat_dim for b in bounds], slice_file_names(pre_path_name, 'feat', steps),
                                            min_feat_list, max_feat_list).view(N, self.feat_dim)
     scaling_decoded = decoder_gaussian_slices(c["mean_scaling"], c["scale_scaling"], c["Q_scaling"], [b * 6 for b in bounds],
-                                              _names(pre_path_name, 'scaling', steps), min_scaling_list, max_scaling_list).view(N, 6)
-    mask = masks_decoded.repeat(1, 1, 3).view(-1, 3 * n_off).view(-1).to(torch.bool)
+                                              slice_file_names(pre_path_name, 'scaling', steps), min_scaling_list, max_scaling_list).view(N, 6)
+    mask = offsets_mask(masks_decoded)
     mo = c["mean_offsets"]
-    offs = decoder_gaussian_slices(mo[mask], c["scale_offsets"][mask], c["Q_offsets"][mask], _offset_bounds(mask, N, bounds),
-                                   _names(pre_path_name, 'offsets', steps), min_offsets_list, max_offsets_list)
+    offs = decoder_gaussian_slices(mo[mask], c["scale_offsets"][mask], c["Q_offsets"][mask], offset_bounds(mask, N, bounds),
+                                   slice_file_names(pre_path_name, 'offsets', steps), min_offsets_list, max_offsets_list)
     offsets_decoded = torch.zeros_like(mo)
     offsets_decoded[mask] = offs
     offsets_decoded = offsets_decoded.view(N, -1).view(N, n_off, 3)  # [N, K, 3]
@@ -235,25 +194,11 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
     print('decoding time:', t2 - t1)
 
     # fill back N_full (:1429-1440)
-    _anchor = torch.zeros(size=[N, 3], device=dev)
-    _anchor_feat = torch.zeros(size=[N, self.feat_dim], device=dev)
-    _offset = torch.zeros(size=[N, n_off, 3], device=dev)
-    _scaling = torch.zeros(size=[N, 6], device=dev)
-    _mask = torch.zeros(size=[N, n_off, 1], device=dev)
-    _anchor[:N] = anchor_decoded
-    _anchor_feat[:N] = feat_decoded
-    _offset[:N] = offsets_decoded
-    _scaling[:N] = scaling_decoded
-    _mask[:N] = masks_decoded
+    filled = [zero_filled(t) for t in (anchor_decoded, feat_decoded, offsets_decoded, scaling_decoded, masks_decoded)]
 
     print('Start replacing parameters with decoded ones...')
-    self._anchor_feat = nn.Parameter(_anchor_feat)
-    self._offset = nn.Parameter(_offset)
-    self.decoded_version = True      # the accessors stop applying activations / quantisers (:1449)
-    self._anchor = nn.Parameter(_anchor)
-    self._scaling = nn.Parameter(_scaling)
-    self._mask = nn.Parameter(_mask)
+    install_decoded(self, *filled)      # (:1445-1455)
     if self.ste_binary:
-        self.triplane.planes = nn.Parameter(hash_embeddings)
+        self.triplane.planes = torch.nn.Parameter(hash_embeddings)
     print('Parameters are successfully replaced by decoded ones!')
     return f"\nDecTime {round(t2 - t1, 4)}"

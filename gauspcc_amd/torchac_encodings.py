@@ -159,6 +159,14 @@ def _slice_lens(slice_start, n):
     return ss, [b - a for a, b in zip(ss, ss[1:])]
 
 
+def host(vals):
+    """per-slice bounds as the encoder returned them (0-d tensors, or numbers) -> a float32 numpy array"""
+    import numpy as np
+    if all(isinstance(v, torch.Tensor) for v in vals):
+        return torch.stack([v.detach().reshape(()) for v in vals]).to(torch.float32).cpu().numpy()
+    return np.array([float(v) for v in vals], dtype=np.float32)
+
+
 def encoder_gaussian_slices(x, mean, scale, Q, slice_start, file_names):
     """encoder_gaussian for MANY slices of one attribute: slice s = elements [slice_start[s], slice_start[s + 1]) goes to file_names[s] as ONE raw
     torchac stream with its own min / max, as TC-GS's loop writes it per 1 000-anchor slice (TC-GS/scene/gaussian_model.py:1197-1271).  Returns
@@ -218,29 +226,14 @@ def decoder_gaussian_slices(mean, scale, Q, slice_start, file_names, min_values,
         parts = [decoder_gaussian(mean[a:b], scale[a:b], Q[a:b], file_name=fn, min_value=mn, max_value=mx)
                  for a, b, fn, mn, mx in zip(ss, ss[1:], file_names, min_values, max_values) if b > a]
         return torch.cat(parts, dim=0) if parts else torch.zeros(0, dtype=torch.float32)
-    import ctypes as C
-    import os
-
     import numpy as np
 
-    from . import _lib, arithmetic
-
-    def host(vals):
-        if all(isinstance(v, torch.Tensor) for v in vals):
-            return torch.stack([v.detach().reshape(()) for v in vals]).to(torch.float32).cpu().numpy()
-        return np.array([float(v) for v in vals], dtype=np.float32)
+    from . import arithmetic
+    from .encodings_cuda import _read_files
 
     mins, maxs = host(min_values), host(max_values)
-    n = len(file_names)
-    cp = (C.c_char_p * n)(*[os.fsencode(p) for p in file_names])
-    offs = (C.c_int64 * (n + 1))()
-    pb = C.c_void_p()
-    _lib.check(_lib.lib().gpcc_read_files(cp, n, 8, C.byref(pb), offs))         # one blob, valid until this thread's next call: decoded at once
-    offs = np.frombuffer(offs, dtype=np.int64)
-    blob = np.frombuffer((C.c_ubyte * max(int(offs[n]), 1)).from_address(pb.value), dtype=np.uint8)[:int(offs[n])]
+    blob, offs = _read_files(file_names)         # one blob, valid until this thread's next call: decoded at once
     cnt = np.diff(offs)
-    if cnt.size and int(cnt.max()) >= 1 << 31:
-        raise ValueError("decoder_gaussian_slices: a stream of 2 GiB or more")
     cont = lambda t, a, b: t[a:b].detach().contiguous()
     out = []
     for ga, gb in _slice_groups(lens):

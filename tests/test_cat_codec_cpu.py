@@ -1,6 +1,5 @@
 """Host-side pieces of gauspcc_amd.cat_codec (no GPU): the stage table of CAT-3DGS's channel-wise context chain, the pipeline schedule of
-gsac_decode_normal_chain restated in a few lines, and the slice bounds."""
-import os
+gsac_decode_normal_chain restated in a few lines, and the chain's class and switch (the slice geometry: tests/test_anchor_codec_cpu.py)."""
 import types
 
 import pytest
@@ -49,11 +48,6 @@ def test_stage_table(groups, on_s, on_o, n_offsets):
     assert len(st) == G + 2 <= cat_codec.CHAIN_MAX_STAGES
 
 
-def test_file_names():
-    assert cat_codec._names("/x/y", "feat2", 3) == [os.path.join("/x/y", f"feat2_{s}.b") for s in range(3)]
-    assert cat_codec._names("d", "offsets", 0) == []
-
-
 @pytest.mark.parametrize("groups,on_s,on_o", CONFIGS)
 @pytest.mark.parametrize("n_anchors", [1, 37, 499, 500])
 @pytest.mark.parametrize("block", [1, 7, 8, 16, 64])
@@ -91,19 +85,6 @@ def test_schedule_reads_only_what_earlier_steps_wrote(groups, on_s, on_o, n_anch
     for b in range(nblocks - W):
         last_read = b + max(lags)
         assert min(written[(k, b + W)] for k, s in enumerate(st) if s["feat_col"] >= 0) > last_read
-
-
-@pytest.mark.parametrize("N", [0, 1, 500, 501, 1037])
-def test_slice_and_offset_bounds(N):
-    b = cat_codec.slice_bounds(N)
-    steps = -(-N // 500)
-    assert len(b) == steps + 1 and b[0] == 0 and b[-1] == N
-    assert all(0 < y - x <= 500 for x, y in zip(b, b[1:])) and all(y - x == 500 for x, y in zip(b[:-1], b[1:-1]))
-    assert cat_codec._steps(N, 500) == steps
-    g = torch.Generator().manual_seed(N)
-    mask = torch.rand(N, 3 * K, generator=g) < 0.4
-    ob = cat_codec._offset_bounds(mask.reshape(-1), N, b)
-    assert ob == [int(mask[:x].sum()) for x in b]
 
 
 def test_chain_class_and_switch(monkeypatch):

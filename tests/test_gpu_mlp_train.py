@@ -74,19 +74,34 @@ def _slab(si):
 
 
 @pytest.mark.parametrize("si", range(len(ref.SHAPES)), ids=IDS)
-def test_forward_is_the_codecs_mlp_bit_for_bit(si):
-    from gauspcc_amd import hac_codec, hac_plus_codec
+def test_forward_is_the_codecs_mlp_bit_for_bit(si, orc):
+    """The codecs' MLP is the oracle's chain (tests/test_gpu_hac_codec.py::test_mlp2_matches_oracle_bit_for_bit); ContextMLP's forward and the
+    codecs' wrappers are one Python function, so the expectation here is the oracle itself."""
+    import numpy as np
 
     din, dh, dout, act = ref.SHAPES[si]
     d = _case(si, 3 * _slab(si) + 5)
     m = _ours(din, dh, dout, act, d["w"])
     x = d["x"].to(DEV)
     y = m(x)
-    ps = (m[0].weight, m[0].bias, m[2].weight, m[2].bias)
-    want = hac_codec.mlp2(x, *ps) if act == "relu" else hac_plus_codec.mlp2_act(x, *ps, ref.SLOPE)
-    assert y.requires_grad and torch.equal(y.detach(), want)
+    want = orc.mlp2(d["x"].numpy(), *(t.numpy() for t in d["w"]), slope=0.0 if act == "relu" else ref.SLOPE)
+    assert y.requires_grad and np.array_equal(y.detach().cpu().numpy(), want)
     with torch.no_grad():
-        assert torch.equal(m(x), want)
+        assert np.array_equal(m(x).cpu().numpy(), want)
+
+
+def test_no_rows_give_an_empty_result():
+    """The n == 0 guard of mlp.mlp2_forward, through every wrapper the codecs call: nothing is launched, the result is (0, dout) float32."""
+    from gauspcc_amd import anchor_codec, hac_codec, hac_plus_codec
+
+    m = nn.Sequential(nn.Linear(6, 9), nn.ReLU(True), nn.Linear(9, 4)).to(DEV)
+    leaky = nn.Sequential(nn.Linear(6, 9), nn.LeakyReLU(0.1), nn.Linear(9, 4)).to(DEV)
+    x = torch.zeros(0, 6, device=DEV)
+    ps = (m[0].weight, m[0].bias, m[2].weight, m[2].bias)
+    with torch.no_grad():
+        outs = [anchor_codec.run_mlp2(m, x), anchor_codec.run_mlp2(leaky, x), hac_codec.mlp2(x, *ps), hac_plus_codec.mlp2_act(x, *ps, 0.01)]
+    for y in outs:
+        assert y.shape == (0, 4) and y.dtype == torch.float32 and y.device == x.device
 
 
 @pytest.mark.parametrize("si", range(len(ref.SHAPES)), ids=IDS)

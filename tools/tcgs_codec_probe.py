@@ -73,7 +73,7 @@ def _parent_slice_context(torch, m, rows):
 def _parent_loop(torch, m, src, path, nslices):
     """the loop of the module docstring over the first nslices slices: (encode seconds, decode seconds, split, bytes, exact?)"""
     from gauspcc_amd import torchac_encodings as te
-    from gauspcc_amd.hac_codec import ste_multistep
+    from gauspcc_amd.anchor_codec import ste_multistep
 
     N, no = src["anchor"].shape[0], m.n_offsets
     means = {k: src[k].mean() for k in ("feat", "scaling", "offs")}
@@ -117,15 +117,13 @@ def _parent_loop(torch, m, src, path, nslices):
 
 
 def step_size(n, out_json):
-    import ctypes as C
-
     import numpy as np
     import torch
 
-    from gauspcc_amd import _lib, arithmetic, tcgs_codec
+    from gauspcc_amd import anchor_codec, arithmetic, tcgs_codec
     from gauspcc_amd import torchac_encodings as te
-    from gauspcc_amd.encodings_cuda import _write_files
-    from gauspcc_amd.hac_codec import ste_multistep
+    from gauspcc_amd.encodings_cuda import _read_files, _write_files
+    from gauspcc_amd.anchor_codec import ste_multistep
     from gauspcc_amd.synth import SyntheticGaussianModelTC
 
     res = dict(n=n)
@@ -160,16 +158,16 @@ def step_size(n, out_json):
     res["new_encode"], res["new_decode"] = _med(enc_t), _med(dec_t)
 
     # ---- here: the parts (context, coder, file I/O), measured apart from the calls above
-    bounds = [min(s * 1000, N) for s in range(steps + 1)]
+    bounds = anchor_codec.slice_bounds(N, 1000)
     ctx_t = [_sync_time(torch, lambda: tcgs_codec._context(m, src["anchor"]))[0] for _ in range(REPEATS)]
     c = tcgs_codec._context(m, src["anchor"])
-    mask = src["mask"].repeat(1, 1, 3).view(-1, 3 * no).view(-1).to(torch.bool)
+    mask = anchor_codec.offsets_mask(src["mask"])
     xs = dict(feat=ste_multistep(src["feat"].reshape(-1), c["Q_feat"], src["feat"].mean()),
               scaling=ste_multistep(src["scaling"].reshape(-1), c["Q_scaling"], src["scaling"].mean()),
               offsets=ste_multistep(src["offs"].reshape(-1), c["Q_offsets"], src["offs"].mean())[mask])
     par = dict(feat=(c["mean"], c["scale"], c["Q_feat"]), scaling=(c["mean_scaling"], c["scale_scaling"], c["Q_scaling"]),
                offsets=tuple(v[mask].contiguous() for v in (c["mean_offsets"], c["scale_offsets"], c["Q_offsets"])))
-    ss = dict(feat=[b * fd for b in bounds], scaling=[b * 6 for b in bounds], offsets=tcgs_codec._offset_bounds(mask, N, bounds))
+    ss = dict(feat=[b * fd for b in bounds], scaling=[b * 6 for b in bounds], offsets=anchor_codec.offset_bounds(mask, N, bounds))
     enc_c, dec_c, wr_t, rd_t = [], [], [], []
     for _ in range(REPEATS):
         dt, coded = _sync_time(torch, lambda: {k: arithmetic.encode_normal_streams(xs[k].contiguous(), *par[k], ss[k]) for k in xs})
@@ -185,10 +183,8 @@ def step_size(n, out_json):
                 _write_files([(os.path.join(d, f"{k}_{i}.b"), blob[int(off[i]):int(off[i + 1])]) for i in range(steps)])
             wr_t.append(time.perf_counter() - t0)
             t0 = time.perf_counter()
-            for k in xs:                                   # as decoder_gaussian_slices reads them: one gpcc_read_files call per attribute
-                paths = (C.c_char_p * steps)(*[os.fsencode(os.path.join(d, f"{k}_{i}.b")) for i in range(steps)])
-                offs, pb = (C.c_int64 * (steps + 1))(), C.c_void_p()
-                _lib.check(_lib.lib().gpcc_read_files(paths, steps, 8, C.byref(pb), offs))
+            for k in xs:                                   # as decoder_gaussian_slices reads them: one _read_files call per attribute
+                _, offs = _read_files([os.path.join(d, f"{k}_{i}.b") for i in range(steps)])
                 assert offs[steps] == int(coded[k][3].sum())
             rd_t.append(time.perf_counter() - t0)
     res["new_coder_exact"] = all(bool(torch.equal(back[k], xs[k])) for k in xs)
