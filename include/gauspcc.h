@@ -634,6 +634,51 @@ GPCC_API int gpcc_grow_voxels(gpcc_ctx *ctx, const float *xyz_dev, int64_t m, co
                               int64_t c, const float *anchors_dev, int64_t n, float inv, float size, int64_t *count_out, gsr_alloc_fn alloc,
                               void *alloc_user, void *stream);
 
+/* ================= Densification statistics (HAC/scene/gaussian_model.py:758-775 training_statis, :914-968 adjust_anchor) =================
+ * One iteration of training_statis, in place, enqueued on `stream` with NO host synchronisation.  n anchors of k offsets; visible (n) bytes
+ * or NULL (all; then v must equal n); opacity (v k) float32, the neural opacity of the v visible anchors in order; selection (v k) bytes;
+ * update_filter (s) bytes; grad (s rows of grad_stride >= 2 floats, columns 0 and 1 read); the accumulators opacity_accum, anchor_demon (n)
+ * and offset_gradient_accum, offset_denom (n k) float32.  With v(a) = the visible anchors before a and s(j) = the set selection entries
+ * before j, for every visible a, in float32 without contraction:
+ *   opacity_accum[a] += ((0.0f + c_0) + c_1) + ... + c_{k-1},  c_i = o_i < 0 ? 0 : o_i,  o_i = opacity[v(a) k + i]  (a NaN stays one)
+ *   anchor_demon[a] += 1
+ *   for every i with selection[j] set, j = v(a) k + i, and update_filter[s(j)] set, g = grad row s(j):
+ *     offset_gradient_accum[a k + i] += sqrtf(g[0] g[0] + g[1] g[1])  (each product, the sum and the root rounded once),  offset_denom[a k + i] += 1
+ * Every destination has one source: no atomics, bitwise reproducible.  The host knows v and s from shapes only.  When count(visible) != v
+ * or count(selection) != s the update writes NOTHING to the accumulators and forms no index from a rank (the scans are complete before it
+ * starts and it compares their totals first); it sets err[0] |= 1 (visible) | 2 (selection) and err[1..4] = count(visible), v,
+ * count(selection), s.  err: 8 uint32 words of device memory owned by the caller, zero before the first call; the caller reads them at its
+ * next synchronisation.  alloc is called once, for 8 (max(n, v) + 1) bytes plus 512 that the call no longer needs once its kernels have
+ * run.  n, v < 2^28, k <= 256, n k and v k < 2^31. */
+GPCC_API int gpcc_densify_stats(gpcc_ctx *ctx, int64_t n, int k, const uint8_t *visible_dev, const float *opacity_dev, int64_t v,
+                                const uint8_t *selection_dev, const uint8_t *update_filter_dev, int64_t s, const float *grad_dev, int64_t grad_stride,
+                                float *opacity_accum_dev, float *anchor_demon_dev, float *offset_gradient_accum_dev, float *offset_denom_dev,
+                                uint32_t *err_dev, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
+/* The head of adjust_anchor over total = n0 k entries: g = offset_gradient_accum / offset_denom in float32 (correctly rounded),
+ * grads_norm = g != g ? 0 : fabsf(g) (0/0 and every other NaN give 0), offset_mask = offset_denom > offset_thr (bytes 0 / 1).  One launch,
+ * no synchronisation. */
+GPCC_API int gpcc_densify_front(gpcc_ctx *ctx, const float *offset_gradient_accum_dev, const float *offset_denom_dev, int64_t total, float offset_thr,
+                                float *grads_norm_out_dev, uint8_t *offset_mask_out_dev, void *stream);
+
+/* The tail of adjust_anchor, after the framework's anchor_growing has grown opacity_accum and anchor_demon from n0 to n1 >= n0 rows.
+ * anchors_mask[a] = anchor_demon[a] > anchor_thr; prune[a] = opacity_accum[a] < min_opacity * anchor_demon[a] (one rounded float32
+ * product) && anchors_mask[a], written to prune_out (n1 bytes).  *count_out = n2 = n1 - count(prune).  For the survivors, in order:
+ * offset_gradient_accum and offset_denom rows (k each) with the entries of a set offset_mask (n0 k bytes) zeroed and rows of anchors
+ * >= n0 zero; opacity_accum and anchor_demon, zero where anchors_mask is set.  alloc is called (1) once for 4 (n1 + 1) bytes of ranks, not
+ * needed once the kernels have run, then, only when n2 > 0, (2)-(5) for offset_gradient_accum (n2 k), offset_denom (n2 k), opacity_accum
+ * (n2), anchor_demon (n2) floats.  One scan, one gather pass, one synchronisation (the read-back of n2).  n1 < 2^28, n1 k < 2^31. */
+GPCC_API int gpcc_densify_finish(gpcc_ctx *ctx, const float *offset_gradient_accum_dev, const float *offset_denom_dev, const uint8_t *offset_mask_dev,
+                                 int64_t n0, int k, const float *opacity_accum_dev, const float *anchor_demon_dev, int64_t n1, float anchor_thr,
+                                 float min_opacity, uint8_t *prune_out_dev, int64_t *count_out, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
+/* Row compaction of nmats <= 32 float32 matrices of n rows: src[t] (n, widths[t]) device, keep (n) bytes.  *count_out = n2 = count(keep);
+ * alloc is called (1) once for 4 (n + 1) bytes of ranks, then, only when n2 > 0, once per matrix in order for its n2 widths[t] floats:
+ * the kept rows in order.  One scan, one launch over all matrices, one synchronisation (the read-back of n2).  n < 2^28,
+ * n widths[t] < 2^31.  src and widths are host arrays. */
+GPCC_API int gpcc_compact_rows(gpcc_ctx *ctx, const uint8_t *keep_dev, int64_t n, int nmats, const float *const *src, const int64_t *widths,
+                               int64_t *count_out, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
 /* ================= Photometric loss (training step, HAC/utils/loss_utils.py: ssim, l1_loss; train.py's loss) =================
  * img1, img2 (batch, channels, height, width) float32 device, contiguous.  SSIM of every plane with the reference's window: the outer
  * product of taps (window_size float32 HOST values: the caller builds them as the reference does, Gaussian taps of sigma 1.5 normalised
