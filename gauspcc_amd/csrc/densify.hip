@@ -3,6 +3,7 @@
 //   gpcc_densify_front   adjust_anchor's head: grads_norm = |accum / denom| (NaN -> 0) and offset_mask
 //   gpcc_densify_finish  adjust_anchor's tail: the prune mask and the four accumulators of the survivors
 //   gpcc_compact_rows    the kept rows of up to 32 float32 matrices, one scan and one launch
+//   gpcc_expand_rows     its transpose (the backward of the gather): kept rows back at their positions, zero rows elsewhere, no synchronisation
 // The contracts are in include/gauspcc.h.  No float atomics: every destination has exactly one source lane.
 //
 // gpcc_densify_stats.  The torch sequence finds its destinations with four boolean-mask index operations, each a nonzero() and a wait for the
@@ -171,6 +172,22 @@ __global__ __launch_bounds__(TB) void k_compact(Mats mats, const uint8_t *__rest
     mats.dst[blockIdx.y][(uint64_t)rank[row] * w + col] = mats.src[blockIdx.y][i];
 }
 
+// The transpose of k_compact: blockIdx.y = the matrix, a lane per element of the n-row destination.  rank == nullptr: no row is kept.
+// A kept row whose rank is not below m (a mask that does not count m rows) reads nothing and gets zeros.
+__global__ __launch_bounds__(TB) void k_expand(Mats mats, const uint8_t *__restrict__ keep, const uint32_t *__restrict__ rank, uint32_t n, uint32_t m)
+{
+    const uint32_t w = mats.width[blockIdx.y];
+    const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= (uint64_t)n * w) return;
+    const uint32_t row = (uint32_t)i / w, col = (uint32_t)i - row * w;   // n w < 2^31 (checked by the host)
+    float v = 0.0f;
+    if (rank && keep[row]) {
+        const uint32_t r = rank[row];
+        if (r < m) v = mats.src[blockIdx.y][(uint64_t)r * w + col];
+    }
+    mats.dst[blockIdx.y][i] = v;
+}
+
 // the survivors' count, the call's one synchronisation
 int read_count(gpcc_ctx *ctx, hipStream_t st, const uint32_t *word, int64_t *count)
 {
@@ -288,6 +305,39 @@ extern "C" int gpcc_compact_rows(gpcc_ctx *ctx, const uint8_t *keep, int64_t n, 
     for (int t = 0; t < nmats; ++t) GP_TRY(caller_alloc(alloc, alloc_user, sizeof(float) * (size_t)(n2 * widths[t]), &mats.dst[t], "gpcc_compact_rows: outputs"));
     if (wmax == 0) return GPCC_OK;
     k_compact<<<dim3((unsigned)cdiv(n * wmax, TB), (unsigned)nmats), TB, 0, st>>>(mats, keep, rank, (uint32_t)n);
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
+
+extern "C" int gpcc_expand_rows(gpcc_ctx *ctx, const uint8_t *keep, int64_t n, int64_t m, int nmats, const float *const *src, const int64_t *widths, float *const *dst,
+                                gsr_alloc_fn alloc, void *alloc_user, void *stream)
+{
+    if (!ctx) return fail(GPCC_ERR_ARG, "gpcc_expand_rows: null context");
+    if (n < 0 || n >= ROWS_MAX || m < 0 || m > n || nmats < 0 || nmats > MAX_MATS)
+        return fail(GPCC_ERR_ARG, "gpcc_expand_rows: n = %lld (< 2^28), m = %lld (0..n), %d matrices (<= %d)", (long long)n, (long long)m, nmats, MAX_MATS);
+    if (nmats > 0 && (!src || !widths || !dst)) return fail(GPCC_ERR_ARG, "gpcc_expand_rows: null argument");
+    Mats mats = {};
+    int64_t wmax = 0;
+    for (int t = 0; t < nmats; ++t) {
+        if (widths[t] < 0 || (n > 0 && widths[t] > (((int64_t)1 << 31) - 1) / n) || (n > 0 && widths[t] > 0 && (!dst[t] || (m > 0 && !src[t]))))
+            return fail(GPCC_ERR_ARG, "gpcc_expand_rows: matrix %d of width %lld (n width < 2^31, non-null)", t, (long long)widths[t]);
+        mats.src[t] = src[t];
+        mats.dst[t] = dst[t];
+        mats.width[t] = (uint32_t)widths[t];
+        wmax = widths[t] > wmax ? widths[t] : wmax;
+    }
+    if (n == 0 || nmats == 0 || wmax == 0) return GPCC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *rank = nullptr;
+    if (m > 0) {   // m == 0: every row is zero, no scan
+        if (!keep || !alloc) return fail(GPCC_ERR_ARG, "gpcc_expand_rows: null argument");
+        GP_TRY(caller_alloc(alloc, alloc_user, sizeof(uint32_t) * (size_t)(n + 1), &rank, "gpcc_expand_rows: ranks"));
+        k_keep_flags<<<(unsigned)cdiv(n + 1, TB), TB, 0, st>>>(keep, n, rank);
+        LAUNCH_CHECK();
+        GP_TRY(exclusive_scan_u32(ctx, st, rank, rank, n + 1, nullptr));
+    }
+    k_expand<<<dim3((unsigned)cdiv(n * wmax, TB), (unsigned)nmats), TB, 0, st>>>(mats, keep, rank, (uint32_t)n, (uint32_t)m);
     LAUNCH_CHECK();
     return GPCC_OK;
 }

@@ -1031,8 +1031,9 @@ __global__ __launch_bounds__(256) void k_ngb_wsum(NGWArgs a)
     const int idx = blockIdx.x * 256 + threadIdx.x, m = s.m0 + idx / 64, c = idx % 64;
     if (m >= s.M || m >= s.m0 + 64 || c >= s.N) return;
     const float *p = a.partial + (int64_t)blockIdx.y * a.ranges * 4096 + idx;
-    float v = 0.0f;
-    for (int r = 0; r < a.ranges; ++r) v += p[(int64_t)r * 4096];
+    double sum = 0.0;
+    for (int r = 0; r < a.ranges; ++r) sum += (double)p[(int64_t)r * 4096];
+    const float v = (float)sum;
     if (c < s.N - 1) s.w[(int64_t)m * (s.N - 1) + c] = v;
     else s.b[m] = v;
 }
@@ -1094,8 +1095,10 @@ extern "C" int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offse
         return fail(GPCC_ERR_ARG, "null argument");
     const int64_t np = (n + 15) / 16 * 16;
     const int ncol = (F + 5) + 3 * (F + 1) + 3 * F + 11 * K + (bank ? 5 + (F + 1) + F + 3 : 0);
-    // anchor ranges of the weight-gradient pass: a function of n only
-    const int ranges = (int)std::min<int64_t>(256, cdiv(np, 2048));
+    // anchor ranges of the weight-gradient pass: a function of n only.  A range's float32 accumulator runs over few anchors (64 up to 16384
+    // anchors, n / 256 beyond: the partials are 64 KB per range and strip) and k_ngb_wsum adds the partials in double: with 2048 anchors per
+    // range a bias gradient over 2400 anchors was 5 float32 ulp off, where torch's tree sum stays within 1.
+    const int ranges = (int)std::min<int64_t>(256, cdiv(np, 64));
     const int64_t chunk = cdiv(cdiv(np, ranges), 16) * 16;
     NGWArgs w = {};
     w.np = np; w.chunk = chunk; w.ranges = ranges;

@@ -1,6 +1,7 @@
 """Densification bookkeeping on the device: drop-ins for `GaussianModel.training_statis` and `GaussianModel.adjust_anchor` of HAC, HAC++,
 TC-GS and CAT-3DGS (e.g. HAC/scene/gaussian_model.py:758-775 and :914-968; the four files hold the same program), and the multi-tensor
-row compaction that `_prune_anchor_optimizer` needs.
+row compaction that `_prune_anchor_optimizer` needs, with its differentiable form `select_rows` (the masked gathers of the training branches;
+backward: gpcc_expand_rows).
 
 `training_statis` is one native call (gpcc_densify_stats) that never waits for the host: the reference's four boolean-mask index
 operations are two scans and one update pass.  What the host cannot know from shapes -- that the visible mask counts as many anchors as
@@ -156,6 +157,60 @@ def compact_rows(keep, *tensors):
     if n2 == 0:
         return [torch.empty((0, *t.shape[1:]), dtype=torch.float32, device=dev) for t in tensors]
     return [_floats(work.buffers[1 + i], n2, *t.shape[1:]) for i, t in enumerate(tensors)]   # allocation (1) is the ranks
+
+
+def _check_rows(who, keep, tensors):
+    """the argument checks of select_rows: ValueErrors that name the argument"""
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.dim() != 1 or not keep.is_contiguous() or not keep.is_cuda:
+        raise ValueError(f"{who}: mask must be a contiguous 1-D bool CUDA tensor")
+    if len(tensors) > MAX_TENSORS:
+        raise ValueError(f"{who}: {len(tensors)} tensors, at most {MAX_TENSORS} in one call")
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != keep.device:
+            raise ValueError(f"{who}: tensor {i} must be a float32 CUDA tensor on the mask's device")
+        if t.dim() < 1 or t.shape[0] != keep.shape[0]:
+            raise ValueError(f"{who}: tensor {i} must have {keep.shape[0]} rows, got {tuple(t.shape)}")
+
+
+class _SelectRows(torch.autograd.Function):
+    """gpcc_compact_rows / gpcc_expand_rows over all tensors at once"""
+
+    @staticmethod
+    def forward(ctx, keep, *tensors):
+        outs = compact_rows(keep, *tensors)
+        ctx.keep, ctx.m, ctx.shapes = keep, (outs[0].shape[0] if outs else 0), [t.shape for t in tensors]
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        keep, m, dev = ctx.keep, ctx.m, ctx.keep.device
+        N = keep.shape[0]
+        want = [i for i in range(len(grads)) if ctx.needs_input_grad[1 + i]]
+        out = [None] * len(grads)
+        if want:
+            srcs = [torch.zeros((m, *ctx.shapes[i][1:]), dtype=torch.float32, device=dev) if grads[i] is None else grads[i].detach().to(torch.float32).contiguous()
+                    for i in want]
+            dsts = [torch.empty(ctx.shapes[i], dtype=torch.float32, device=dev) for i in want]
+            widths = [int(np.prod(ctx.shapes[i][1:], dtype=np.int64)) for i in want]
+            T = len(want)
+            _lib.check(_lib.lib().gpcc_expand_rows(runtime.context(dev), _ptr(keep), N, m, T, runtime.ptrs([None if t.numel() == 0 else t for t in srcs], T),
+                                                   (ctypes.c_int64 * T)(*widths), runtime.ptrs([None if t.numel() == 0 else t for t in dsts], T),
+                                                   runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
+            for i, d in zip(want, dsts):
+                out[i] = d
+        return (None, *out)
+
+
+def select_rows(mask, *tensors):
+    """tuple(t[mask] for t in tensors), differentiable: the values and the gradients are those of the indexing, bit for bit.  The forward is
+    one gpcc_compact_rows call (one scan, one launch, one wait for the row count) where the indexing does a nonzero and a wait per tensor;
+    the backward is one gpcc_expand_rows call, without a wait, for all the tensors that need a gradient (the others get None).  Up to 32
+    float32 CUDA tensors of mask.shape[0] rows, any trailing shape; anything else raises a ValueError that names the argument."""
+    _check_rows("select_rows", mask, tensors)
+    if not tensors:
+        return ()
+    return _SelectRows.apply(mask, *tensors)
 
 
 def front(offset_gradient_accum, offset_denom, offset_thr):

@@ -11,6 +11,7 @@ test (:188-205) where HAC multiplies them into the opacity before it (:136-137) 
 `is_training=True` serves HAC's training branch (:47-98 and the 11-tuple of :170): the gathers, the quantisation noise, the
 context model's rate terms on the 5 % chosen anchors (the model's own torch modules: they train too) and then the differentiable core
 neural_gaussians_train (gsnn_forward_train / gsnn_backward), which HAC++, TC-GS and CAT-3DGS callers can use after their own rate code.
+HAC++'s training branch is gauspcc_amd.hac_plus_renderer, built on that core and on quant_noise below (gsnn_noise_forward / _backward).
 The model `pc` is used through the attributes the reference uses.  When `pc.decoded_version` is false the attributes are first quantised
 with the context model's step sizes exactly as the reference does (:103-114); everything after that -- view vectors,
 feature bank, the three MLPs, masking, assembly -- is ONE call into libgauspcc (gsnn_generate: two kernels and a scan
@@ -18,6 +19,7 @@ instead of ~40 PyTorch kernels and an (n K, 22) concatenate / mask / split).  Fo
 index list: the kernels read those rows of the model's tensors in place instead of five `tensor[visible_mask]` copies.
 """
 import ctypes as C
+import math
 import time
 
 import torch
@@ -182,6 +184,90 @@ def neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, masks, cam_
         raise _lib.GpccError(-1, f"neural_gaussians_train: feat_dim must be 32 or 50 and n_offsets 1..64 (got {F}, {K})")
     cam = cam_center.reshape(3)
     return _NeuralGaussians.apply(bool(mask_after_opacity), anchor, feat, grid_offsets, grid_scaling, masks, cam, *_mlp_params(pc))
+
+
+def _noise_args(xs, us, q0s, adj, cols):
+    """(n, widths, the ctypes arrays gsnn_noise_* share) after the argument checks"""
+    who = "quant_noise"
+    T = len(xs)
+    if not 1 <= T <= 3 or len(us) != T or len(q0s) != T:
+        raise ValueError(f"{who}: xs, us and q0s must hold the same number (1..3) of entries, got {len(xs)}, {len(us)}, {len(q0s)}")
+    n = xs[0].shape[0] if isinstance(xs[0], torch.Tensor) and xs[0].dim() >= 1 else -1
+    for name, ts in (("xs", xs), ("us", us)):
+        for j, t in enumerate(ts):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+                raise ValueError(f"{who}: {name}[{j}] must be a float32 CUDA tensor")
+            if t.dim() < 2 or t.shape != xs[j].shape or t.shape[0] != n or t.device != xs[0].device:
+                raise ValueError(f"{who}: {name}[{j}] of shape {tuple(t.shape)}: every attribute is (n, ...) and its noise has its shape")
+    widths = [math.prod(x.shape[1:]) for x in xs]
+    if any(w < 1 for w in widths):
+        raise ValueError(f"{who}: xs must have at least one column each")
+    if adj is not None:
+        if not isinstance(adj, torch.Tensor) or adj.dtype != torch.float32 or not adj.is_cuda or adj.device != xs[0].device:
+            raise ValueError(f"{who}: adj must be a float32 CUDA tensor on the attributes' device")
+        cols = list(range(T)) if cols is None else [int(c) for c in cols]
+        if adj.dim() != 2 or adj.shape[0] != n or len(cols) != T or any(not 0 <= c < adj.shape[1] for c in cols):
+            raise ValueError(f"{who}: adj must be ({n}, >= {T}) and cols name {T} of its columns, got {tuple(adj.shape)} and {cols}")
+    elif cols is not None:
+        raise ValueError(f"{who}: cols without adj")
+    return n, widths, (C.c_int64 * T)(*widths), (C.c_double * T)(*[float(q) for q in q0s]), None if adj is None else (C.c_int * T)(*cols)
+
+
+def _adj_view(adj):
+    """adj as the kernels read it in place: unit column stride and rows that do not overlap (a column slice of mlp_grid's output is one)"""
+    return adj if adj.stride(1) == 1 and adj.stride(0) >= adj.shape[1] else adj.contiguous()
+
+
+class _QuantNoise(torch.autograd.Function):
+    """gsnn_noise_forward / gsnn_noise_backward.  Inputs: adj (or None), then the attributes; the noise and the rest ride on `cfg`."""
+
+    @staticmethod
+    def forward(ctx, cfg, adj, *xs):
+        us, q0s, cols = cfg
+        n, widths, c_w, c_q, c_cols = _noise_args(xs, us, q0s, adj, cols)
+        dev, T = xs[0].device, len(xs)
+        xc = [x.detach().contiguous() for x in xs]
+        uc = [u.detach().contiguous() for u in us]
+        ys = [torch.empty_like(x) for x in xc]
+        q = torch.empty(n, T, device=dev)
+        a = None if adj is None else _adj_view(adj.detach())
+        if n:
+            _lib.check(_lib.lib().gsnn_noise_forward(runtime.context(dev), n, T, ptrs(xc), ptrs(uc), c_w, c_q, ptr(a), a.stride(0) if a is not None else 0, c_cols,
+                                                     ptrs(ys), q.data_ptr(), runtime.stream_ptr(dev)))
+        ctx.cfg = (n, T, c_w, c_q, c_cols, uc, a)
+        return (*ys, q)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        n, T, c_w, c_q, c_cols, uc, a = ctx.cfg
+        gs, gq = grads[:T], grads[T]
+        d_adj = None
+        if a is not None and ctx.needs_input_grad[1]:
+            dev = uc[0].device
+            gc = [torch.zeros_like(u) if g is None else g.detach().contiguous() for g, u in zip(gs, uc)]
+            d = torch.empty(n, T, device=dev)
+            gqc = None if gq is None else gq.detach().contiguous()
+            if n:
+                _lib.check(_lib.lib().gsnn_noise_backward(runtime.context(dev), n, T, ptrs(gc), ptrs(uc), c_w, c_q, a.data_ptr(), a.stride(0), c_cols, ptr(gqc),
+                                                          d.data_ptr(), runtime.stream_ptr(dev)))
+            cols = list(c_cols)
+            if a.shape[1] == T and cols == list(range(T)):
+                d_adj = d
+            else:
+                d_adj = torch.zeros(a.shape, device=dev)
+                d_adj[:, cols] = d
+        return (None, d_adj, *gs)       # dx_j is the incoming gradient itself
+
+
+def quant_noise(xs, us, q0s, adj=None, cols=None):
+    """The adaptive-step quantisation noise on up to three row-aligned attributes in one launch (gsnn_noise_forward):
+    y_j = xs[j] + us[j] * Q_j with Q_j[r] = q0s[j] * (1 + tanh(adj[r, cols[j]])), or the constant q0s[j] without adj.  us are the caller's
+    U(-0.5, 0.5) draws, shaped as xs.  adj is read in place: a column slice of mlp_grid's output costs no copy (cols default to 0, 1, ...).
+    Returns (y_0, ..., Q) with Q (n, len(xs)) the per-row steps, which the rate modules take as (n, 1) operands.  Differentiable in xs (the
+    gradient is the incoming tensor itself) and adj (gsnn_noise_backward, bitwise reproducible).  Float32 CUDA tensors only."""
+    _noise_args(xs, us, q0s, adj, cols)
+    return _QuantNoise.apply((list(us), list(q0s), cols), adj, *xs)
 
 
 def _generate_training(viewpoint_camera, pc, visible_mask, step):

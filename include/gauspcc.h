@@ -513,6 +513,24 @@ GPCC_API int gsnn_backward(gpcc_ctx *ctx, int64_t n, int feat_dim, int n_offsets
                            const float *g_nopa, float *d_anchor, float *d_feat, float *d_offsets, float *d_scaling, float *d_mask, float *const *d_mlp,
                            gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
+/* The adaptive-step quantisation noise of the training branch (HAC-plus/gaussian_renderer/__init__.py:47-51, 64-69, 91-99) on nattr <= 3
+ * row-aligned attributes of n rows in ONE launch: x[j], u[j], y[j] (n, widths[j]) float32 device, contiguous (any alignment of 4 bytes:
+ * the vector width is chosen per attribute from the width and the addresses); u is the caller's U(-0.5, 0.5) draw; q0[j] the base step
+ * (host, rounded to float32).  adj: the context MLP's output read in place -- adj[r adj_stride + adj_cols[j]] is row r's adjustment of
+ * attribute j -- or NULL for the constant step q0[j] (adj_stride, adj_cols unused).  Per element, in float32 without contraction:
+ *   Q_j[r] = q0_j * (1 + tanhf(adj[r, j]))  (q0_j without adj);  y_j[r, c] = x_j[r, c] + u_j[r, c] * Q_j[r];  q_out[r nattr + j] = Q_j[r]
+ * gsnn_noise_backward (adj must not be NULL): g[j] (n, widths[j]) the upstream gradients of the y_j, grad_q (n, nattr) that of q_out (NULL: none);
+ *   d_adj[r nattr + j] = ((S + grad_q[r nattr + j]) * q0_j) * fmaf(-t, t, 1),  t = tanhf(adj[r, j])  (= q0_j (1 - t^2) (S + grad_q)),
+ *   S = sum_c g_j[r, c] * u_j[r, c] in this fixed order: with L = 4 lanes for widths[j] <= 8 and 16 otherwise, lane l adds the rounded
+ *   products of the columns l, l + L, l + 2 L, ... in ascending order to 0.0f, then the L partial sums are added in a butterfly,
+ *   s_l += s_(l xor d) for d = 1, 2, ..., L / 2.  No atomics: bitwise reproducible.  The gradient of x_j is g[j] itself: nothing is written for it.
+ * n = 0 launches nothing.  n < 2^31, n widths[j] < 2^31.  x, u, y, g, widths, q0, adj_cols are host arrays.  Enqueued on `stream`, no synchronisation. */
+GPCC_API int gsnn_noise_forward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const float *const *u, const int64_t *widths,
+                                const double *q0, const float *adj, int64_t adj_stride, const int *adj_cols, float *const *y, float *q_out, void *stream);
+GPCC_API int gsnn_noise_backward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths,
+                                 const double *q0, const float *adj, int64_t adj_stride, const int *adj_cols, const float *grad_q, float *d_adj,
+                                 void *stream);
+
 /* ================= Gaussian splat rasteriser, forward (a20) =================
  * diff_gaussian_rasterization (Scaffold-GS fork; zip missing from the reference tree).  Mirrors the C++ API the
  * reference's viewer calls: CudaRasterizer::Rasterizer::visible_filter / ::forward,
@@ -678,6 +696,15 @@ GPCC_API int gpcc_densify_finish(gpcc_ctx *ctx, const float *offset_gradient_acc
  * n widths[t] < 2^31.  src and widths are host arrays. */
 GPCC_API int gpcc_compact_rows(gpcc_ctx *ctx, const uint8_t *keep_dev, int64_t n, int nmats, const float *const *src, const int64_t *widths,
                                int64_t *count_out, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
+/* The transpose of gpcc_compact_rows (the backward of t[keep]): src[t] (m, widths[t]) device, the rows of the kept set in order; dst[t]
+ * (n, widths[t]) device receives row i of src[t] at the position of the i-th set entry of keep (n bytes) and zero rows elsewhere.  The
+ * caller knows m = count(keep) from the forward: NO synchronisation.  Should keep count more than m entries, those beyond the m-th get
+ * zero rows and nothing outside src is read.  alloc is called once, only when m > 0, for 4 (n + 1) bytes of ranks, not needed once the
+ * kernels have run.  One scan (none when m = 0), one launch over all matrices.  nmats <= 32, 0 <= m <= n < 2^28, n widths[t] < 2^31.
+ * src, widths and dst are host arrays. */
+GPCC_API int gpcc_expand_rows(gpcc_ctx *ctx, const uint8_t *keep_dev, int64_t n, int64_t m, int nmats, const float *const *src, const int64_t *widths,
+                              float *const *dst, gsr_alloc_fn alloc, void *alloc_user, void *stream);
 
 /* ================= Photometric loss (training step, HAC/utils/loss_utils.py: ssim, l1_loss; train.py's loss) =================
  * img1, img2 (batch, channels, height, width) float32 device, contiguous.  SSIM of every plane with the reference's window: the outer
