@@ -1,6 +1,7 @@
 // noise.hip -- the adaptive-step quantisation noise of the HAC family's training branch (HAC-plus/gaussian_renderer/__init__.py:47-51,
 // 64-69, 91-99): x + U(-0.5, 0.5) * Q0 * (1 + tanh(adj)) on up to three row-aligned attributes (feat, scaling, offsets) in one launch.
 //   gsnn_noise_forward    y_j = x_j + u_j * Q_j, Q_j[r] = Q0_j * (1 + tanh(adj[r, col_j])), and the (n, nattr) table of the Q_j[r]
+//   gsnn_noise_forward_b / _backward_b   the same with the step rule's base as an argument: Q0 * (base + tanh(adj)), CAT-3DGS's 1.1
 //   gsnn_noise_backward   d_adj[r, j] = (sum_c g_j[r, c] u_j[r, c] + gQ[r, j]) * Q0_j * (1 - tanh^2); dx_j is g_j itself, nothing is copied
 // The contract is in include/gauspcc.h.  Per element, in float32 and in torch's expression order (no contraction): t = tanhf(adj),
 // Q = Q0 * (1 + t), y = x + u * Q.  The noise u is the caller's: which random numbers a seeded run consumes does not change.
@@ -37,6 +38,7 @@ struct Args {
     int64_t adj_stride;
     int nattr;
     uint32_t n;
+    float base;               // Q = Q0 * (base + tanh(adj)): 1 for the HAC family, 1.1 for CAT-3DGS
 };
 
 template <int V> struct Vec;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(TB) void k_noise_fwd(Args P, float *__restrict__ q_
     if (e >= (uint64_t)P.n * w) return;
     const uint32_t row = (uint32_t)e / w, col = (uint32_t)e - row * w;      // n w < 2^31 (checked by the host)
     float q = A.q0;
-    if (P.adj) q = A.q0 * (1.0f + tanhf(P.adj[(int64_t)row * P.adj_stride + A.col]));
+    if (P.adj) q = A.q0 * (P.base + tanhf(P.adj[(int64_t)row * P.adj_stride + A.col]));
     if (col == 0) q_out[(uint64_t)row * P.nattr + j] = q;
     if (A.vec == 4) noise_vec<4>(A, e, q);
     else if (A.vec == 2) noise_vec<2>(A, e, q);
@@ -100,7 +102,7 @@ bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) &
 
 // the checks the two entry points share; fills everything of P but the per-attribute pointers' roles
 int make_args(const char *who, int64_t n, int nattr, const float *const *a, const float *const *b, const int64_t *widths, const double *q0, const float *adj,
-              int64_t adj_stride, const int *adj_cols, Args &P)
+              int64_t adj_stride, const int *adj_cols, double base, Args &P)
 {
     if (n < 0 || nattr < 1 || nattr > MAX_ATTR) return fail(GPCC_ERR_ARG, "%s: n = %lld, %d attributes (1..%d)", who, (long long)n, nattr, MAX_ATTR);
     if (!a || !b || !widths || !q0) return fail(GPCC_ERR_ARG, "%s: null argument", who);
@@ -109,6 +111,7 @@ int make_args(const char *who, int64_t n, int nattr, const float *const *a, cons
     P.n = (uint32_t)n;
     P.adj = adj;
     P.adj_stride = adj_stride;
+    P.base = (float)base;
     for (int j = 0; j < nattr; ++j) {
         if (widths[j] < 1 || (n > 0 && widths[j] > (((int64_t)1 << 31) - 1) / n))
             return fail(GPCC_ERR_ARG, "%s: attribute %d of width %lld (>= 1, n width < 2^31)", who, j, (long long)widths[j]);
@@ -129,12 +132,12 @@ int make_args(const char *who, int64_t n, int nattr, const float *const *a, cons
 
 }  // namespace
 
-extern "C" int gsnn_noise_forward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const float *const *u, const int64_t *widths, const double *q0,
-                                  const float *adj, int64_t adj_stride, const int *adj_cols, float *const *y, float *q_out, void *stream)
+extern "C" int gsnn_noise_forward_b(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const float *const *u, const int64_t *widths, const double *q0,
+                                    const float *adj, int64_t adj_stride, const int *adj_cols, double base, float *const *y, float *q_out, void *stream)
 {
     if (!ctx) return fail(GPCC_ERR_ARG, "gsnn_noise_forward: null context");
     Args P;
-    GP_TRY(make_args("gsnn_noise_forward", n, nattr, x, u, widths, q0, adj, adj_stride, adj_cols, P));
+    GP_TRY(make_args("gsnn_noise_forward", n, nattr, x, u, widths, q0, adj, adj_stride, adj_cols, base, P));
     if (n == 0) return GPCC_OK;
     if (!y || !q_out) return fail(GPCC_ERR_ARG, "gsnn_noise_forward: null output");
     int64_t lanes = 0;
@@ -153,12 +156,19 @@ extern "C" int gsnn_noise_forward(gpcc_ctx *ctx, int64_t n, int nattr, const flo
     return GPCC_OK;
 }
 
-extern "C" int gsnn_noise_backward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths, const double *q0,
-                                   const float *adj, int64_t adj_stride, const int *adj_cols, const float *grad_q, float *d_adj, void *stream)
+extern "C" int gsnn_noise_forward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const float *const *u, const int64_t *widths, const double *q0,
+                                  const float *adj, int64_t adj_stride, const int *adj_cols, float *const *y, float *q_out, void *stream)
+{
+    return gsnn_noise_forward_b(ctx, n, nattr, x, u, widths, q0, adj, adj_stride, adj_cols, 1.0, y, q_out, stream);
+}
+
+// base shifts the step, not its slope: the gradient of adj is the same for every base
+extern "C" int gsnn_noise_backward_b(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths, const double *q0,
+                                     const float *adj, int64_t adj_stride, const int *adj_cols, double base, const float *grad_q, float *d_adj, void *stream)
 {
     if (!ctx) return fail(GPCC_ERR_ARG, "gsnn_noise_backward: null context");
     Args P;
-    GP_TRY(make_args("gsnn_noise_backward", n, nattr, g, u, widths, q0, adj, adj_stride, adj_cols, P));
+    GP_TRY(make_args("gsnn_noise_backward", n, nattr, g, u, widths, q0, adj, adj_stride, adj_cols, base, P));
     if (n == 0) return GPCC_OK;
     if (!adj || !d_adj) return fail(GPCC_ERR_ARG, "gsnn_noise_backward: null adj or output (a constant step has no gradient)");
     int lmax = 4;
@@ -170,4 +180,10 @@ extern "C" int gsnn_noise_backward(gpcc_ctx *ctx, int64_t n, int nattr, const fl
     k_noise_bwd<<<dim3((unsigned)cdiv(n * lmax, TB), (unsigned)nattr), TB, 0, (hipStream_t)stream>>>(P, grad_q, d_adj);
     LAUNCH_CHECK();
     return GPCC_OK;
+}
+
+extern "C" int gsnn_noise_backward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths, const double *q0,
+                                   const float *adj, int64_t adj_stride, const int *adj_cols, const float *grad_q, float *d_adj, void *stream)
+{
+    return gsnn_noise_backward_b(ctx, n, nattr, g, u, widths, q0, adj, adj_stride, adj_cols, 1.0, grad_q, d_adj, stream);
 }

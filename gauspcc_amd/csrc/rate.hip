@@ -63,31 +63,34 @@ struct Elem {
     bool x_in, q_in;
 };
 
-__device__ __forceinline__ Elem element(const Args &A, int64_t e, int64_t r)
+// CAT-3DGS's torch.clamp(Q, min=q_floor): passes where Q >= q_floor
+__device__ __forceinline__ bool floor_q(float &q, float q_floor)
+{
+    if (!(q_floor > 0.f)) return true;
+    const bool in = q >= q_floor;
+    q = q < q_floor ? q_floor : q;
+    return in;
+}
+
+// x against x_mean +- hw (hw = 15000 Q), and the half bin
+__device__ __forceinline__ Elem clamped(float x, float xm, float q, float hw, bool q_in)
 {
     Elem E;
-    float q, hw;
-    if (A.q.kind == HOST) {
-        q = A.q_host;
-        hw = A.hw_host;
-        E.q_in = true;
-    } else {
-        q = load(A.q, e, r);
-        E.q_in = true;
-        if (A.q_floor > 0.f) {            // torch.clamp(Q, min=q_floor): passes where Q >= q_floor
-            E.q_in = q >= A.q_floor;
-            q = q < A.q_floor ? A.q_floor : q;
-        }
-        hw = 15000.f * q;
-    }
-    const float xm = A.xm[0];
+    E.q_in = q_in;
     const float lo = xm - hw, hi = xm + hw;
-    const float x = A.x[e];
     E.x_in = x >= lo && x <= hi;
     E.xc = fminf(fmaxf(x, lo), hi);
     E.xc = x != x ? x : E.xc;             // torch.clamp keeps a NaN
     E.hq = 0.5f * q;
     return E;
+}
+
+__device__ __forceinline__ Elem element(const Args &A, int64_t e, int64_t r)
+{
+    if (A.q.kind == HOST) return clamped(A.x[e], A.xm[0], A.q_host, A.hw_host, true);
+    float q = load(A.q, e, r);
+    const bool q_in = floor_q(q, A.q_floor);
+    return clamped(A.x[e], A.xm[0], q, 15000.f * q, q_in);
 }
 
 // one component: its two CDF values, their erf arguments and the reciprocal scale
@@ -385,5 +388,259 @@ extern "C" int gsac_rate_backward(gpcc_ctx *ctx, int k, int64_t n, int64_t c, co
         k_rate_reduce<<<nones, TB, 0, st>>>(P, blocks);
         LAUNCH_CHECK();
     }
+    return GPCC_OK;
+}
+
+// ---- the channel-wise context chain of CAT-3DGS's training branch (CAT-3DGS/gaussian_renderer/__init__.py:92-123) ------------------------
+// Every stage of the chain -- the feat groups, scaling, offsets -- priced in one launch and differentiated in one: in training the "decoded"
+// channels a stage's MLP reads are the noisy feat itself, so once the MLPs have run the stages do not depend on one another.  Per element
+// the math is element() / component() above with k = 1 and a per-row Q: mean = ctx + dmean and scale = ctx + dscale are one rounded add
+// each, the offsets' bits are multiplied by the anchor's offset mask.  The contract is in include/gauspcc.h.
+namespace {
+
+constexpr int CR_STAGES = 8;
+constexpr int CR_CH = 64;
+constexpr int CR_COLS = CR_STAGES * CR_CH;            // the widest bits row
+constexpr int CR_WIDTH = 2 * CR_COLS + 64;            // the widest ctx row
+constexpr int CR_WORDS = (CR_WIDTH + 31) / 32;
+
+struct CStage {
+    const float *res;         // (m, 2 ch) or NULL
+    float *d_res;             // backward: (m, 2 ch) or NULL
+    int out0;                 // first column of bits
+    int attr, col, ch, mean_col, scale_col;
+};
+
+struct CArgs {
+    const float *ctx, *x[3], *q, *xm, *mask;
+    int64_t ctx_stride, m;
+    int width[3];             // F, 6, 3 K
+    int W, C, K, S;
+    float q_floor;
+    CStage st[CR_STAGES];
+};
+
+struct CGrads {
+    float *x[3], *ctx, *q, *mask;
+    uint32_t covered[CR_WORDS];   // the columns of ctx some stage reads
+};
+
+// what one element of bits reads
+struct CElem {
+    int s, a, j, ca;          // stage, attribute, column in the stage, column in the attribute
+    float mean, scale, mk;    // mk: the offsets mask (1 elsewhere)
+    bool masked;
+    Elem E;
+    Comp P;
+};
+
+__device__ __forceinline__ CElem chain_element(const CArgs &A, int64_t r, int c)
+{
+    CElem X;
+    X.s = 0;
+    for (int s = 1; s < A.S; ++s)
+        if (c >= A.st[s].out0 && c < A.st[s].out0 + A.st[s].ch) X.s = s;
+    const CStage &T = A.st[X.s];
+    X.a = T.attr;
+    X.j = c - T.out0;
+    X.ca = T.col + X.j;
+    const float *row = A.ctx + r * A.ctx_stride;
+    X.mean = row[T.mean_col + X.j];
+    X.scale = row[T.scale_col + X.j];
+    if (T.res) {
+        const float *d = T.res + r * (2 * T.ch);
+        X.mean = X.mean + d[X.j];
+        X.scale = X.scale + d[T.ch + X.j];
+    }
+    float q = A.q[r * 3 + X.a];
+    const bool q_in = floor_q(q, A.q_floor);
+    X.E = clamped(A.x[X.a][r * A.width[X.a] + X.ca], A.xm[X.a], q, 15000.f * q, q_in);
+    X.P = component(X.E.xc, X.E.hq, X.mean, X.scale);
+    X.masked = X.a == 2 && A.mask;
+    X.mk = X.masked ? A.mask[r * A.K + X.ca / 3] : 1.f;
+    return X;
+}
+
+__global__ __launch_bounds__(TB) void k_chain_fwd(CArgs A, float *__restrict__ bits)
+{
+    const int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (e >= A.m * A.C) return;
+    const int64_t r = e / A.C;
+    const CElem X = chain_element(A, r, (int)(e - r * A.C));
+    const float L = fabsf(X.P.u - X.P.l);
+    const float Lb = L < LOW ? LOW : L;
+    const float b = -log2f(Lb);
+    bits[e] = X.masked ? b * X.mk : b;
+}
+
+// a workgroup per `rows` rows (rows C <= max(TB, C) <= CR_COLS elements): per-element gradients are written as they are formed, the
+// per-row sums wait in LDS for their owner, which adds them with columns ascending
+__global__ __launch_bounds__(TB) void k_chain_bwd(CArgs A, const float *__restrict__ g, CGrads G, int rows_per_block)
+{
+    __shared__ float sq[CR_COLS], sm[CR_COLS];
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    const int rows = (int)min((int64_t)rows_per_block, A.m - r0);
+    const int span = rows * A.C;
+    const int t = threadIdx.x;
+    const int K3 = 3 * A.K;
+    for (int le = t; le < span; le += TB) {
+        const int rl = le / A.C, c = le - rl * A.C;
+        const int64_t r = r0 + rl, e = r * A.C + c;
+        const CElem X = chain_element(A, r, c);
+        const CStage &T = A.st[X.s];
+        const Comp &P = X.P;
+        const float diff = P.u - P.l;
+        const float L = fabsf(diff);
+        float go = g[e];
+        if (X.masked) {
+            const float Lb = L < LOW ? LOW : L;
+            sm[rl * K3 + X.ca] = go * -log2f(Lb);
+            go = go * X.mk;
+        }
+        const float gl = L >= LOW ? (-go) / (L * LN2) : 0.f;      // Low_bound passes iff L >= 1e-6
+        const float sg = (float)(diff > 0.f) - (float)(diff < 0.f);
+        const float a = gl * sg;
+        const float eu = expf(-(P.zu * P.zu)), el = expf(-(P.zl * P.zl));
+        const float ak = a * KPDF;
+        const float dvu = (ak * eu) * P.r, dvl = -((ak * el) * P.r);
+        const float gx = dvu + dvl;
+        const float gq = 0.5f * (dvu - dvl);
+        const float gmean = -(dvu + dvl);
+        const float dr = ak * (eu * P.du - el * P.dl);
+        const float gscale = X.scale >= SCALE_FLOOR ? -(dr * (P.r * P.r)) : 0.f;   // the gate tests the sum scale + dscale
+        sq[le] = X.E.q_in ? gq : 0.f;
+        if (G.x[X.a]) G.x[X.a][r * A.width[X.a] + X.ca] = X.E.x_in ? gx : 0.f;
+        if (G.ctx) {
+            float *row = G.ctx + r * A.W;
+            row[T.mean_col + X.j] = gmean;
+            row[T.scale_col + X.j] = gscale;
+        }
+        if (T.d_res) {
+            float *d = T.d_res + r * (2 * T.ch);
+            d[X.j] = gmean;
+            d[T.ch + X.j] = gscale;
+        }
+    }
+    __syncthreads();
+    if (G.q && t < rows * 3) {
+        const int rl = t / 3, a = t - rl * 3;
+        const int c0 = a == 0 ? 0 : a == 1 ? A.width[0] : A.width[0] + A.width[1];
+        const float *v = sq + rl * A.C + c0;
+        float s = 0.f;
+        for (int j = 0; j < A.width[a]; ++j) s += v[j];
+        G.q[(r0 + rl) * 3 + a] = s;
+    }
+    if (G.mask) {
+        for (int i = t; i < rows * A.K; i += TB) {
+            const float *v = sm + i * 3;      // (row, k): rows are K3 = 3 K apart
+            G.mask[r0 * A.K + i] = (v[0] + v[1]) + v[2];
+        }
+    }
+    if (G.ctx) {
+        for (int i = t; i < rows * A.W; i += TB) {
+            const int rl = i / A.W, c = i - rl * A.W;
+            if (!((G.covered[c >> 5] >> (c & 31)) & 1u)) G.ctx[(r0 + rl) * A.W + c] = 0.f;
+        }
+    }
+}
+
+int chain_args(const char *who, int64_t m, int feat_dim, int n_offsets, const float *ctxp, int64_t ctx_stride, int ctx_width, const float *feat,
+               const float *scaling, const float *offsets, const float *q, const float *x_mean, double q_floor, const float *mask,
+               const gsac_rate_stage *stages, int nstages, CArgs &A, uint32_t *covered)
+{
+    if (m < 0 || feat_dim < 1 || feat_dim > CR_COLS || n_offsets < 1 || 3 * n_offsets > CR_COLS)
+        return fail(GPCC_ERR_ARG, "%s: m = %lld, feat_dim %d, %d offsets", who, (long long)m, feat_dim, n_offsets);
+    if (!stages || nstages < 1 || nstages > CR_STAGES) return fail(GPCC_ERR_ARG, "%s: %d stages (1..%d)", who, nstages, CR_STAGES);
+    if (ctx_width < 1 || ctx_width > CR_WIDTH || ctx_stride < ctx_width)
+        return fail(GPCC_ERR_ARG, "%s: ctx of width %d (1..%d) with row stride %lld", who, ctx_width, CR_WIDTH, (long long)ctx_stride);
+    if (m > 0 && (!ctxp || !feat || !scaling || !offsets || !q || !x_mean)) return fail(GPCC_ERR_ARG, "%s: null argument", who);
+    memset(&A, 0, sizeof(A));
+    A.ctx = ctxp; A.ctx_stride = ctx_stride; A.W = ctx_width; A.m = m;
+    A.x[0] = feat; A.x[1] = scaling; A.x[2] = offsets;
+    A.width[0] = feat_dim; A.width[1] = 6; A.width[2] = 3 * n_offsets;
+    A.q = q; A.xm = x_mean; A.mask = mask;
+    A.K = n_offsets; A.S = nstages;
+    A.C = feat_dim + 6 + 3 * n_offsets;
+    A.q_floor = q_floor > 0.0 ? (float)q_floor : 0.f;
+    if (A.C > CR_COLS) return fail(GPCC_ERR_ARG, "%s: %d columns of bits (<= %d)", who, A.C, CR_COLS);
+    if (m > ((int64_t)1 << 38) / A.C) return fail(GPCC_ERR_ARG, "%s: m = %lld", who, (long long)m);
+    const int base[3] = {0, feat_dim, feat_dim + 6};
+    uint32_t out_seen[(CR_COLS + 31) / 32];
+    memset(out_seen, 0, sizeof(out_seen));
+    memset(covered, 0, CR_WORDS * sizeof(uint32_t));
+    int total = 0;
+    for (int s = 0; s < nstages; ++s) {
+        const gsac_rate_stage &T = stages[s];
+        if (T.attr < 0 || T.attr > 2 || T.ch < 1 || T.ch > CR_CH || T.col < 0 || T.col + T.ch > A.width[T.attr] || T.mean_col < 0 ||
+            T.mean_col + T.ch > ctx_width || T.scale_col < 0 || T.scale_col + T.ch > ctx_width)
+            return fail(GPCC_ERR_ARG, "%s: stage %d (attribute %d, columns %d + %d, mean_col %d, scale_col %d) outside its tensors", who, s, T.attr,
+                        T.col, T.ch, T.mean_col, T.scale_col);
+        CStage &D = A.st[s];
+        D.res = T.res; D.attr = T.attr; D.col = T.col; D.ch = T.ch; D.mean_col = T.mean_col; D.scale_col = T.scale_col;
+        D.out0 = base[T.attr] + T.col;
+        for (int j = 0; j < T.ch; ++j) {
+            const int o = D.out0 + j, cs[2] = {T.mean_col + j, T.scale_col + j};
+            if ((out_seen[o >> 5] >> (o & 31)) & 1u) return fail(GPCC_ERR_ARG, "%s: stage %d prices a column another stage prices", who, s);
+            out_seen[o >> 5] |= 1u << (o & 31);
+            for (int c : cs) {
+                if ((covered[c >> 5] >> (c & 31)) & 1u) return fail(GPCC_ERR_ARG, "%s: stage %d reads a ctx column twice read", who, s);
+                covered[c >> 5] |= 1u << (c & 31);
+            }
+        }
+        total += T.ch;
+    }
+    if (total != A.C) return fail(GPCC_ERR_ARG, "%s: the stages price %d of the %d columns", who, total, A.C);
+    return GPCC_OK;
+}
+
+}  // namespace
+
+extern "C" int gsac_chain_rate_forward(gpcc_ctx *ctx, int64_t m, int feat_dim, int n_offsets, const float *ctx_dev, int64_t ctx_stride, int ctx_width,
+                                       const float *feat, const float *scaling, const float *offsets, const float *q, const float *x_mean, double q_floor,
+                                       const float *mask, const gsac_rate_stage *stages, int nstages, float *bits, void *stream)
+{
+    if (!ctx) return fail(GPCC_ERR_ARG, "gsac_chain_rate_forward: null context");
+    CArgs A;
+    uint32_t covered[CR_WORDS];
+    GP_TRY(chain_args("gsac_chain_rate_forward", m, feat_dim, n_offsets, ctx_dev, ctx_stride, ctx_width, feat, scaling, offsets, q, x_mean, q_floor, mask,
+                      stages, nstages, A, covered));
+    if (m == 0) return GPCC_OK;
+    if (!bits) return fail(GPCC_ERR_ARG, "gsac_chain_rate_forward: null output");
+    const int64_t blocks = cdiv(m * A.C, TB);
+    if (blocks > INT32_MAX) return fail(GPCC_ERR_ARG, "gsac_chain_rate_forward: %lld rows", (long long)m);
+    HIP_TRY(hipSetDevice(ctx->device));
+    k_chain_fwd<<<(unsigned)blocks, TB, 0, (hipStream_t)stream>>>(A, bits);
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
+
+extern "C" int gsac_chain_rate_backward(gpcc_ctx *ctx, int64_t m, int feat_dim, int n_offsets, const float *ctx_dev, int64_t ctx_stride, int ctx_width,
+                                        const float *feat, const float *scaling, const float *offsets, const float *q, const float *x_mean, double q_floor,
+                                        const float *mask, const gsac_rate_stage *stages, int nstages, const float *grad_bits, float *d_feat,
+                                        float *d_scaling, float *d_offsets, float *d_ctx, float *const *d_res, float *d_q, float *d_mask, void *stream)
+{
+    if (!ctx) return fail(GPCC_ERR_ARG, "gsac_chain_rate_backward: null context");
+    CArgs A;
+    CGrads G;
+    memset(&G, 0, sizeof(G));
+    GP_TRY(chain_args("gsac_chain_rate_backward", m, feat_dim, n_offsets, ctx_dev, ctx_stride, ctx_width, feat, scaling, offsets, q, x_mean, q_floor, mask,
+                      stages, nstages, A, G.covered));
+    if (d_mask && !mask) return fail(GPCC_ERR_ARG, "gsac_chain_rate_backward: d_mask without a mask");
+    if (m == 0) return GPCC_OK;
+    if (!grad_bits) return fail(GPCC_ERR_ARG, "gsac_chain_rate_backward: null upstream gradient");
+    G.x[0] = d_feat; G.x[1] = d_scaling; G.x[2] = d_offsets;
+    G.ctx = d_ctx; G.q = d_q; G.mask = d_mask;
+    bool any = d_feat || d_scaling || d_offsets || d_ctx || d_q || d_mask;
+    for (int s = 0; s < nstages; ++s) {
+        A.st[s].d_res = d_res && A.st[s].res ? d_res[s] : nullptr;
+        any = any || A.st[s].d_res;
+    }
+    if (!any) return GPCC_OK;
+    const int rows_per_block = A.C >= TB ? 1 : TB / A.C;
+    const int64_t blocks = cdiv(m, (int64_t)rows_per_block);
+    if (blocks > INT32_MAX) return fail(GPCC_ERR_ARG, "gsac_chain_rate_backward: %lld rows", (long long)m);
+    HIP_TRY(hipSetDevice(ctx->device));
+    k_chain_bwd<<<(unsigned)blocks, TB, 0, (hipStream_t)stream>>>(A, grad_bits, G, rows_per_block);
+    LAUNCH_CHECK();
     return GPCC_OK;
 }

@@ -163,6 +163,134 @@ def rate(x, means, scales, probs=None, Q=1, x_mean=None, q_floor=None, return_lk
     return _forward(plan, x.detach().reshape(n, c).contiguous(), xm)
 
 
+ATTRS = ("feat", "scaling", "offsets")
+CHAIN_MAX_STAGES, CHAIN_MAX_CH, CHAIN_MAX_COLS = 8, 64, 512
+
+
+class _ChainPlan:
+    """What one chain_rate call reads: the shapes, the stage records and how the gradients go back."""
+    def __init__(self, m, F, K, W, stages, has_res, q_floor, offsets_shape, mask_shape):
+        self.m, self.F, self.K, self.W, self.stages, self.has_res = m, F, K, W, stages, has_res
+        self.q_floor, self.offsets_shape, self.mask_shape = float(q_floor or 0.0), offsets_shape, mask_shape
+
+    def args(self, ctx, feat, scaling, offsets, Q, xm, mask, res):
+        recs = (_lib.RateStage * len(self.stages))()
+        for rec, st, r in zip(recs, self.stages, res):
+            rec.attr, rec.col, rec.ch, rec.mean_col, rec.scale_col, rec.res = *st, ptr(r)
+        return (self.m, self.F, self.K, ctx.data_ptr(), ctx.stride(0), self.W, feat.data_ptr(), scaling.data_ptr(), offsets.data_ptr(), Q.data_ptr(),
+                xm.data_ptr(), self.q_floor, ptr(mask), recs, len(self.stages))
+
+
+def _rows_in_place(t):
+    """a 2-D tensor as the kernels read it in place: unit column stride, rows that do not overlap"""
+    return t if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+class _ChainRate(torch.autograd.Function):
+    """gsac_chain_rate_forward / gsac_chain_rate_backward.  Inputs after the plan: ctx, feat, scaling, offsets, Q, x_means, mask, residuals."""
+
+    @staticmethod
+    def forward(fctx, plan, ctx, feat, scaling, offsets, Q, xm, mask, *res):
+        m, dev = plan.m, feat.device
+        ins = [_rows_in_place(ctx.detach()), feat.detach().contiguous(), scaling.detach().contiguous(), offsets.detach().reshape(m, 3 * plan.K).contiguous(),
+               Q.detach().contiguous(), xm, None if mask is None else mask.detach().reshape(m, plan.K).contiguous()]
+        rs = [None if r is None else r.detach().contiguous() for r in res]
+        bits = torch.empty(m, plan.F + 6 + 3 * plan.K, dtype=torch.float32, device=dev)
+        if m:
+            _lib.check(_lib.lib().gsac_chain_rate_forward(runtime.context(dev), *plan.args(*ins, rs), bits.data_ptr(), runtime.stream_ptr(dev)))
+        fctx.plan, fctx.ins, fctx.rs = plan, ins, rs
+        return bits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad):
+        plan, ins, rs = fctx.plan, fctx.ins, fctx.rs
+        m, F, K, dev = plan.m, plan.F, plan.K, ins[1].device
+        need = fctx.needs_input_grad
+        new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None   # noqa: E731
+        d_ctx, d_feat, d_scaling, d_offsets = new(need[1], m, plan.W), new(need[2], m, F), new(need[3], m, 6), new(need[4], m, 3 * K)
+        d_q, d_mask = new(need[5], m, 3), new(need[7] and ins[6] is not None, m, K)
+        d_res = [new(need[8 + i] and r is not None, m, 2 * st[2]) for i, (r, st) in enumerate(zip(rs, plan.stages))]
+        outs = [d_feat, d_scaling, d_offsets, d_ctx, d_q, d_mask]
+        if m and (any(o is not None for o in outs) or any(d is not None for d in d_res)):
+            g = grad.detach().contiguous()
+            _lib.check(_lib.lib().gsac_chain_rate_backward(runtime.context(dev), *plan.args(*ins, rs), g.data_ptr(), ptr(d_feat), ptr(d_scaling), ptr(d_offsets),
+                                                           ptr(d_ctx), ptrs(d_res), ptr(d_q), ptr(d_mask), runtime.stream_ptr(dev)))
+        return (None, d_ctx, d_feat, d_scaling, None if d_offsets is None else d_offsets.view(plan.offsets_shape), d_q, None,
+                None if d_mask is None else d_mask.view(plan.mask_shape), *d_res)
+
+
+def chain_rate(ctx, feat, scaling, offsets, Q, x_means, stages, residuals, offset_mask=None, q_floor=1e-9):
+    """The bits of CAT-3DGS's channel-wise context chain in training, every stage in one launch (gsac_chain_rate_forward) and one in the
+    backward: bits (m, F + 6 + 3 K), columns [feat | scaling | offsets].  ctx (m, W) is the context model's output, read in place (a row
+    stride is fine); feat (m, F), scaling (m, 6), offsets (m, K, 3) or (m, 3 K) the noisy attributes; Q (m, 3) their per-row steps
+    (quant_noise's); x_means three one-value device tensors or one of three values, the clamp centres; stages the records of
+    cat_codec.stage_table (attr, out_col, ch, mean_col, scale_col are read: that table is the one statement of the row layout); residuals one
+    entry per stage, the stage MLP's output (m, 2 ch) = [dmean | dscale] or None; offset_mask (m, K) or (m, K, 1) multiplies the offsets'
+    bits.  Per element the value is Entropy_gaussian(q_floor)'s on mean = ctx + dmean, scale = ctx + dscale.  Differentiable in ctx (the
+    three adjustment columns get 0: their gradient arrives through quant_noise), the attributes, Q, the residuals and the mask; bitwise
+    reproducible.  Float32 CUDA tensors only."""
+    who = "chain_rate"
+    named = [("ctx", ctx), ("feat", feat), ("scaling", scaling), ("offsets", offsets), ("Q", Q)]
+    for name, t in named + ([("offset_mask", offset_mask)] if offset_mask is not None else []):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        _check_tensor(t, name, who)
+        if t.device != feat.device:
+            raise ValueError(f"{who}: {name} on {t.device}, feat on {feat.device}")
+    if feat.dim() != 2 or ctx.dim() != 2 or offsets.dim() not in (2, 3):
+        raise ValueError(f"{who}: ctx and feat must be 2-D and offsets (m, K, 3) or (m, 3 K), got {tuple(ctx.shape)}, {tuple(feat.shape)}, {tuple(offsets.shape)}")
+    m, F = feat.shape
+    K3 = offsets.shape[1] * (offsets.shape[2] if offsets.dim() == 3 else 1)
+    if K3 % 3 or K3 < 3 or (offsets.dim() == 3 and offsets.shape[2] != 3):
+        raise ValueError(f"{who}: offsets of shape {tuple(offsets.shape)} is not (m, K, 3) or (m, 3 K)")
+    K, W = K3 // 3, ctx.shape[1]
+    if F < 1 or F + 6 + K3 > CHAIN_MAX_COLS:
+        raise ValueError(f"{who}: {F} + 6 + {K3} columns of bits (<= {CHAIN_MAX_COLS})")
+    for name, t, shape in (("ctx", ctx, (m, W)), ("scaling", scaling, (m, 6)), ("Q", Q, (m, 3)), ("offsets", offsets, None)):
+        if t.shape[0] != m or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{who}: {name} of shape {tuple(t.shape)}, expected {shape or (m, K, 3)} (feat is {tuple(feat.shape)})")
+    if offset_mask is not None and tuple(offset_mask.shape) not in ((m, K), (m, K, 1)):
+        raise ValueError(f"{who}: offset_mask of shape {tuple(offset_mask.shape)}, expected ({m}, {K}) or ({m}, {K}, 1)")
+    if isinstance(x_means, torch.Tensor):
+        xs = [x_means.reshape(-1)] if x_means.numel() == 3 else None
+    else:
+        xs = [x.reshape(1) for x in x_means] if len(x_means) == 3 and all(isinstance(x, torch.Tensor) and x.numel() == 1 for x in x_means) else None
+    if xs is None:
+        raise ValueError(f"{who}: x_means must be three one-value tensors or one tensor of three values")
+    for x in xs:
+        if not x.is_cuda:
+            raise RuntimeError(f"{who}: x_means must be CUDA tensors (got {x.device}); gauspcc_amd has no CPU path")
+    xm = torch.cat([x.detach().to(device=feat.device, dtype=torch.float32) for x in xs]).contiguous()
+    stages, residuals = list(stages), list(residuals)
+    if not 1 <= len(stages) <= CHAIN_MAX_STAGES or len(residuals) != len(stages):
+        raise ValueError(f"{who}: {len(stages)} stages (1..{CHAIN_MAX_STAGES}) with {len(residuals)} residuals")
+    widths = {"feat": F, "scaling": 6, "offsets": K3}
+    recs, seen, read = [], set(), set()
+    for i, (st, r) in enumerate(zip(stages, residuals)):
+        if st["attr"] not in widths:
+            raise ValueError(f"{who}: stage {i} of attribute {st['attr']!r}")
+        a, col, ch, mc, sc = ATTRS.index(st["attr"]), int(st["out_col"]), int(st["ch"]), int(st["mean_col"]), int(st["scale_col"])
+        if not 1 <= ch <= CHAIN_MAX_CH or col < 0 or col + ch > widths[st["attr"]] or min(mc, sc) < 0 or max(mc, sc) + ch > W:
+            raise ValueError(f"{who}: stage {i} ({st['attr']} columns {col}..{col + ch}, mean_col {mc}, scale_col {sc}) outside its tensors (ch <= {CHAIN_MAX_CH}, ctx width {W})")
+        cols, reads = {(a, col + j) for j in range(ch)}, {mc + j for j in range(ch)} | {sc + j for j in range(ch)}
+        if cols & seen or reads & read or len(reads) != 2 * ch:
+            raise ValueError(f"{who}: stage {i} overlaps another stage")
+        seen |= cols
+        read |= reads
+        if r is not None:
+            if not isinstance(r, torch.Tensor):
+                raise TypeError(f"{who}: residuals[{i}] must be a torch.Tensor or None")
+            _check_tensor(r, f"residuals[{i}]", who)
+            if tuple(r.shape) != (m, 2 * ch) or r.device != feat.device:
+                raise ValueError(f"{who}: residuals[{i}] of shape {tuple(r.shape)} on {r.device}, expected ({m}, {2 * ch}) on {feat.device}")
+        recs.append((a, col, ch, mc, sc))
+    if len(seen) != F + 6 + K3:
+        raise ValueError(f"{who}: the stages price {len(seen)} of the {F + 6 + K3} columns")
+    plan = _ChainPlan(m, F, K, W, recs, [r is not None for r in residuals], q_floor, offsets.shape, None if offset_mask is None else offset_mask.shape)
+    return _ChainRate.apply(plan, ctx, feat, scaling, offsets, Q, xm, offset_mask, *residuals)
+
+
 class Low_bound(torch.autograd.Function):
     """max(x, 1e-6), the gradient passed iff x >= 1e-6 (the reference's extra pass-through where g < 0 multiplies a gradient that is
     already zero there, so it changes nothing); no host copy."""

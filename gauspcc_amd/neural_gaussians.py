@@ -11,7 +11,8 @@ test (:188-205) where HAC multiplies them into the opacity before it (:136-137) 
 `is_training=True` serves HAC's training branch (:47-98 and the 11-tuple of :170): the gathers, the quantisation noise, the
 context model's rate terms on the 5 % chosen anchors (the model's own torch modules: they train too) and then the differentiable core
 neural_gaussians_train (gsnn_forward_train / gsnn_backward), which HAC++, TC-GS and CAT-3DGS callers can use after their own rate code.
-HAC++'s training branch is gauspcc_amd.hac_plus_renderer, built on that core and on quant_noise below (gsnn_noise_forward / _backward).
+HAC++'s training branch is gauspcc_amd.hac_plus_renderer, CAT-3DGS's renderer gauspcc_amd.cat_renderer, both built on that core, on quant_noise
+below (gsnn_noise_forward_b / _backward_b) and, for inference, on _generate_tail.
 The model `pc` is used through the attributes the reference uses.  When `pc.decoded_version` is false the attributes are first quantised
 with the context model's step sizes exactly as the reference does (:103-114); everything after that -- view vectors,
 feature bank, the three MLPs, masking, assembly -- is ONE call into libgauspcc (gsnn_generate: two kernels and a scan
@@ -108,6 +109,15 @@ def _generate_inference(viewpoint_camera, pc, visible_mask):
             n = rows.numel()
     if n == 0:                      # no visible anchor: the reference's tensor program runs on empty tensors (:33-38, 115-167); no device buffer to hand over
         return (*_no_gaussians(dev), time_sub)
+    return (*_generate_tail(viewpoint_camera, pc, n, rows, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks), time_sub)
+
+
+@torch.no_grad()
+def _generate_tail(viewpoint_camera, pc, n, rows, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks):
+    """gsnn_generate on n > 0 anchors -- the rows `rows` (int32 index list) of the tensors, or all of them (rows None) -- to (xyz, color,
+    opacity, scaling, rot).  The end of every inference path: HAC's and HAC++'s above, CAT-3DGS's in gauspcc_amd.cat_renderer."""
+    dev = anchor.device
+    K, F = pc.n_offsets, pc.feat_dim
     tensors = _linears(pc)
     anchor, feat, grid_offsets, grid_scaling = _f32(anchor), _f32(feat), _f32(grid_offsets), _f32(grid_scaling)
     mask = _f32(binary_grid_masks).view(-1, K)
@@ -119,7 +129,7 @@ def _generate_inference(viewpoint_camera, pc, visible_mask):
                                         grid_offsets.data_ptr(), grid_scaling.data_ptr(), mask.data_ptr(), cam.data_ptr(), ptrs(tensors, 16), xyz.data_ptr(), color.data_ptr(),
                                         opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), C.byref(m), runtime.stream_ptr(dev)))
     m = m.value
-    return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m], time_sub
+    return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m]
 
 
 # ---- training path ----------------------------------------------------------------------------------------------------------------------
@@ -223,7 +233,7 @@ class _QuantNoise(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, adj, *xs):
-        us, q0s, cols = cfg
+        us, q0s, cols, base = cfg
         n, widths, c_w, c_q, c_cols = _noise_args(xs, us, q0s, adj, cols)
         dev, T = xs[0].device, len(xs)
         xc = [x.detach().contiguous() for x in xs]
@@ -232,15 +242,15 @@ class _QuantNoise(torch.autograd.Function):
         q = torch.empty(n, T, device=dev)
         a = None if adj is None else _adj_view(adj.detach())
         if n:
-            _lib.check(_lib.lib().gsnn_noise_forward(runtime.context(dev), n, T, ptrs(xc), ptrs(uc), c_w, c_q, ptr(a), a.stride(0) if a is not None else 0, c_cols,
-                                                     ptrs(ys), q.data_ptr(), runtime.stream_ptr(dev)))
-        ctx.cfg = (n, T, c_w, c_q, c_cols, uc, a)
+            _lib.check(_lib.lib().gsnn_noise_forward_b(runtime.context(dev), n, T, ptrs(xc), ptrs(uc), c_w, c_q, ptr(a), a.stride(0) if a is not None else 0, c_cols,
+                                                       base, ptrs(ys), q.data_ptr(), runtime.stream_ptr(dev)))
+        ctx.cfg = (n, T, c_w, c_q, c_cols, uc, a, base)
         return (*ys, q)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        n, T, c_w, c_q, c_cols, uc, a = ctx.cfg
+        n, T, c_w, c_q, c_cols, uc, a, base = ctx.cfg
         gs, gq = grads[:T], grads[T]
         d_adj = None
         if a is not None and ctx.needs_input_grad[1]:
@@ -249,8 +259,8 @@ class _QuantNoise(torch.autograd.Function):
             d = torch.empty(n, T, device=dev)
             gqc = None if gq is None else gq.detach().contiguous()
             if n:
-                _lib.check(_lib.lib().gsnn_noise_backward(runtime.context(dev), n, T, ptrs(gc), ptrs(uc), c_w, c_q, a.data_ptr(), a.stride(0), c_cols, ptr(gqc),
-                                                          d.data_ptr(), runtime.stream_ptr(dev)))
+                _lib.check(_lib.lib().gsnn_noise_backward_b(runtime.context(dev), n, T, ptrs(gc), ptrs(uc), c_w, c_q, a.data_ptr(), a.stride(0), c_cols, base,
+                                                            ptr(gqc), d.data_ptr(), runtime.stream_ptr(dev)))
             cols = list(c_cols)
             if a.shape[1] == T and cols == list(range(T)):
                 d_adj = d
@@ -260,14 +270,16 @@ class _QuantNoise(torch.autograd.Function):
         return (None, d_adj, *gs)       # dx_j is the incoming gradient itself
 
 
-def quant_noise(xs, us, q0s, adj=None, cols=None):
-    """The adaptive-step quantisation noise on up to three row-aligned attributes in one launch (gsnn_noise_forward):
-    y_j = xs[j] + us[j] * Q_j with Q_j[r] = q0s[j] * (1 + tanh(adj[r, cols[j]])), or the constant q0s[j] without adj.  us are the caller's
+def quant_noise(xs, us, q0s, adj=None, cols=None, base=1.0):
+    """The adaptive-step quantisation noise on up to three row-aligned attributes in one launch (gsnn_noise_forward_b):
+    y_j = xs[j] + us[j] * Q_j with Q_j[r] = q0s[j] * (base + tanh(adj[r, cols[j]])), or the constant q0s[j] without adj.  base is 1 for the
+    HAC family and 1.1 for CAT-3DGS; CAT-3DGS's constant regime, x + (u * Q0) * 1.1, is this without adj and with q0s[j] = Q0 * 1.1 formed in
+    double: one rounding where the reference's expression has two, a difference below an ulp of the noise term.  us are the caller's
     U(-0.5, 0.5) draws, shaped as xs.  adj is read in place: a column slice of mlp_grid's output costs no copy (cols default to 0, 1, ...).
     Returns (y_0, ..., Q) with Q (n, len(xs)) the per-row steps, which the rate modules take as (n, 1) operands.  Differentiable in xs (the
     gradient is the incoming tensor itself) and adj (gsnn_noise_backward, bitwise reproducible).  Float32 CUDA tensors only."""
     _noise_args(xs, us, q0s, adj, cols)
-    return _QuantNoise.apply((list(us), list(q0s), cols), adj, *xs)
+    return _QuantNoise.apply((list(us), list(q0s), cols, float(base)), adj, *xs)
 
 
 def _generate_training(viewpoint_camera, pc, visible_mask, step):

@@ -494,6 +494,15 @@ class SyntheticGaussianModelCAT(SyntheticGaussianModel):
         with torch.no_grad():
             return (torch.sum(self.get_mask(weighted_mask), dim=1)[:, 0]) > 0
 
+    # accessors as in the reference (:344-359, 370-375): what gaussian_renderer reads
+    get_chcm_mlp_list = property(lambda self: self.mlp_chcm_list)
+    get_chcm_mlp_scaling = property(lambda self: self.mlp_chcm_scaling if self.chcm_for_scaling else None)
+    get_chcm_mlp_offsets = property(lambda self: self.mlp_chcm_offsets if self.chcm_for_offsets else None)
+
+    def update_anchor_bound(self):
+        self.x_bound_min = self._anchor.min(dim=0, keepdim=True)[0].detach()
+        self.x_bound_max = self._anchor.max(dim=0, keepdim=True)[0].detach()
+
     def get_mlp_size(self, digit=32):
         grid = self.feature_net.attribute_net.grid
         mods = [self.mlp_opacity, self.mlp_cov, self.mlp_color, grid.arm, grid.arm2, grid.arm3, self.mlp_chcm_list]

@@ -530,6 +530,15 @@ GPCC_API int gsnn_noise_forward(gpcc_ctx *ctx, int64_t n, int nattr, const float
 GPCC_API int gsnn_noise_backward(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths,
                                  const double *q0, const float *adj, int64_t adj_stride, const int *adj_cols, const float *grad_q, float *d_adj,
                                  void *stream);
+/* The same with the step rule's base as an argument (host, rounded to float32): Q_j[r] = q0_j * (base + tanhf(adj[r, j])).  CAT-3DGS's rule
+ * is base = 1.1 (CAT-3DGS/gaussian_renderer/__init__.py:65-67); the two calls above are these with base = 1 and give the same bits.  The base
+ * shifts the step and leaves its slope alone: d_adj does not depend on it. */
+GPCC_API int gsnn_noise_forward_b(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const float *const *u, const int64_t *widths,
+                                  const double *q0, const float *adj, int64_t adj_stride, const int *adj_cols, double base, float *const *y, float *q_out,
+                                  void *stream);
+GPCC_API int gsnn_noise_backward_b(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths,
+                                   const double *q0, const float *adj, int64_t adj_stride, const int *adj_cols, double base, const float *grad_q,
+                                   float *d_adj, void *stream);
 
 /* ================= Gaussian splat rasteriser, forward (a20) =================
  * diff_gaussian_rasterization (Scaffold-GS fork; zip missing from the reference tree).  Mirrors the C++ API the
@@ -754,6 +763,38 @@ GPCC_API int gsac_rate_backward(gpcc_ctx *ctx, int k, int64_t n, int64_t c, cons
                                 const float *const *scale, const float *const *prob, const int *kinds, const float *q, int q_kind, double q_host,
                                 double q_floor, int return_lkl, const float *grad_out, float *grad_x, float *const *grad_mean,
                                 float *const *grad_scale, float *const *grad_prob, float *grad_q, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+
+/* The rate term of CAT-3DGS's channel-wise context chain in training (CAT-3DGS/gaussian_renderer/__init__.py:92-123): the feat groups, then
+ * scaling, then offsets, each stage under mean = ctx + dmean, scale = ctx + dscale with (dmean | dscale) the stage MLP's output.  In training
+ * the channels an MLP reads are the noisy feat itself, so with the MLPs' outputs in hand every stage is priced in ONE launch and
+ * differentiated in one.  One record per stage (at most 8; together they price every column of the three attributes exactly once and no ctx
+ * column is read by two of them): */
+typedef struct {
+    int32_t attr;                  /* 0 feat, 1 scaling, 2 offsets */
+    int32_t col;                   /* the stage prices the attribute's columns [col, col + ch) */
+    int32_t ch;                    /* 1..64 */
+    int32_t mean_col, scale_col;   /* first columns of the stage's base mean / scale in a row of ctx (CAT-3DGS: scales come first) */
+    const float *res;              /* device (m, 2 ch) contiguous, the stage MLP's output read in place: dmean = res[:, :ch], dscale = res[:, ch:]; NULL: none */
+} gsac_rate_stage;
+/* All tensors float32 device: ctx (m, ctx_width) with ctx_stride floats between rows, read in place; feat (m, F), scaling (m, 6),
+ * offsets (m, 3 K) contiguous; q (m, 3) the per-row steps of the three attributes (gsnn_noise_forward's q_out); x_mean[3] the three clamp
+ * centres, read on the device; mask (m, K) the offsets mask or NULL.  Per element of stage s, in float32 without contraction:
+ *   mean = ctx[r, mean_col + j] + res[r, j], scale = ctx[r, scale_col + j] + res[r, ch + j] (one rounded add each; the operand itself
+ *   without res); then gsac_rate_forward's element with k = 1, Q = q[r, attr], x_mean[attr] and q_floor; offsets bits are multiplied by
+ *   mask[r, c / 3].  bits (m, F + 6 + 3 K), columns [feat | scaling | offsets].
+ * gsac_chain_rate_backward takes grad_bits (m, F + 6 + 3 K) and writes any of (NULL = not wanted): d_feat, d_scaling, d_offsets (shaped as the
+ * inputs); d_ctx (m, ctx_width) contiguous, EVERY column written -- a stage's mean and scale columns its gradients, columns no stage reads
+ * (the three step adjustments) 0; d_res[s] (m, 2 ch) the same values as the stage's d_ctx columns (d_res or an entry NULL: not wanted);
+ * d_q (m, 3); d_mask (m, K) = sum over the three columns of grad_bits * the unmasked bits.  Gates are gsac_rate_backward's, the scale gate on
+ * the sum scale + dscale >= 1e-9.  d_q and d_mask are added by one owner with columns ascending, no atomics: bitwise reproducible.
+ * F + 6 + 3 K <= 512, ctx_width <= 1088.  m = 0 launches nothing.  stages, d_res are host arrays.  Enqueued on `stream`, no synchronisation. */
+GPCC_API int gsac_chain_rate_forward(gpcc_ctx *ctx, int64_t m, int feat_dim, int n_offsets, const float *ctx_dev, int64_t ctx_stride, int ctx_width,
+                                     const float *feat, const float *scaling, const float *offsets, const float *q, const float *x_mean, double q_floor,
+                                     const float *mask, const gsac_rate_stage *stages, int nstages, float *bits, void *stream);
+GPCC_API int gsac_chain_rate_backward(gpcc_ctx *ctx, int64_t m, int feat_dim, int n_offsets, const float *ctx_dev, int64_t ctx_stride, int ctx_width,
+                                      const float *feat, const float *scaling, const float *offsets, const float *q, const float *x_mean, double q_floor,
+                                      const float *mask, const gsac_rate_stage *stages, int nstages, const float *grad_bits, float *d_feat,
+                                      float *d_scaling, float *d_offsets, float *d_ctx, float *const *d_res, float *d_q, float *d_mask, void *stream);
 
 /* ================= Tri-plane context sampler (TC-GS/utils/triplane.py: sample_from_planes :87-164, Triplane.sample :226-238) =================
  * planes (3, C, H, W), max_coords, min_coords (3), all float32 device; radii and box_warp = 1 as Triplane passes them (radii = 0.5 *
