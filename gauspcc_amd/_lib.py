@@ -62,13 +62,13 @@ EXPORTS = [
     "gpcc_model_create", "gpcc_model_destroy", "gpcc_encode", "gpcc_decode", "gpcc_decode_to", "gpcc_encode_batch", "gpcc_decode_batch", "gpcc_sort_zyx",
     "gpcc_build_octree", "gpcc_conv3d", "gpcc_head_cdf", "gpcc_rc_encode", "gpcc_rc_decode", "gpcc_memcpy_d2d",
     "gpcc_profile_enable", "gpcc_profile_get", "gpcc_profile_stages", "gpcc_debug_trace_enable", "gpcc_debug_trace_get", "gpcc_debug_capture", "gpcc_debug_capture_get", "gpcc_debug_exclusive_scan", "gpcc_debug_launches", "gpcc_device_error_check",
-    "gsac_calculate_cdf", "gsac_encode", "gsac_decode", "gsac_encode_u16", "gsac_decode_u16", "gsac_encode_const", "gsac_decode_const", "gsac_host_encode_u16", "gsac_host_decode_u16", "gsac_host_encode_f32", "gsac_host_decode_f32", "gpcc_write_files", "gpcc_read_files", "gsac_encode_gaussian", "gsac_decode_gaussian", "gsac_encode_gaussian_mixed", "gsac_decode_gaussian_mixed", "gsac_calculate_cdf_mixed", "gsac_encode_gaussian_slices", "gsac_decode_gaussian_slices", "gsac_encode_gaussian_mixed_slices", "gsac_decode_gaussian_mixed_slices", "gshac_mlp2", "gshac_mlp2_act", "gsge_forward", "gsge_forward_train", "gsge_backward", "gsr_visible_filter", "gsr_forward", "gsr_forward_train", "gsr_backward", "gsnn_generate", "gsnn_forward_train", "gsnn_backward", "gsnn_noise_forward", "gsnn_noise_backward", "gsnn_noise_forward_b", "gsnn_noise_backward_b",
+    "gsac_calculate_cdf", "gsac_encode", "gsac_decode", "gsac_encode_u16", "gsac_decode_u16", "gsac_encode_const", "gsac_decode_const", "gsac_host_encode_u16", "gsac_host_decode_u16", "gsac_host_encode_f32", "gsac_host_decode_f32", "gpcc_write_files", "gpcc_read_files", "gsac_encode_gaussian", "gsac_decode_gaussian", "gsac_encode_gaussian_mixed", "gsac_decode_gaussian_mixed", "gsac_calculate_cdf_mixed", "gsac_encode_gaussian_slices", "gsac_decode_gaussian_slices", "gsac_encode_gaussian_mixed_slices", "gsac_decode_gaussian_mixed_slices", "gshac_mlp2", "gshac_mlp2_act", "gsge_forward", "gsge_forward_train", "gsge_backward", "gsr_visible_filter", "gsr_forward", "gsr_forward_train", "gsr_backward", "gsnn_generate", "gsnn_forward_train", "gsnn_backward", "gsnn_noise_forward", "gsnn_noise_backward", "gsnn_noise_forward_b", "gsnn_noise_backward_b", "gsnn_quantise", "gsnn_mean",
     "gpcc_train_frame", "gpcc_train_frame_nodes", "gpcc_train_weights", "gpcc_train_conv", "gpcc_train_wgrad",
     "gpcc_knn", "gpcc_scatter_max", "gpcc_grow_voxels",
     "gpcc_densify_stats", "gpcc_densify_front", "gpcc_densify_finish", "gpcc_compact_rows", "gpcc_expand_rows",
     "gsr_ssim_forward", "gsr_ssim_backward",
     "gsac_rate_forward", "gsac_rate_backward", "gsac_chain_rate_forward", "gsac_chain_rate_backward",
-    "gsge_plane_forward", "gsge_plane_backward",
+    "gsge_plane_forward", "gsge_plane_backward", "gsge_plane_rows_forward", "gsge_plane_rows_backward",
     "gsge_msplane_forward", "gsge_msplane_backward",
     "gshac_mlp2_backward", "gshac_mlp2_slab_rows",
     "gsac_arm_encode", "gsac_arm_decode", "gsac_arm_cdf_rows",
@@ -187,6 +187,8 @@ def lib():
     L.gsnn_noise_backward.argtypes = [vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), dp, vp, i64, C.POINTER(i32), vp, vp, vp]
     L.gsnn_noise_forward_b.argtypes = [vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), dp, vp, i64, C.POINTER(i32), C.c_double, C.POINTER(vp), vp, vp]
     L.gsnn_noise_backward_b.argtypes = [vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), dp, vp, i64, C.POINTER(i32), C.c_double, vp, vp, vp]
+    L.gsnn_quantise.argtypes = [vp, i64, i32, C.POINTER(vp), C.POINTER(i64), dp, vp, i64, C.POINTER(i32), C.c_double, vp, i32, C.POINTER(vp), vp, vp]
+    L.gsnn_mean.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64), vp, vp, vp]
     L.gsr_ssim_forward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, fp, i32, vp, vp, vp, C.c_double, vp, i32, GSR_ALLOC, vp, vp]
     L.gsr_ssim_backward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, fp, i32, vp, i32, vp, f32, vp, f32, vp, vp, vp]
     pp, ip, f64 = C.POINTER(vp), C.POINTER(i32), C.c_double
@@ -197,6 +199,8 @@ def lib():
     L.gsac_chain_rate_backward.argtypes = chain + [vp, vp, vp, vp, vp, pp, vp, vp, vp]
     L.gsge_plane_forward.argtypes = [vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, GSR_ALLOC, vp, vp]
     L.gsge_plane_backward.argtypes = [vp, vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, vp, GSR_ALLOC, vp, vp]
+    L.gsge_plane_rows_forward.argtypes = [vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, vp, i32, vp, GSR_ALLOC, vp, vp]
+    L.gsge_plane_rows_backward.argtypes = [vp, vp, vp, vp, vp, vp, f64, i64, i32, i32, i32, i32, i32, i32, vp, vp, GSR_ALLOC, vp, vp]
     L.gsge_msplane_forward.argtypes = [vp, vp, i64, i32, pp, i32, ip, ip, i32, i32, i32, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, vp]
     L.gsge_msplane_backward.argtypes = [vp, vp, vp, i64, i32, pp, i32, ip, ip, i32, i32, i32, vp, vp, vp, vp, vp, pp, vp, GSR_ALLOC, vp, vp]
     L.gshac_mlp2_backward.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, vp]

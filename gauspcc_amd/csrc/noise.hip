@@ -3,6 +3,8 @@
 //   gsnn_noise_forward    y_j = x_j + u_j * Q_j, Q_j[r] = Q0_j * (1 + tanh(adj[r, col_j])), and the (n, nattr) table of the Q_j[r]
 //   gsnn_noise_forward_b / _backward_b   the same with the step rule's base as an argument: Q0 * (base + tanh(adj)), CAT-3DGS's 1.1
 //   gsnn_noise_backward   d_adj[r, j] = (sum_c g_j[r, c] u_j[r, c] + gQ[r, j]) * Q0_j * (1 - tanh^2); dx_j is g_j itself, nothing is copied
+//   gsnn_quantise        the evaluation side, STE_multistep on the same attributes in one launch: y_j = rint(clamp(x_j, m_j -+ 15000 Q_j) / Q_j) Q_j with
+//                        the means m_j device scalars; gsnn_mean forms them (x_j.mean()) by a fixed-order double sum when the caller has none
 // The contract is in include/gauspcc.h.  Per element, in float32 and in torch's expression order (no contraction): t = tanhf(adj),
 // Q = Q0 * (1 + t), y = x + u * Q.  The noise u is the caller's: which random numbers a seeded run consumes does not change.
 //
@@ -130,7 +132,140 @@ int make_args(const char *who, int64_t n, int nattr, const float *const *a, cons
     return GPCC_OK;
 }
 
+// ------------------------------------------------------------------ the quantiser (STE_multistep's forward; no backward: every caller detaches)
+struct QArgs {
+    Args P;
+    const float *means;       // nattr device scalars
+    int clamp;
+};
+
+template <int V> __device__ __forceinline__ void quant_vec(const Attr &A, uint64_t e, float q, float lo, float hi, bool clamp)
+{
+    typedef typename Vec<V>::type T;
+    const T xv = *reinterpret_cast<const T *>(A.x + e);
+    T yv;
+    const float *xs = reinterpret_cast<const float *>(&xv);
+    float *ys = reinterpret_cast<float *>(&yv);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        float v = xs[i];
+        if (clamp) {            // torch.clamp: a NaN element stays NaN
+            v = v < lo ? lo : v;
+            v = v > hi ? hi : v;
+        }
+        ys[i] = rintf(v / q) * q;      // IEEE division (-fhip-fp32-correctly-rounded-divide-sqrt), half to even, no contraction
+    }
+    *reinterpret_cast<T *>(A.y + e) = yv;
+}
+
+// blockIdx.y = the attribute, a lane per vector of it
+__global__ __launch_bounds__(TB) void k_quantise(QArgs Q, float *__restrict__ q_out)
+{
+    const Args &P = Q.P;
+    const int j = blockIdx.y;
+    const Attr &A = P.a[j];
+    const uint32_t w = A.width;
+    const uint64_t e = ((uint64_t)blockIdx.x * TB + threadIdx.x) * (uint32_t)A.vec;
+    if (e >= (uint64_t)P.n * w) return;
+    const uint32_t row = (uint32_t)e / w, col = (uint32_t)e - row * w;      // n w < 2^31 (checked by the host)
+    float q = A.q0;
+    if (P.adj) q = A.q0 * (P.base + tanhf(P.adj[(int64_t)row * P.adj_stride + A.col]));
+    if (col == 0) q_out[(uint64_t)row * P.nattr + j] = q;
+    const float m = Q.means[j], r = 15000.0f * q, lo = m - r, hi = m + r;
+    if (A.vec == 4) quant_vec<4>(A, e, q, lo, hi, Q.clamp);
+    else if (A.vec == 2) quant_vec<2>(A, e, q, lo, hi, Q.clamp);
+    else quant_vec<1>(A, e, q, lo, hi, Q.clamp);
+}
+
+// ------------------------------------------------------------------ the means: MEAN_PARTS workgroups per tensor, then one
+constexpr int MEAN_PARTS = 256;
+
+struct MeanArgs {
+    const float *x[MAX_ATTR];
+    int64_t count[MAX_ATTR];
+};
+
+// the workgroup's TB doubles to one, a fixed tree
+__device__ __forceinline__ double block_sum(double s, double *sh)
+{
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = TB / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// thread t of workgroup b adds the elements b TB + t, + MEAN_PARTS TB, ... in ascending order
+__global__ __launch_bounds__(TB) void k_mean_partial(MeanArgs M, double *__restrict__ partials)
+{
+    __shared__ double sh[TB];
+    const int j = blockIdx.y;
+    const float *x = M.x[j];
+    const int64_t n = M.count[j];
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)MEAN_PARTS * TB) s += (double)x[i];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) partials[j * MEAN_PARTS + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(TB) void k_mean_final(MeanArgs M, const double *__restrict__ partials, float *__restrict__ means)
+{
+    __shared__ double sh[TB];
+    static_assert(MEAN_PARTS == TB, "one partial per thread");
+    const int j = blockIdx.x;
+    const double s = block_sum(partials[j * MEAN_PARTS + threadIdx.x], sh);
+    if (threadIdx.x == 0) means[j] = (float)(s / (double)M.count[j]);
+}
+
 }  // namespace
+
+extern "C" int gsnn_mean(gpcc_ctx *ctx, int nattr, const float *const *x, const int64_t *counts, double *partials, float *means, void *stream)
+{
+    if (!ctx) return fail(GPCC_ERR_ARG, "gsnn_mean: null context");
+    if (nattr < 1 || nattr > MAX_ATTR || !x || !counts || !partials || !means) return fail(GPCC_ERR_ARG, "gsnn_mean: %d tensors (1..%d) or a null argument", nattr, MAX_ATTR);
+    MeanArgs M;
+    for (int j = 0; j < nattr; ++j) {
+        if (counts[j] < 0 || (counts[j] > 0 && !x[j])) return fail(GPCC_ERR_ARG, "gsnn_mean: tensor %d of %lld elements", j, (long long)counts[j]);
+        M.x[j] = x[j];
+        M.count[j] = counts[j];      // an empty tensor's mean is 0 / 0 = NaN, as torch's
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    k_mean_partial<<<dim3(MEAN_PARTS, (unsigned)nattr), TB, 0, (hipStream_t)stream>>>(M, partials);
+    LAUNCH_CHECK();
+    k_mean_final<<<(unsigned)nattr, TB, 0, (hipStream_t)stream>>>(M, partials, means);
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
+
+extern "C" int gsnn_quantise(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const int64_t *widths, const double *q0, const float *adj,
+                             int64_t adj_stride, const int *adj_cols, double base, const float *means, int use_clamp, float *const *y, float *q_out,
+                             void *stream)
+{
+    if (!ctx) return fail(GPCC_ERR_ARG, "gsnn_quantise: null context");
+    QArgs Q;
+    GP_TRY(make_args("gsnn_quantise", n, nattr, x, x, widths, q0, adj, adj_stride, adj_cols, base, Q.P));
+    if (n == 0) return GPCC_OK;
+    if (!y || !q_out || !means) return fail(GPCC_ERR_ARG, "gsnn_quantise: null output or means");
+    Q.means = means;
+    Q.clamp = use_clamp != 0;
+    int64_t lanes = 0;
+    for (int j = 0; j < nattr; ++j) {
+        if (!y[j]) return fail(GPCC_ERR_ARG, "gsnn_quantise: null output of attribute %d", j);
+        Attr &A = Q.P.a[j];
+        A.y = y[j];
+        A.u = nullptr;
+        const uint32_t w = A.width;
+        A.vec = (w % 4 == 0 && aligned(A.x, 16) && aligned(A.y, 16)) ? 4 : (w % 2 == 0 && aligned(A.x, 8) && aligned(A.y, 8)) ? 2 : 1;
+        const int64_t v = n * w / A.vec;
+        lanes = v > lanes ? v : lanes;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    k_quantise<<<dim3((unsigned)cdiv(lanes, TB), (unsigned)nattr), TB, 0, (hipStream_t)stream>>>(Q, q_out);
+    LAUNCH_CHECK();
+    return GPCC_OK;
+}
 
 extern "C" int gsnn_noise_forward_b(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const float *const *u, const int64_t *widths, const double *q0,
                                     const float *adj, int64_t adj_stride, const int *adj_cols, double base, float *const *y, float *q_out, void *stream)

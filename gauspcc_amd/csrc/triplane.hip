@@ -1,6 +1,9 @@
 // triplane.hip -- TC-GS's tri-plane context sampler (TC-GS/utils/triplane.py: sample_from_planes, Triplane.sample), forward and backward:
 //   gsge_plane_forward   out (N, K 3 C): every sample (n, k) read bilinearly from the three (C, H, W) feature planes
 //   gsge_plane_backward  the plane gradient (no float atomics) and, when wanted, the coordinate gradient
+//   gsge_plane_rows_forward / _backward   the same with an output row of K 3 C + T floats whose last T columns are a copy of a row-aligned
+//                        (N, T) tail (TC-GS: the anchor, T = 3: the (N, 603) input of mlp_triplane, without torch.cat); the backward reads the
+//                        upstream gradient in place with that row stride.  The two entry points above forward here with T = 0: the same bits.
 //
 // Arithmetic per sample and plane p, float32 in the reference's expression order (include/gauspcc.h has the full contract):
 //   mag_p = sqrt(min(min(|proj_p(max)|^2, |proj_p(min)|^2), radii^2)), proj_0 = (x, y), proj_1 = (x, z), proj_2 = (z, x)
@@ -10,14 +13,17 @@
 //
 // The planes are first transposed to channel-last (3, H W, C) in the caller's workspace (3 C H W floats, read and written once: ~1 % of the
 // output's traffic at 1 M anchors): a corner is then C contiguous floats instead of C cache lines.
-// Forward: a workgroup owns PF_SAMPLES consecutive (n, k) samples = a contiguous piece of the row-major output.  One thread per (sample,
-// plane) leaves four texel indices and weights in LDS; then the workgroup walks its output elements in order, so a wave's stores (and its
-// four corner reads) are contiguous.  The repeat form (coordinates (N, 3), K copies) computes an anchor's three entries once and writes
-// them to the K slots the walk reads.
+// Forward: a workgroup owns whole output rows -- floor(PF_SAMPLES / K) of them, K 3 C + T floats each -- which is a contiguous piece of the
+// row-major output because the tensor is exactly that wide.  One thread per (sample, plane) leaves four texel indices and weights in LDS;
+// then the workgroup walks its output elements in order (element -> row and column by one magic division, feature column -> slot and channel
+// by a second; tail columns are copied from the tail), so a wave's scalar stores (and its four corner reads) are contiguous: 256 bytes per
+// store instruction wherever a row starts.  The repeat form (coordinates (N, 3), K copies) computes an anchor's three entries once and
+// writes them to the K slots the walk reads.  With T = 0 and (N, K, 3) coordinates the output is (N K, 3 C) in all but name: rows of one
+// sample, 64 per workgroup, for any K.
 // Backward, planes: one (texel row, slot) entry per (sample, plane, corner), sentinel for padding corners; stable radix sort by texel row;
 // sorted_sum.hpp's sum and combine with one wave per chunk of PB_CHUNK entries and one lane per channel, into a channel-last gradient that
 // is transposed back to (3, C, H, W).  The repeat form first adds the K copies of the upstream gradient per (n, plane) in k order.
-// Backward, coordinates: one thread per sample.
+// Backward, coordinates: one thread per sample.  All three read the upstream gradient through GradRows: row n of it starts at n * stride.
 #include "common.hpp"
 #include "primitives.hpp"
 #include "sorted_sum.hpp"
@@ -30,9 +36,9 @@ using namespace gpcc;
 namespace {
 
 constexpr int TB = 256;
-constexpr int PF_SAMPLES = 64;            // (n, k) samples per forward workgroup
+constexpr int PF_SAMPLES = 64;            // (n, k) samples per forward workgroup, at most
 constexpr int PF_SLOTS = PF_SAMPLES * 3;  // their (sample, plane) entries
-constexpr int MAX_C = 256, MAX_SIZE = 4096;
+constexpr int MAX_C = 256, MAX_SIZE = 4096, MAX_TAIL = 16;
 constexpr int PB_CHUNK = 256;             // sorted entries per wave of the sum pass
 constexpr int PB_WALK = 8;
 
@@ -41,6 +47,24 @@ struct Geom {
     int rep;           // output copies per coordinate row (1: coordinates are (N, K, 3))
     uint32_t magic;    // floor(2^32 / C) + 1: e / C = umulhi(e, magic) for e < 2^16 (C >= 2)
     float radii_sq;
+    // the output rows: `per` coordinate rows and `slots` = (sample, plane) entries each, slots C + tail floats wide, `rows` of them per workgroup
+    int per, slots, tail, rows;
+    uint32_t width, magic_w;   // width = slots C + tail >= 3; floor(2^32 / width) + 1, for e < 2^16 as above
+};
+
+// The upstream gradient of (coordinate row, plane) entry u, C contiguous floats: entry u of a contiguous (U, C) matrix (per == 0), or entry
+// u % per of row u / per of a matrix whose rows are `stride` floats apart (the (N, K 3 C + T) gradient read in place).
+struct GradRows {
+    const float *__restrict__ g;
+    int64_t stride;
+    uint32_t per;
+    int C;
+    __device__ __forceinline__ const float *at(uint32_t u) const
+    {
+        if (per == 0) return g + (int64_t)u * C;
+        const uint32_t n = u / per;
+        return g + (int64_t)n * stride + (int64_t)(u - n * per) * C;
+    }
 };
 
 // sqrt(mag_sq[p]) from the bounds (device memory: no host copy, no synchronisation)
@@ -125,15 +149,18 @@ void transpose_launch(hipStream_t st, const float *in, float *out, int batch, in
 }
 
 // ------------------------------------------------------------------ forward
-// M coordinate rows; workgroup b owns rows [b R, (b + 1) R), R = PF_SAMPLES / rep, and the rep 3 C output elements of each
+// NR output rows; workgroup b owns rows [b G.rows, (b + 1) G.rows): their G.per coordinate rows each and their G.width output floats each.
+// G.rows G.per G.rep <= PF_SAMPLES samples, so the slots fit the LDS tables and an element index stays below 2^16.
 __global__ __launch_bounds__(TB) void k_plane_fwd(const float *__restrict__ planes_cl, const float *__restrict__ coords, const float *__restrict__ maxc,
-                                                  const float *__restrict__ minc, Geom G, int64_t M, float *__restrict__ out)
+                                                  const float *__restrict__ minc, const float *__restrict__ tail, Geom G, int64_t NR,
+                                                  float *__restrict__ out)
 {
     __shared__ int4 st[PF_SLOTS];
     __shared__ float4 sw[PF_SLOTS];
-    const int R = PF_SAMPLES / G.rep;
-    const int64_t r0 = (int64_t)blockIdx.x * R;
-    const int nr = (int)min((int64_t)R, M - r0);
+    const int64_t a0 = (int64_t)blockIdx.x * G.rows;
+    const int na = (int)min((int64_t)G.rows, NR - a0);
+    const int64_t r0 = a0 * G.per;
+    const int nr = na * G.per;
     for (int u = threadIdx.x; u < nr * 3; u += TB) {
         const int r = u / 3, p = u - 3 * r;
         const Pixel q = plane_pixel(coords + (r0 + r) * 3, p, plane_mag(maxc, minc, G.radii_sq, p), G.H, G.W);
@@ -147,10 +174,21 @@ __global__ __launch_bounds__(TB) void k_plane_fwd(const float *__restrict__ plan
         }
     }
     __syncthreads();
-    const uint32_t C = (uint32_t)G.C, ne = (uint32_t)(nr * G.rep * 3) * C;
-    float *o = out + r0 * G.rep * 3 * (int64_t)C;
+    const uint32_t C = (uint32_t)G.C, width = G.width, feat = width - (uint32_t)G.tail, ne = (uint32_t)na * width;
+    float *o = out + a0 * (int64_t)width;
+    const float *tl = tail ? tail + a0 * G.tail : nullptr;
     for (uint32_t e = threadIdx.x; e < ne; e += TB) {
-        const uint32_t slot = C == 1 ? e : __umulhi(e, G.magic), ch = e - slot * C;
+        uint32_t a = 0, col = e;
+        if (G.tail) {      // without a tail the rows are one run of slots: no row boundary to find
+            a = __umulhi(e, G.magic_w);
+            col = e - a * width;
+            if (col >= feat) {
+                o[e] = tl[a * (uint32_t)G.tail + (col - feat)];
+                continue;
+            }
+        }
+        const uint32_t sl = C == 1 ? col : __umulhi(col, G.magic), ch = col - sl * C;
+        const uint32_t slot = a * (uint32_t)G.slots + sl;
         const int4 t = st[slot];
         const float4 w = sw[slot];
         float v = 0.0f;
@@ -163,13 +201,13 @@ __global__ __launch_bounds__(TB) void k_plane_fwd(const float *__restrict__ plan
 }
 
 // ------------------------------------------------------------------ backward
-// repeat form: folded[(n 3 + p) C + ch] = sum over k, in k order, of grad[((n K + k) 3 + p) C + ch]
-__global__ __launch_bounds__(TB) void k_plane_fold(const float *__restrict__ grad, int64_t total, int row, int K, float *__restrict__ folded)
+// repeat form: folded[(n 3 + p) C + ch] = sum over k, in k order, of grad[n stride + (k 3 + p) C + ch]
+__global__ __launch_bounds__(TB) void k_plane_fold(const float *__restrict__ grad, int64_t stride, int64_t total, int row, int K, float *__restrict__ folded)
 {
     const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
     if (i >= total) return;
     const int64_t n = i / row;
-    const float *g = grad + n * row * K + (i - n * row);
+    const float *g = grad + n * stride + (i - n * row);
     float s = g[0];
     for (int k = 1; k < K; ++k) s += g[(int64_t)k * row];
     folded[i] = s;
@@ -198,7 +236,7 @@ __global__ __launch_bounds__(TB) void k_plane_keys(const float *__restrict__ coo
 
 // one lane = one channel of the wave's chunk; g: upstream gradient per (coordinate row, plane), C contiguous floats each
 struct PlaneRowSum {
-    const float *__restrict__ g;
+    GradRows g;
     const uint32_t *__restrict__ slots;
     const float *__restrict__ wts;
     float *__restrict__ grad_cl, *__restrict__ head, *__restrict__ tail;
@@ -208,7 +246,7 @@ struct PlaneRowSum {
     __device__ __forceinline__ void add(int64_t i)
     {
         const uint32_t s = slots[i];
-        acc = __builtin_fmaf(wts[s], g[(int64_t)(s >> 2) * C + ch], acc);
+        acc = __builtin_fmaf(wts[s], g.at(s >> 2)[ch], acc);
     }
     __device__ __forceinline__ void to_head(int64_t t) { head[t * C + ch] = acc; }
     __device__ __forceinline__ void to_tail(int64_t t) { tail[t * C + ch] = acc; }
@@ -217,7 +255,7 @@ struct PlaneRowSum {
 
 // grad_cl is zeroed before: a texel row is written once, by the sum or by the combine pass
 __global__ __launch_bounds__(TB) void k_plane_bwd_sum(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ slots, const float *__restrict__ wts,
-                                                      const float *__restrict__ g, int C, int64_t E, uint32_t n_rows, float *__restrict__ grad_cl,
+                                                      GradRows g, int C, int64_t E, uint32_t n_rows, float *__restrict__ grad_cl,
                                                       float *__restrict__ head, float *__restrict__ tail, uint8_t *__restrict__ own)
 {
     const int64_t t = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
@@ -241,7 +279,7 @@ __global__ __launch_bounds__(TB) void k_plane_bwd_combine(const uint64_t *__rest
 // Coordinate gradient, one thread per coordinate row.  d out / d pixel as grid_sample's backward forms it, then through
 // pixel = ((g + 1) size - 1) / 2, g = z / 2, z = contract(x) (both branches), x = 6 (2 c / mag * 2 - 1).
 __global__ __launch_bounds__(TB) void k_plane_bwd_coords(const float *__restrict__ planes_cl, const float *__restrict__ coords, const float *__restrict__ maxc,
-                                                         const float *__restrict__ minc, Geom G, int64_t M, const float *__restrict__ g,
+                                                         const float *__restrict__ minc, Geom G, int64_t M, GradRows g,
                                                          float *__restrict__ grad_coords)
 {
     const int64_t r = (int64_t)blockIdx.x * TB + threadIdx.x;
@@ -256,7 +294,7 @@ __global__ __launch_bounds__(TB) void k_plane_bwd_coords(const float *__restrict
         if (!plane_corners(q, p, G.H, G.W, t, w)) continue;
         const float xw = floorf(q.ix), yn = floorf(q.iy);
         const float dxe = (xw + 1.0f) - q.ix, dxw = q.ix - xw, dys = (yn + 1.0f) - q.iy, dyn = q.iy - yn;
-        const float *go = g + (r * 3 + p) * (int64_t)C;
+        const float *go = g.at((uint32_t)(r * 3 + p));
         float gix = 0.0f, giy = 0.0f;
         for (int ch = 0; ch < C; ++ch) {
             const float gv = go[ch];
@@ -283,54 +321,79 @@ __global__ __launch_bounds__(TB) void k_plane_bwd_coords(const float *__restrict
     for (int d = 0; d < 3; ++d) grad_coords[r * 3 + d] = gc[d];
 }
 
-int check_args(const char *who, int64_t n, int k, int repeat, int C, int H, int W, Geom &G, int64_t &M)
+uint32_t magic_of(int d) { return (uint32_t)((((uint64_t)1 << 32) / (uint64_t)d) + 1); }
+
+// NR: the output rows the forward's workgroups are dealt (n, or n k one-sample rows when there is no tail and no repeat)
+int check_args(const char *who, int64_t n, int k, int repeat, int C, int H, int W, int T, Geom &G, int64_t &M, int64_t &NR)
 {
     if (n < 0 || k < 1) return fail(GPCC_ERR_ARG, "%s: n = %lld, k = %d", who, (long long)n, k);
     if (C < 1 || C > MAX_C) return fail(GPCC_ERR_ARG, "%s: %d channels outside [1, %d]", who, C, MAX_C);
     if (H < 2 || H > MAX_SIZE || W < 2 || W > MAX_SIZE) return fail(GPCC_ERR_ARG, "%s: planes of %d x %d outside [2, %d]", who, H, W, MAX_SIZE);
+    if (T < 0 || T > MAX_TAIL) return fail(GPCC_ERR_ARG, "%s: a tail of %d columns outside [0, %d]", who, T, MAX_TAIL);
     if (repeat && k > PF_SAMPLES) return fail(GPCC_ERR_ARG, "%s: repeat = %d above %d", who, k, PF_SAMPLES);
+    if (T && k > PF_SAMPLES) return fail(GPCC_ERR_ARG, "%s: k = %d above %d with a tail (a workgroup owns whole rows)", who, k, PF_SAMPLES);
     if (n * k * 12 >= ((int64_t)1 << 32)) return fail(GPCC_ERR_ARG, "%s: %lld x %d samples: more than 2^32 (sample, plane, corner) slots", who, (long long)n, k);
     G.C = C; G.H = H; G.W = W;
     G.rep = repeat ? k : 1;
-    G.magic = (uint32_t)((((uint64_t)1 << 32) / (uint64_t)C) + 1);   // unused for C = 1
+    G.magic = magic_of(C);   // unused for C = 1
     M = repeat ? n : n * k;
+    G.tail = T;
+    if (T == 0 && !repeat) {     // (n k, 3 C): rows of one sample
+        NR = n * k;
+        G.per = 1; G.slots = 3; G.rows = PF_SAMPLES;
+    } else {
+        NR = n;
+        G.per = repeat ? 1 : k; G.slots = 3 * k; G.rows = PF_SAMPLES / k;
+    }
+    G.width = (uint32_t)(G.slots * C + T);
+    G.magic_w = magic_of((int)G.width);
     return GPCC_OK;
 }
 
 }  // namespace
 
-extern "C" int gsge_plane_forward(gpcc_ctx *ctx, const float *planes, const float *coordinates, const float *max_coords, const float *min_coords,
-                                  double radii, int64_t n, int k, int repeat, int channels, int height, int width, float *out, gsr_alloc_fn alloc,
-                                  void *alloc_user, void *stream)
+extern "C" int gsge_plane_rows_forward(gpcc_ctx *ctx, const float *planes, const float *coordinates, const float *max_coords, const float *min_coords,
+                                       double radii, int64_t n, int k, int repeat, int channels, int height, int width, const float *tail, int tail_width,
+                                       float *out, gsr_alloc_fn alloc, void *alloc_user, void *stream)
 {
-    if (!ctx) return fail(GPCC_ERR_ARG, "gsge_plane_forward: null context");
+    const char *who = tail_width ? "gsge_plane_rows_forward" : "gsge_plane_forward";
+    if (!ctx) return fail(GPCC_ERR_ARG, "%s: null context", who);
     Geom G;
-    int64_t M;
-    GP_TRY(check_args("gsge_plane_forward", n, k, repeat, channels, height, width, G, M));
+    int64_t M, NR;
+    GP_TRY(check_args(who, n, k, repeat, channels, height, width, tail_width, G, M, NR));
     if (n == 0) return GPCC_OK;
-    if (!planes || !coordinates || !max_coords || !min_coords || !out || !alloc) return fail(GPCC_ERR_ARG, "gsge_plane_forward: null argument");
+    if (!planes || !coordinates || !max_coords || !min_coords || !out || !alloc || (tail_width && !tail)) return fail(GPCC_ERR_ARG, "%s: null argument", who);
     G.radii_sq = (float)(radii * radii);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)height * width;
     float *planes_cl;
-    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)(3 * HW * channels) * sizeof(float), &planes_cl, "gsge_plane_forward"));
+    GP_TRY(caller_alloc(alloc, alloc_user, (size_t)(3 * HW * channels) * sizeof(float), &planes_cl, who));
     transpose_launch(st, planes, planes_cl, 3, channels, HW);
     LAUNCH_CHECK();
-    k_plane_fwd<<<(unsigned)cdiv(M, PF_SAMPLES / G.rep), TB, 0, st>>>(planes_cl, coordinates, max_coords, min_coords, G, M, out);
+    k_plane_fwd<<<(unsigned)cdiv(NR, G.rows), TB, 0, st>>>(planes_cl, coordinates, max_coords, min_coords, tail_width ? tail : nullptr, G, NR, out);
     LAUNCH_CHECK();
     return GPCC_OK;
 }
 
-extern "C" int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const float *planes, const float *coordinates, const float *max_coords,
-                                   const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
-                                   float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream)
+extern "C" int gsge_plane_forward(gpcc_ctx *ctx, const float *planes, const float *coordinates, const float *max_coords, const float *min_coords,
+                                  double radii, int64_t n, int k, int repeat, int channels, int height, int width, float *out, gsr_alloc_fn alloc,
+                                  void *alloc_user, void *stream)
 {
-    if (!ctx) return fail(GPCC_ERR_ARG, "gsge_plane_backward: null context");
+    return gsge_plane_rows_forward(ctx, planes, coordinates, max_coords, min_coords, radii, n, k, repeat, channels, height, width, nullptr, 0, out, alloc,
+                                   alloc_user, stream);
+}
+
+extern "C" int gsge_plane_rows_backward(gpcc_ctx *ctx, const float *grad_out, const float *planes, const float *coordinates, const float *max_coords,
+                                        const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
+                                        int tail_width, float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream)
+{
+    const char *who = tail_width ? "gsge_plane_rows_backward" : "gsge_plane_backward";
+    if (!ctx) return fail(GPCC_ERR_ARG, "%s: null context", who);
     Geom G;
-    int64_t M;
-    GP_TRY(check_args("gsge_plane_backward", n, k, repeat, channels, height, width, G, M));
-    if (!grad_planes || !alloc) return fail(GPCC_ERR_ARG, "gsge_plane_backward: null argument");
+    int64_t M, NR;
+    GP_TRY(check_args(who, n, k, repeat, channels, height, width, tail_width, G, M, NR));
+    if (!grad_planes || !alloc) return fail(GPCC_ERR_ARG, "%s: null argument", who);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int C = channels;
@@ -339,27 +402,30 @@ extern "C" int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const f
         HIP_TRY(hipMemsetAsync(grad_planes, 0, (size_t)plane_floats * sizeof(float), st));
         return GPCC_OK;
     }
-    if (!grad_out || !planes || !coordinates || !max_coords || !min_coords) return fail(GPCC_ERR_ARG, "gsge_plane_backward: null argument");
+    if (!grad_out || !planes || !coordinates || !max_coords || !min_coords) return fail(GPCC_ERR_ARG, "%s: null argument", who);
     G.radii_sq = (float)(radii * radii);
     const bool fold = repeat && k > 1;
     const int64_t U = M * 3, E = U * 4, nchunks = cdiv(E, PB_CHUNK);
+    const int64_t stride = (int64_t)k * 3 * C + tail_width;      // floats between two rows of grad_out
     const uint32_t n_rows = (uint32_t)(3 * HW);
     uint64_t *ka, *kb;
     uint32_t *va, *vb, *hist;
     float *wts, *head, *tail, *grad_cl, *planes_cl = nullptr, *folded = nullptr;
     uint8_t *own;
-    GP_TRY(caller_block(alloc, alloc_user, "gsge_plane_backward", [&](Carver &c) {
+    GP_TRY(caller_block(alloc, alloc_user, who, [&](Carver &c) {
         ka = c.take<uint64_t>(E); kb = c.take<uint64_t>(E); va = c.take<uint32_t>(E); vb = c.take<uint32_t>(E); wts = c.take<float>(E);
         hist = c.take<uint32_t>(radix_sort_hist_words(E)); head = c.take<float>(nchunks * C); tail = c.take<float>(nchunks * C);
         own = c.take<uint8_t>(nchunks); grad_cl = c.take<float>(plane_floats);
         if (grad_coordinates) planes_cl = c.take<float>(plane_floats);
         if (fold) folded = c.take<float>(U * C);
     }));
-    const float *g = grad_out;
+    // entry u = (coordinate row, plane): contiguous without a tail (and after the fold); else 3 k entries per row of grad_out (3 in the
+    // repeat form with k = 1)
+    GradRows g{grad_out, stride, tail_width ? (uint32_t)(3 * k) : 0u, C};
     if (fold) {
-        k_plane_fold<<<(unsigned)cdiv(U * C, TB), TB, 0, st>>>(grad_out, U * C, 3 * C, k, folded);
+        k_plane_fold<<<(unsigned)cdiv(U * C, TB), TB, 0, st>>>(grad_out, stride, U * C, 3 * C, k, folded);
         LAUNCH_CHECK();
-        g = folded;
+        g = GradRows{folded, 0, 0u, C};
     }
     k_plane_keys<<<(unsigned)cdiv(U, TB), TB, 0, st>>>(coordinates, max_coords, min_coords, G, U, n_rows, ka, va, wts);
     LAUNCH_CHECK();
@@ -383,4 +449,12 @@ extern "C" int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const f
         LAUNCH_CHECK();
     }
     return GPCC_OK;
+}
+
+extern "C" int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const float *planes, const float *coordinates, const float *max_coords,
+                                   const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
+                                   float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream)
+{
+    return gsge_plane_rows_backward(ctx, grad_out, planes, coordinates, max_coords, min_coords, radii, n, k, repeat, channels, height, width, 0, grad_planes,
+                                    grad_coordinates, alloc, alloc_user, stream);
 }

@@ -11,7 +11,7 @@ test (:188-205) where HAC multiplies them into the opacity before it (:136-137) 
 `is_training=True` serves HAC's training branch (:47-98 and the 11-tuple of :170): the gathers, the quantisation noise, the
 context model's rate terms on the 5 % chosen anchors (the model's own torch modules: they train too) and then the differentiable core
 neural_gaussians_train (gsnn_forward_train / gsnn_backward), which HAC++, TC-GS and CAT-3DGS callers can use after their own rate code.
-HAC++'s training branch is gauspcc_amd.hac_plus_renderer, CAT-3DGS's renderer gauspcc_amd.cat_renderer, both built on that core, on quant_noise
+HAC++'s training branch is gauspcc_amd.hac_plus_renderer, CAT-3DGS's renderer gauspcc_amd.cat_renderer, TC-GS's gauspcc_amd.tcgs_renderer, all built on that core, on quant_noise
 below (gsnn_noise_forward_b / _backward_b) and, for inference, on _generate_tail.
 The model `pc` is used through the attributes the reference uses.  When `pc.decoded_version` is false the attributes are first quantised
 with the context model's step sizes exactly as the reference does (:103-114); everything after that -- view vectors,
@@ -280,6 +280,50 @@ def quant_noise(xs, us, q0s, adj=None, cols=None, base=1.0):
     gradient is the incoming tensor itself) and adj (gsnn_noise_backward, bitwise reproducible).  Float32 CUDA tensors only."""
     _noise_args(xs, us, q0s, adj, cols)
     return _QuantNoise.apply((list(us), list(q0s), cols, float(base)), adj, *xs)
+
+
+def fixed_order_mean(*xs):
+    """The means of up to three float32 CUDA tensors as a (len(xs),) device tensor, each a double sum in a fixed order rounded once
+    (gsnn_mean): bitwise reproducible, within float32 rounding of `x.mean()`.  What `quantise_steps` uses when it is given no means."""
+    if not 1 <= len(xs) <= 3 or any(not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda for x in xs):
+        raise ValueError("fixed_order_mean: one to three float32 CUDA tensors")
+    dev = xs[0].device
+    xc = [x.detach().contiguous() for x in xs]
+    T = len(xc)
+    partials = torch.empty(T * 256, dtype=torch.float64, device=dev)
+    means = torch.empty(T, device=dev)
+    _lib.check(_lib.lib().gsnn_mean(runtime.context(dev), T, ptrs(xc), (C.c_int64 * T)(*[x.numel() for x in xc]), partials.data_ptr(), means.data_ptr(),
+                                    runtime.stream_ptr(dev)))
+    return means
+
+
+@torch.no_grad()
+def quantise_steps(xs, q0s, adj, cols=None, base=1.0, means=None):
+    """STE_multistep's forward on up to three row-aligned attributes in one launch (gsnn_quantise), the evaluation side of `quant_noise`:
+    y_j = round(clamp(xs[j], m_j - 15000 Q_j, m_j + 15000 Q_j) / Q_j) * Q_j with Q_j[r] = q0s[j] * (base + tanh(adj[r, cols[j]])); adj is read
+    in place (a column slice of the context MLP's output costs no copy).  means: one 0-d tensor or number per attribute (the reference's
+    `pc._anchor_feat.mean()`, ...), or None for the means of the xs themselves (STE_multistep's default `input.mean()`), which
+    `fixed_order_mean` forms in two more launches.  The clamp follows anchor_codec.USE_CLAMP.  Returns (y_0, ..., Q) with Q (n, len(xs)) as
+    quant_noise returns it.  Detached: no backward (every caller of the reference detaches the result).  Float32 CUDA tensors only."""
+    from . import anchor_codec
+    if adj is None:
+        raise ValueError("quantise_steps: adj is required (the step is Q0 * (base + tanh(adj)))")
+    n, widths, c_w, c_q, c_cols = _noise_args(xs, xs, q0s, adj, cols)
+    dev, T = xs[0].device, len(xs)
+    xc = [x.detach().contiguous() for x in xs]
+    if means is None:
+        m = fixed_order_mean(*xc)
+    else:
+        if len(means) != T:
+            raise ValueError(f"quantise_steps: {len(means)} means for {T} attributes")
+        m = torch.stack([torch.as_tensor(v, dtype=torch.float32, device=dev).detach().reshape(()) for v in means])
+    ys = [torch.empty_like(x) for x in xc]
+    q = torch.empty(n, T, device=dev)
+    a = _adj_view(adj.detach())
+    if n:
+        _lib.check(_lib.lib().gsnn_quantise(runtime.context(dev), n, T, ptrs(xc), c_w, c_q, a.data_ptr(), a.stride(0), c_cols, float(base), m.data_ptr(),
+                                            int(bool(anchor_codec.USE_CLAMP)), ptrs(ys), q.data_ptr(), runtime.stream_ptr(dev)))
+    return (*ys, q)
 
 
 def _generate_training(viewpoint_camera, pc, visible_mask, step):

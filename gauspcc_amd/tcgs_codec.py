@@ -1,10 +1,11 @@
-"""GaussianModel.conduct_encoding / conduct_decoding of TC-GS (src/gs_compress/TC-GS/scene/gaussian_model.py:1135-1311, 1313-1465) on the
-gfx950 kernels.  Both functions take the model as their first argument and touch it only through the attributes the reference methods touch,
-so they bind as methods:
+"""GaussianModel.conduct_encoding / conduct_decoding / estimate_final_bits of TC-GS (src/gs_compress/TC-GS/scene/gaussian_model.py:1135-1311,
+1313-1465, 1072-1133) on the gfx950 kernels.  The functions take the model as their first argument and touch it only through the attributes
+the reference methods touch, so they bind as methods:
 
     from gauspcc_amd import tcgs_codec
     GaussianModel.conduct_encoding = tcgs_codec.conduct_encoding
     GaussianModel.conduct_decoding = tcgs_codec.conduct_decoding
+    GaussianModel.estimate_final_bits = tcgs_codec.estimate_final_bits
 
 Same files under `pre_path_name` (xyz_pcc.bin, feat_{s}.b, scaling_{s}.b, offsets_{s}.b, masks.b, and hash.b when `ste_binary`), each attribute
 file ONE raw torchac stream per 1 000-anchor slice; the same twelve-element `patched_infos` (the per-slice min / max lists of 0-d tensors,
@@ -37,6 +38,7 @@ from .torchac_encodings import decoder, decoder_gaussian_slices, encoder, encode
 
 K = 4                              # TC-GS/scene/gaussian_model.py:32
 MAX_BATCH_SIZE = 1_000             # :1173
+anchor_round_digits = 16           # TC-GS/utils/encodings.py:11
 _CONTEXT_ROWS = 1 << 17            # anchors per pass of the context (603 floats of features each: 0.3 GB at a time, whatever the scene's size)
 
 
@@ -202,3 +204,83 @@ def conduct_decoding(self, pre_path_name, patched_infos, ckpt_path=None):
         self.triplane.planes = torch.nn.Parameter(hash_embeddings)
     print('Parameters are successfully replaced by decoded ones!')
     return f"\nDecTime {round(t2 - t1, 4)}"
+
+
+# ---------------------------------------------------------------- rate estimate
+def _binary_vxl_bits(binary_vxl):
+    """get_binary_vxl_size(...)[1] (TC-GS/utils/encodings.py:16-34)"""
+    ttl_num = binary_vxl.numel()
+    pos_num = torch.sum(binary_vxl)
+    neg_num = ttl_num - pos_num
+    Pg = torch.clamp(pos_num / ttl_num, min=1e-6, max=1 - 1e-6)
+    return pos_num * (-torch.log2(Pg)) + neg_num * (-torch.log2(1 - Pg)) + 32
+
+
+def update_knn(self):
+    """(:1060-1069) on the device: the K nearest kept anchors of every kept anchor (gauspcc_amd.knn.kneighbors in place of sklearn on the
+    host).  As in the reference the indices count the KEPT anchors and are then looked up in the full `self._anchor`."""
+    from .knn import kneighbors
+    _anchor = self.get_anchor[self.get_mask_anchor]
+    self.knn_indices = kneighbors(_anchor.detach(), K).to(torch.long)
+    self.knnanchor = self._anchor[self.knn_indices].detach()
+
+
+@torch.no_grad()
+def estimate_final_bits(self):
+    """(:1072-1133) the rate estimate on the kept anchors: update_knn, the context rows of `knnanchor` in the (N, K, 3) form, the three
+    STE_multistep calls WITHOUT a mean argument (input.mean()) in one launch (quantise_steps; Q_offsets is the codec's 0.2 here, :1077),
+    entropy_models.Entropy_gaussian in place of the coder, the reference's `print` and log string.
+    Side effect, as in the reference (:1094): `self.triplane.autoencoder.encoder` is None afterwards -- the encoder half of the plane
+    autoencoder is not part of the shipped model, and `get_mlp_size` counts what is left."""
+    from . import entropy_models
+    from .neural_gaussians import quantise_steps
+    from .tcgs_renderer import context_input
+    mask_anchor = self.get_mask_anchor
+    _anchor = self.get_anchor[mask_anchor]
+    update_knn(self)
+    knnanchor = self.knnanchor
+    _feat = self._anchor_feat[mask_anchor]
+    _grid_offsets = self._offset[mask_anchor]
+    _scaling = self.get_scaling[mask_anchor]
+    _mask = self.get_mask[mask_anchor]
+    hash_embeddings = self.get_encoding_params()
+    feat_dim, n_off = self.feat_dim, self.n_offsets
+    outs = []
+    for a in range(0, _anchor.shape[0], _CONTEXT_ROWS):
+        rows = context_input(self, _anchor[a:a + _CONTEXT_ROWS].contiguous(), knnanchor[a:a + _CONTEXT_ROWS].contiguous(), False, 0)[0]
+        outs.append(tri_mlp(self, rows))
+    self.triplane.autoencoder.encoder = None
+    ctx = torch.cat(outs, dim=0) if len(outs) != 1 else outs[0]
+    mean, scale, mean_scaling, scale_scaling, mean_offsets, scale_offsets, _, _, _ = torch.split(
+        ctx, split_size_or_sections=[feat_dim, feat_dim, 6, 6, 3 * n_off, 3 * n_off, 1, 1, 1], dim=-1)
+    _feat, grid_scaling, offsets, Q = quantise_steps([_feat, _scaling, _grid_offsets], (Q_FEAT, Q_SCALING, Q_OFFSETS), ctx[:, -3:])
+    offsets = offsets.view(-1, 3 * n_off)
+    mask_tmp = _mask.repeat(1, 1, 3).view(-1, 3 * n_off)
+    entropy = getattr(self, "entropy_gaussian", None) or entropy_models.Entropy_gaussian(Q=1)
+    bit_feat = entropy.forward(_feat, mean, scale, Q[:, 0:1])
+    bit_scaling = entropy.forward(grid_scaling, mean_scaling, scale_scaling, Q[:, 1:2])
+    bit_offsets = entropy.forward(offsets, mean_offsets, scale_offsets, Q[:, 2:3])
+    bit_offsets = bit_offsets * mask_tmp
+
+    bit_anchor = _anchor.shape[0] * 3 * anchor_round_digits
+    bit_feat = torch.sum(bit_feat).item()
+    bit_scaling = torch.sum(bit_scaling).item()
+    bit_offsets = torch.sum(bit_offsets).item()
+    if self.ste_binary:
+        bit_hash = _binary_vxl_bits((hash_embeddings + 1) / 2).item()
+    else:
+        bit_hash = hash_embeddings.numel() * 32
+    bit_masks = _binary_vxl_bits(_mask).item()
+
+    print(bit_anchor, bit_feat, bit_scaling, bit_offsets, bit_hash, bit_masks)
+    mlp_bits = self.get_mlp_size()[0] if hasattr(self, "get_mlp_size") else 0
+    log_info = f"\nEstimated sizes in MB: " \
+               f"anchor {round(bit_anchor/bit2MB_scale, 4)}, " \
+               f"feat {round(bit_feat/bit2MB_scale, 4)}, " \
+               f"scaling {round(bit_scaling/bit2MB_scale, 4)}, " \
+               f"offsets {round(bit_offsets/bit2MB_scale, 4)}, " \
+               f"triplane {round(bit_hash/bit2MB_scale, 4)}, " \
+               f"masks {round(bit_masks/bit2MB_scale, 4)}, " \
+               f"MLPs {round(mlp_bits/bit2MB_scale, 4)}, " \
+               f"Total {round((bit_anchor + bit_feat + bit_scaling + bit_offsets + bit_hash + bit_masks + mlp_bits)/bit2MB_scale, 4)}"
+    return log_info

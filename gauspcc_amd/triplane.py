@@ -1,4 +1,5 @@
-"""TC-GS's tri-plane context sampler on the device (gsge_plane_forward / gsge_plane_backward): a drop-in for utils/triplane.py,
+"""TC-GS's tri-plane context sampler on the device (gsge_plane_forward / gsge_plane_backward, and the context rows gsge_plane_rows_forward /
+_backward: the features with a row-aligned tail behind them, `triplane_rows` / `Triplane.context_rows`): a drop-in for utils/triplane.py,
 
     from utils.triplane import Triplane   ->   from gauspcc_amd.triplane import Triplane      (TC-GS/scene/gaussian_model.py:27)
 
@@ -118,6 +119,76 @@ def triplane_sample(planes, coordinates, max_coords, min_coords, radii, repeat=N
     return _forward(planes.detach().contiguous(), coordinates.detach().contiguous(), mx, mn, float(radii), N, K, repeat is not None)
 
 
+MAX_TAIL = 16   # gsge_plane_rows_forward's limit
+
+
+def _rows_forward(planes, coords, tail, mx, mn, radii, N, K, repeat):
+    dev = planes.device
+    C, H, W = planes.shape[1:]
+    T = tail.shape[1]
+    out = torch.empty((N, K * 3 * C + T), dtype=torch.float32, device=dev)
+    if N:
+        _lib.check(_lib.lib().gsge_plane_rows_forward(runtime.context(dev), planes.data_ptr(), coords.data_ptr(), mx.data_ptr(), mn.data_ptr(), float(radii),
+                                                      N, K, int(repeat), C, H, W, ptr(tail) if T else None, T, out.data_ptr(),
+                                                      runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
+    return out
+
+
+class _Rows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, planes, coordinates, tail, mx, mn, radii, N, K, repeat):
+        p, c = planes.detach().contiguous(), coordinates.detach().contiguous()
+        out = _rows_forward(p, c, tail.detach().contiguous(), mx, mn, radii, N, K, repeat)
+        ctx.save_for_backward(p, c, mx, mn)
+        ctx.args = (radii, N, K, repeat, tail.shape[1])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        p, c, mx, mn = ctx.saved_tensors
+        radii, N, K, repeat, T = ctx.args
+        dev = p.device
+        C, H, W = p.shape[1:]
+        g = grad.to(torch.float32).contiguous()      # the whole (N, K 3 C + T) gradient as it arrives: the kernels read its feature columns in place
+        row = K * 3 * C
+        gp = gc = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gp = torch.empty_like(p)
+            gc = torch.empty_like(c) if ctx.needs_input_grad[1] else None
+            if N == 0:
+                gp.zero_()
+            else:
+                _lib.check(_lib.lib().gsge_plane_rows_backward(runtime.context(dev), g.data_ptr(), p.data_ptr(), c.data_ptr(), mx.data_ptr(), mn.data_ptr(),
+                                                               float(radii), N, K, int(repeat), C, H, W, T, gp.data_ptr(), ptr(gc),
+                                                               runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
+        gt = g[:, row:] if ctx.needs_input_grad[2] else None      # the tail's gradient: a column view, no kernel
+        return (gp if ctx.needs_input_grad[0] else None), gc, gt, None, None, None, None, None, None
+
+
+def triplane_rows(planes, coordinates, tail, max_coords, min_coords, radii, repeat=None):
+    """The context rows (gsge_plane_rows_forward): the (N, K * 3 * C + T) tensor whose first K * 3 * C columns are `triplane_sample`'s, bit for
+    bit, and whose last T are `tail` (N, T), T in [0, 16] -- torch.cat([triplane_sample(...), tail], dim=1) written once (TC-GS: the anchor,
+    T = 3, the input of mlp_triplane).  Coordinates as `triplane_sample` takes them, (N, K, 3) or (N, 3) with `repeat=K`; K <= 64 in both
+    forms.  Differentiable in planes, coordinates and tail: the backward reads the upstream gradient in place (no contiguous copy of the
+    feature columns) and the tail's gradient is the column view grad[:, K * 3 * C:].  When tail and coordinates are the same tensor (the
+    repeat form with the anchor) autograd adds the two."""
+    who = "triplane_rows"
+    N, K = _check(planes, coordinates, max_coords, min_coords, radii, repeat, who)
+    _f32_cuda(tail, "tail", who)
+    if tail.device != planes.device:
+        raise ValueError(f"{who}: tail on {tail.device}, planes on {planes.device}")
+    if tail.dim() != 2 or tail.shape[0] != N or tail.shape[1] > MAX_TAIL:
+        raise ValueError(f"{who}: tail must be ({N}, T) with T <= {MAX_TAIL}, got {tuple(tail.shape)}")
+    if K > MAX_REPEAT:
+        raise ValueError(f"{who}: K = {K} above {MAX_REPEAT} (a workgroup owns whole rows)")
+    mx, mn = max_coords.detach().reshape(3).contiguous(), min_coords.detach().reshape(3).contiguous()
+    if torch.is_grad_enabled() and (planes.requires_grad or coordinates.requires_grad or tail.requires_grad):
+        return _Rows.apply(planes, coordinates, tail, mx, mn, float(radii), N, K, repeat is not None)
+    return _rows_forward(planes.detach().contiguous(), coordinates.detach().contiguous(), tail.detach().contiguous(), mx, mn, float(radii), N, K,
+                         repeat is not None)
+
+
 def sample_from_planes(plane_axes, plane_features, coordinates, max_coords, min_coords, mode='bilinear', padding_mode='zeros', box_warp=1, radii=None):
     """utils/triplane.py's sample_from_planes: the (N, K, 3, C) features of coordinates (N, K, 3)."""
     if mode != 'bilinear' or padding_mode != 'zeros':
@@ -178,7 +249,14 @@ class Triplane(nn.Module):
         return self.compressed_plane
 
     def forward(self, sample_coordinates, max_coords, min_coords, is_training=0, step=0, repeat=None):
-        out = self.sample(self.planes, sample_coordinates, max_coords, min_coords, repeat=repeat)
+        return self._with_autoencoder(self.sample(self.planes, sample_coordinates, max_coords, min_coords, repeat=repeat), is_training, step)
+
+    def context_rows(self, sample_coordinates, tail, max_coords, min_coords, is_training=0, step=0, repeat=None):
+        """`forward` with the context rows [features | tail] (triplane_rows) in place of the features: the same return convention."""
+        rows = triplane_rows(self.planes, sample_coordinates, tail, max_coords, min_coords, 0.5 * self.radii, repeat=repeat)
+        return self._with_autoencoder(rows, is_training, step)
+
+    def _with_autoencoder(self, out, is_training, step):
         if is_training and step > 15000:
             pairs = [self.autoencoder(self.planes[i].unsqueeze(0)) for i in range(3)]
             compressed = torch.stack([c for c, _ in pairs], dim=0)        # (3, 8, H / 8, W / 8)

@@ -539,6 +539,18 @@ GPCC_API int gsnn_noise_forward_b(gpcc_ctx *ctx, int64_t n, int nattr, const flo
 GPCC_API int gsnn_noise_backward_b(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *g, const float *const *u, const int64_t *widths,
                                    const double *q0, const float *adj, int64_t adj_stride, const int *adj_cols, double base, const float *grad_q,
                                    float *d_adj, void *stream);
+/* The evaluation side: STE_multistep's forward (utils/encodings.py:55-67) on the same nattr <= 3 row-aligned attributes in ONE launch.
+ * x, widths, q0, adj, adj_stride, adj_cols, base, y, q_out as above; means: nattr float32 DEVICE scalars.  Per element, in float32, IEEE
+ * division, no contraction, rintf (half to even, as torch.round):
+ *   Q = q0_j * (base + tanhf(adj[r, j]));  v = use_clamp ? min(max(x, m_j - 15000 Q), m_j + 15000 Q) : x (a NaN x stays NaN);  y = rintf(v / Q) * Q
+ * Q = 0 gives non-finite y, as the torch expression does.  No backward: every caller detaches.
+ * gsnn_mean: means[j] = (float)(sum of x[j][0 .. counts[j]) / counts[j]) for nattr <= 3 tensors, the sum in double and in a fixed order
+ * (256 workgroups per tensor, thread t of workgroup b adds elements b 256 + t, + 65536, ... ascending; a fixed tree over the 256 threads,
+ * then over the 256 workgroups): bitwise reproducible, two launches.  partials: nattr * 256 doubles of device scratch. */
+GPCC_API int gsnn_quantise(gpcc_ctx *ctx, int64_t n, int nattr, const float *const *x, const int64_t *widths, const double *q0, const float *adj,
+                           int64_t adj_stride, const int *adj_cols, double base, const float *means, int use_clamp, float *const *y, float *q_out,
+                           void *stream);
+GPCC_API int gsnn_mean(gpcc_ctx *ctx, int nattr, const float *const *x, const int64_t *counts, double *partials, float *means, void *stream);
 
 /* ================= Gaussian splat rasteriser, forward (a20) =================
  * diff_gaussian_rasterization (Scaffold-GS fork; zip missing from the reference tree).  Mirrors the C++ API the
@@ -820,6 +832,19 @@ GPCC_API int gsge_plane_forward(gpcc_ctx *ctx, const float *planes, const float 
 GPCC_API int gsge_plane_backward(gpcc_ctx *ctx, const float *grad_out, const float *planes, const float *coordinates, const float *max_coords,
                                  const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
                                  float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+/* The context rows: the sampler with an output row of k * 3 * C + tail_width floats whose last tail_width columns are a copy of row n of
+ * `tail` (n, tail_width) float32 contiguous -- TC-GS's torch.cat([feat_context, anchor], dim=1) (gaussian_renderer/__init__.py:66), the
+ * (N, 603) input of mlp_triplane, written once.  tail_width in [0, 16] (0: tail may be NULL; the two calls above are these with 0 and give
+ * the same bits); with a tail k <= 64 in both coordinate forms.  The feature columns are the sampler's, bit for bit; the tail is copied.
+ * gsge_plane_rows_backward reads grad_out (n, k * 3 * C + tail_width) in place, rows that many floats apart: no contiguous copy of the
+ * feature columns is needed.  The tail's gradient is the column view grad_out[:, k * 3 * C:], which the caller takes itself. */
+GPCC_API int gsge_plane_rows_forward(gpcc_ctx *ctx, const float *planes, const float *coordinates, const float *max_coords, const float *min_coords,
+                                     double radii, int64_t n, int k, int repeat, int channels, int height, int width, const float *tail,
+                                     int tail_width, float *out, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+GPCC_API int gsge_plane_rows_backward(gpcc_ctx *ctx, const float *grad_out, const float *planes, const float *coordinates, const float *max_coords,
+                                      const float *min_coords, double radii, int64_t n, int k, int repeat, int channels, int height, int width,
+                                      int tail_width, float *grad_planes, float *grad_coordinates, gsr_alloc_fn alloc, void *alloc_user,
+                                      void *stream);
 
 /* ================= Multi-scale tri-plane features (CAT-3DGS/scene/triplane.py: TriPlaneField.forward / get_density :246-342,
  * interpolate_ms_features :89-146, grid_sample_wrapper :40-65) =================
