@@ -67,6 +67,7 @@ EXPORTS = [
     "gpcc_knn", "gpcc_scatter_max", "gpcc_grow_voxels",
     "gpcc_densify_stats", "gpcc_densify_front", "gpcc_densify_finish", "gpcc_compact_rows", "gpcc_expand_rows",
     "gsr_ssim_forward", "gsr_ssim_backward",
+    "gsr_wavelet_l1_forward", "gsr_wavelet_l1_backward", "gsr_haar_forward", "gsr_haar_inverse",
     "gsac_rate_forward", "gsac_rate_backward", "gsac_chain_rate_forward", "gsac_chain_rate_backward",
     "gsge_plane_forward", "gsge_plane_backward", "gsge_plane_rows_forward", "gsge_plane_rows_backward",
     "gsge_msplane_forward", "gsge_msplane_backward",
@@ -191,6 +192,10 @@ def lib():
     L.gsnn_mean.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64), vp, vp, vp]
     L.gsr_ssim_forward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, fp, i32, vp, vp, vp, C.c_double, vp, i32, GSR_ALLOC, vp, vp]
     L.gsr_ssim_backward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, fp, i32, vp, i32, vp, f32, vp, f32, vp, vp, vp]
+    L.gsr_wavelet_l1_forward.argtypes = [vp, vp, vp, i64, i64, i64, dp, vp, vp, GSR_ALLOC, vp, vp]
+    L.gsr_wavelet_l1_backward.argtypes = [vp, vp, vp, i64, i64, i64, dp, vp, vp, vp, vp]
+    L.gsr_haar_forward.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+    L.gsr_haar_inverse.argtypes = [vp, vp, vp, i64, i64, i64, vp, i64, i64, vp]
     pp, ip, f64 = C.POINTER(vp), C.POINTER(i32), C.c_double
     L.gsac_rate_forward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp]
     L.gsac_rate_backward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp, pp, pp, pp, vp, GSR_ALLOC, vp, vp]

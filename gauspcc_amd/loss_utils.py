@@ -7,6 +7,12 @@ the same file in HAC, HAC++, TC-GS and CAT-3DGS:
 differentiable in whichever of its two images requires grad.  `photometric_loss` is train.py's `(1 - lambda_dssim) * Ll1 + lambda_dssim *
 (1 - ssim)` in the same two launches forward and one backward.  Results are bitwise reproducible: no float atomics.
 
+TC-GS's loss_utils.py also has `wavelet_loss` (built on pytorch_wavelets' DWTForward); its swap is
+
+    from utils.loss_utils import l1_loss, ssim, wavelet_loss   ->   from gauspcc_amd.loss_utils import l1_loss, ssim, wavelet_loss
+
+and `tcgs_photometric_loss` is that train.py's loss with the wavelet term (gsr_wavelet_l1_forward / gsr_wavelet_l1_backward).
+
 Differences from the reference: `window_size` must be odd and at most 31 (an even window gives the reference an (H+1) x (W+1) map; ValueError
 here), inputs must be float32 CUDA tensors of the same shape (TypeError for another dtype, RuntimeError for CPU tensors: there is no CPU path).
 """
@@ -157,3 +163,70 @@ def photometric_loss(image, gt, lambda_dssim=0.2):
         return _Photometric.apply(image, gt, float(lambda_dssim))
     s, l1, loss, _ = _forward(_bchw(image), _bchw(gt), 11, True, 0, lam=float(lambda_dssim))
     return loss[0], l1[0], s[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# TC-GS's wavelet term (TC-GS/utils/loss_utils.py:66-83): the weighted L1 of the bands of a two-level Haar DWT (zero mode), one launch
+# over 4 x 4 pixel blocks forward and one backward (gsr_wavelet_l1_forward / gsr_wavelet_l1_backward, csrc/wavelet.hip)
+
+def wavelet_weights(step=0):
+    """The seven band weights of wavelet_loss at `step`, in the order LL2, level-1 bands 0..2, level-2 bands 0..2 (host floats, formed
+    as the reference forms them)."""
+    lmbda1, lmbda2 = 1.0 - step / 30000, step / 30000
+    if step > 25000:
+        return [0.0, 0.4 * lmbda1, 0.3 * lmbda1, 0.3 * lmbda1, 0.4 * lmbda2, 0.3 * lmbda2, 0.3 * lmbda2]
+    return [lmbda1] + [0.2 * lmbda2] * 6
+
+
+def _wavelet_forward(x, y, weights):
+    """gsr_wavelet_l1_forward on contiguous (C, H, W) images: (loss (1,), the seven band means (7,))."""
+    C, H, W = x.shape
+    dev = x.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    bands = torch.empty(7, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().gsr_wavelet_l1_forward(runtime.context(dev), x.data_ptr(), y.data_ptr(), C, H, W, (ctypes.c_double * 7)(*weights),
+                                                 out.data_ptr(), bands.data_ptr(), runtime.Workspace(dev).fn(), None, runtime.stream_ptr(dev)))
+    return out, bands
+
+
+class _Wavelet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img1, img2, weights):
+        x, y = img1.detach().contiguous(), img2.detach().contiguous()
+        ctx.save_for_backward(x, y)
+        ctx.weights = weights
+        return _wavelet_forward(x, y, weights)[0][0]
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, y = ctx.saved_tensors
+        C, H, W = x.shape
+        dev = x.device
+        g = _grad_value(grad, 1, dev)
+        d1 = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        d2 = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().gsr_wavelet_l1_backward(runtime.context(dev), x.data_ptr(), y.data_ptr(), C, H, W, (ctypes.c_double * 7)(*ctx.weights),
+                                                      g.data_ptr(), ptr(d1), ptr(d2), runtime.stream_ptr(dev)))
+        return d1, d2, None
+
+
+def wavelet_loss(img1, img2, step=0):
+    """TC-GS's loss_utils.wavelet_loss: (C, H, W) float32 CUDA images to a 0-d tensor, differentiable in img1 and img2.  The reference
+    takes DWTForward(J=2, mode='zero', wave='haar') from pytorch_wavelets; here both levels of both images and the seven L1 means are one
+    launch.  With step <= 25000 the loss is (1 - step/30000) L1(LL2) + 0.2 step/30000 (sum of the six detail bands' L1), beyond that
+    0.4 / 0.3 / 0.3 of the level-1 bands times (1 - step/30000) plus the same of the level-2 bands times step/30000."""
+    _check(img1, img2, 11, "wavelet_loss")
+    if img1.dim() != 3:
+        raise ValueError(f"wavelet_loss: images must be (C, H, W), got {tuple(img1.shape)}")
+    weights = wavelet_weights(step)
+    if torch.is_grad_enabled() and (img1.requires_grad or img2.requires_grad):
+        return _Wavelet.apply(img1, img2, weights)
+    return _wavelet_forward(img1.detach().contiguous(), img2.detach().contiguous(), weights)[0][0]
+
+
+def tcgs_photometric_loss(image, gt, lambda_dssim=0.2, wavelet=0.02, step=0):
+    """TC-GS's train.py:180-183 without scaling_reg: (loss, l1, ssim_value, wavelet_value) with loss = photometric_loss(image, gt,
+    lambda_dssim)[0] + wavelet * wavelet_loss(image, gt, step); l1, ssim_value and wavelet_value are detached 0-d tensors."""
+    loss, l1, s = photometric_loss(image, gt, lambda_dssim)
+    w = wavelet_loss(image, gt, step)
+    return loss + wavelet * w, l1, s, w.detach()

@@ -749,6 +749,32 @@ GPCC_API int gsr_ssim_backward(gpcc_ctx *ctx, const float *img1, const float *im
                                int window_size, const float *taps, int size_average, const float *maps, int nmaps, const float *grad_ssim, float ssim_scale,
                                const float *grad_l1, float l1_scale, float *grad_img1, float *grad_img2, void *stream);
 
+/* ================= Wavelet loss (training step, TC-GS/utils/loss_utils.py:66-83: wavelet_loss; its DWTForward / DWTInverse of
+ * pytorch_wavelets with wave 'haar', mode 'zero') =================
+ * One level of the transform, float32 with every product rounded on its own, s = (float)0.7071067811865476, a plane read as zero outside:
+ * on the quad a b / c d = x[2r..2r+1][2k..2k+1] the row pass gives lo0 = a s + b s, hi0 = a s - b s, lo1 = c s + d s, hi1 = c s - d s and
+ * the column pass LL[r][k] = lo0 s + lo1 s, band0 = lo0 s - lo1 s (low along width, high along height), band1 = hi0 s + hi1 s, band2 =
+ * hi0 s - hi1 s; all bands are ceil(H / 2) x ceil(W / 2).  The next level transforms LL.
+ * gsr_wavelet_l1_forward: img1, img2 (planes, height, width) float32 device, contiguous.  Two levels of both images in one pass over
+ * 4 x 4 pixel blocks; seven band means of |coefficient of img1 - coefficient of img2| in the order LL2, level-1 bands 0..2, level-2
+ * bands 0..2 (level 1: planes h1 w1 values each, h1 = ceil(height / 2); LL2 and level 2: planes h2 w2, h2 = ceil(h1 / 2)); bands_out (7
+ * values, may be NULL) receives them, loss_out (1 value) = (float) sum_b weights[b] mean_b over the bands with weights[b] != 0 (weights: 7
+ * HOST doubles).  Sums are per-workgroup doubles added in a fixed order (no atomics): bitwise reproducible.  alloc is called once for 56
+ * bytes per 256 blocks, not needed once the kernels have run.
+ * gsr_wavelet_l1_backward: the same images and weights, grad_loss one device value; recomputes the coefficients (nothing is saved) and
+ * writes d loss / d img1 to grad_img1 and its negative, bit for bit, to grad_img2 (either may be NULL); sign(0) = 0.
+ * gsr_haar_forward: x (planes, height, width) to ll_out (planes, h, w) and high_out (planes, 3, h, w), h = ceil(height / 2), w alike.
+ * gsr_haar_inverse: ll (planes, h, w) and high (planes, 3, h, w; NULL = zeros) to out (planes, out_height, out_width), out_height in
+ * {2h - 1, 2h} and out_width alike (the padded row / column is cropped).  Haar is orthonormal: each of the two is the other's adjoint,
+ * so each is the other's backward.  All four calls are enqueued on `stream` without synchronising. */
+GPCC_API int gsr_wavelet_l1_forward(gpcc_ctx *ctx, const float *img1, const float *img2, int64_t planes, int64_t height, int64_t width,
+                                    const double *weights, float *loss_out, float *bands_out, gsr_alloc_fn alloc, void *alloc_user, void *stream);
+GPCC_API int gsr_wavelet_l1_backward(gpcc_ctx *ctx, const float *img1, const float *img2, int64_t planes, int64_t height, int64_t width,
+                                     const double *weights, const float *grad_loss, float *grad_img1, float *grad_img2, void *stream);
+GPCC_API int gsr_haar_forward(gpcc_ctx *ctx, const float *x, int64_t planes, int64_t height, int64_t width, float *ll_out, float *high_out, void *stream);
+GPCC_API int gsr_haar_inverse(gpcc_ctx *ctx, const float *ll, const float *high, int64_t planes, int64_t h, int64_t w, float *out, int64_t out_height,
+                              int64_t out_width, void *stream);
+
 /* ================= Entropy rate models (training step, HAC-plus/utils/entropy_models.py: Entropy_gaussian, Entropy_gaussian_mix_prob_2 / _3,
  * Low_bound; the same Gaussian model as gsac_calculate_cdf) =================
  * x (n, c) float32 device, contiguous; k in {1, 2, 3} mixture components.  mean[i], scale[i] (and prob[i] for k > 1) are device pointers,
