@@ -68,6 +68,7 @@ EXPORTS = [
     "gpcc_densify_stats", "gpcc_densify_front", "gpcc_densify_finish", "gpcc_compact_rows", "gpcc_expand_rows",
     "gsr_ssim_forward", "gsr_ssim_backward",
     "gsr_wavelet_l1_forward", "gsr_wavelet_l1_backward", "gsr_haar_forward", "gsr_haar_inverse",
+    "gsr_sh_forward", "gsr_sh_backward",
     "gsac_rate_forward", "gsac_rate_backward", "gsac_chain_rate_forward", "gsac_chain_rate_backward",
     "gsge_plane_forward", "gsge_plane_backward", "gsge_plane_rows_forward", "gsge_plane_rows_backward",
     "gsge_msplane_forward", "gsge_msplane_backward",
@@ -196,6 +197,8 @@ def lib():
     L.gsr_wavelet_l1_backward.argtypes = [vp, vp, vp, i64, i64, i64, dp, vp, vp, vp, vp]
     L.gsr_haar_forward.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
     L.gsr_haar_inverse.argtypes = [vp, vp, vp, i64, i64, i64, vp, i64, i64, vp]
+    L.gsr_sh_forward.argtypes = [vp, i32, i32, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.gsr_sh_backward.argtypes = [vp, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     pp, ip, f64 = C.POINTER(vp), C.POINTER(i32), C.c_double
     L.gsac_rate_forward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp]
     L.gsac_rate_backward.argtypes = [vp, i32, i64, i64, vp, vp, pp, pp, pp, ip, vp, i32, f64, f64, i32, vp, vp, pp, pp, pp, vp, GSR_ALLOC, vp, vp]

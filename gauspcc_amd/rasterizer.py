@@ -7,8 +7,11 @@ Differentiable like the module it stands in for: with grad mode on and any of me
 colors_precomp, scales, rotations, cov3D_precomp requiring grad, the call goes through _RasterizeGaussians
 (gsr_forward_train + gsr_backward: the same image, and gradients for those seven inputs; means2D's gradient is
 dL/d(NDC x, y) of the projected centre, z column 0, what training_statis reads).  Otherwise -- RD evaluation,
-torch.no_grad() -- the forward-only gsr_forward runs, as before.  No background gradient, no double backward;
-colours must be precomputed (`shs=None` at every call site of the reference).
+torch.no_grad() -- the forward-only gsr_forward runs, as before.  No background gradient, no double backward.
+
+Colours come as `colors_precomp` (P, 3) or as `shs` (P, M, 3) spherical-harmonic coefficients with M >= (sh_degree + 1)^2, sh_degree 0..4:
+sh_utils.sh_colors turns those into colours from means3D and raster_settings.campos (gsr_sh_forward; gsr_sh_backward under autograd, which
+then adds the colour pass's means3D gradient to the rasteriser's) and the frame goes on exactly as with colors_precomp.
 """
 import ctypes as C
 from typing import NamedTuple
@@ -17,7 +20,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib, runtime
+from . import _lib, runtime, sh_utils
 from .runtime import ptr
 
 
@@ -43,8 +46,6 @@ def _f32(t):
 def _check_args(shs, colors_precomp, scales, rotations, cov3D_precomp):
     if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
         raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-    if shs is not None:
-        raise NotImplementedError("gauspcc_amd.rasterizer: SH evaluation is not on the reference's path (shs=None everywhere); pass colors_precomp")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
         raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
 
@@ -129,6 +130,8 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
         _check_args(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        if shs is not None:
+            colors_precomp = sh_utils.sh_colors(shs, means3D, self.raster_settings.campos, self.raster_settings.sh_degree)
         diff = (means3D, means2D, opacities, colors_precomp, scales, rotations, cov3D_precomp)
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in diff):
             info = {}

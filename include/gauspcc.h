@@ -775,6 +775,45 @@ GPCC_API int gsr_haar_forward(gpcc_ctx *ctx, const float *x, int64_t planes, int
 GPCC_API int gsr_haar_inverse(gpcc_ctx *ctx, const float *ll, const float *high, int64_t planes, int64_t h, int64_t w, float *out, int64_t out_height,
                               int64_t out_width, void *stream);
 
+/* ================= Spherical-harmonic colours (the rasteriser's shs= argument: diff_gaussian_rasterization's computeColorFromSH, forward
+ * and backward; utils/sh_utils.py: eval_sh) =================
+ * sh: P rows of coefficients, float32 device; entry (k, c) of row i is sh[i row_stride + k coef_stride + c chan_stride] (strides in
+ * floats): (P, M, 3) contiguous is (3, 1, 3 M), eval_sh's (P, 3, M) is (1, M, 3 M); M may exceed the K = (degree + 1)^2 active ones, degree
+ * 0..4.  Exactly one of means3D and dirs (each (P, 3) contiguous) is given:
+ *   means3D with campos (3 floats on the DEVICE, read there): v = mean - campos, l2 = (v_x v_x + v_y v_y) + v_z v_z, len = sqrt(l2),
+ *     d = v / len, or d = 0 when l2 == 0 (a Gaussian at the camera centre keeps its DC term); colour_c = max(value_c + 0.5, 0) and
+ *     clamped (P, 3) uint8 = (value_c + 0.5 < 0): equality is not clamped;
+ *   dirs: d as given, not renormalised; colour_c = value_c, clamped is not touched (may be NULL).
+ * Arithmetic contract: float32, every step one IEEE operation (no fused multiply-add; sqrt and division correctly rounded), in this order.
+ * With x, y, z = d: xx = x x, yy, zz, xy = x y, yz = y z, xz = x z, xmy = xx - yy, p = 3 xx - yy, q = (4 zz - xx) - yy,
+ * r = (2 zz - 3 xx) - 3 yy, s = xx - 3 yy, xyz = xy z, u = 7 zz - 1, v = 7 zz - 3; each basis value is one constant (a double rounded to
+ * float32, sign included) times one polynomial:
+ *   b0 = C0;  b1 = -C1 y, b2 = C1 z, b3 = -C1 x;
+ *   b4 = C2a xy, b5 = -C2a yz, b6 = C2c ((2 zz - xx) - yy), b7 = -C2a xz, b8 = C2e xmy;
+ *   b9 = -C3a (y p), b10 = C3b xyz, b11 = -C3c (y q), b12 = C3d (z r), b13 = -C3c (x q), b14 = C3f (z xmy), b15 = -C3a (x s);
+ *   b16 = C4a (xy xmy), b17 = -C4b (yz p), b18 = C4c (xy u), b19 = -C4d (yz v), b20 = C4e (zz (35 zz - 30) + 3), b21 = -C4d (xz v),
+ *   b22 = C4g (xmy u), b23 = -C4b (xz s), b24 = C4i (xx s - yy p)           (degree 4 is the r = 1 form, as eval_sh's)
+ *   C0 = 1/2 sqrt(1/pi), C1 = sqrt(3/(4 pi)), C2a = 1/2 sqrt(15/pi), C2c = 1/4 sqrt(5/pi), C2e = 1/4 sqrt(15/pi), C3a = 1/4 sqrt(35/(2 pi)),
+ *   C3b = 1/2 sqrt(105/pi), C3c = 1/4 sqrt(21/(2 pi)), C3d = 1/4 sqrt(7/pi), C3f = 1/4 sqrt(105/pi), C4a = 3/4 sqrt(35/pi),
+ *   C4b = 3/4 sqrt(35/(2 pi)), C4c = 3/4 sqrt(5/pi), C4d = 3/4 sqrt(5/(2 pi)), C4e = 3/16 sqrt(1/pi), C4g = 3/8 sqrt(5/pi), C4i = 3/16 sqrt(35/pi).
+ *   value_c = (..((b0 sh[0][c]) + b1 sh[1][c]) + ...) + b_{K-1} sh[K-1][c].
+ * gsr_sh_backward: the same inputs, M, clamped as the forward wrote it and dL_dcolors (P, 3).  g_c = 0 where clamped, dL_dcolors_c
+ * otherwise.  dL_dsh (entry (k, c) of row i at i grad_row_stride + k grad_coef_stride + c grad_chan_stride; every one of the P M 3
+ * entries is written) = b_k g_c for k < K, and exactly 0 for k >= K and for clamped channels.  dL/dd_a = the sum over k = 1 .. K-1,
+ * ascending and starting with its first term, of (d b_k / d d_a) t_k, t_k = (sh[k][0] g_0 + sh[k][1] g_1) + sh[k][2] g_2, leaving out the
+ * terms whose derivative is identically zero; the derivatives are again constant times polynomial, spelled out in csrc/sh.hip
+ * (sh_dir_grad) and restated in tests/sh_ref.py.  dirs: dL_ddirs (P, 3) = dL/dd.  means3D: dot = (dL/dd_x d_x + dL/dd_y d_y) + dL/dd_z d_z,
+ * dL_dmeans3D_a = (dL/dd_a - d_a dot) / len, and exactly 0 when l2 == 0.  Degree 0: both are exactly 0.  No gradient for campos.  dL_dsh, dL_dmeans3D / dL_ddirs may each be NULL (not
+ * computed).  NaN in a Gaussian's inputs gives NaN in that Gaussian's outputs only.  Each output element has one owner: no atomics, no
+ * reductions, bitwise reproducible; the memory path taken (rows staged through LDS or read directly, by stride and alignment) changes no
+ * value.  Both calls are enqueued on `stream` without synchronising; P = 0 is a no-op. */
+GPCC_API int gsr_sh_forward(gpcc_ctx *ctx, int P, int degree, const float *sh, int64_t coef_stride, int64_t chan_stride, int64_t row_stride,
+                            const float *means3D, const float *campos, const float *dirs, float *colors, uint8_t *clamped, void *stream);
+GPCC_API int gsr_sh_backward(gpcc_ctx *ctx, int P, int degree, int M, const float *sh, int64_t coef_stride, int64_t chan_stride, int64_t row_stride,
+                             const float *means3D, const float *campos, const float *dirs, const uint8_t *clamped, const float *dL_dcolors,
+                             float *dL_dsh, int64_t grad_coef_stride, int64_t grad_chan_stride, int64_t grad_row_stride, float *dL_dmeans3D,
+                             float *dL_ddirs, void *stream);
+
 /* ================= Entropy rate models (training step, HAC-plus/utils/entropy_models.py: Entropy_gaussian, Entropy_gaussian_mix_prob_2 / _3,
  * Low_bound; the same Gaussian model as gsac_calculate_cdf) =================
  * x (n, c) float32 device, contiguous; k in {1, 2, 3} mixture components.  mean[i], scale[i] (and prob[i] for k > 1) are device pointers,
