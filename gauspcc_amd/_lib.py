@@ -66,6 +66,7 @@ EXPORTS = [
     "gpcc_train_frame", "gpcc_train_frame_nodes", "gpcc_train_weights", "gpcc_train_conv", "gpcc_train_wgrad",
     "gpcc_knn", "gpcc_scatter_max", "gpcc_grow_voxels",
     "gpcc_densify_stats", "gpcc_densify_front", "gpcc_densify_finish", "gpcc_compact_rows", "gpcc_expand_rows",
+    "gsr_forward_aux", "gsr_forward_train_aux", "gsr_backward_aux",
     "gsr_ssim_forward", "gsr_ssim_backward",
     "gsr_wavelet_l1_forward", "gsr_wavelet_l1_backward", "gsr_haar_forward", "gsr_haar_inverse",
     "gsr_sh_forward", "gsr_sh_backward",
@@ -166,6 +167,12 @@ def lib():
                                     C.POINTER(C.c_uint64), C.POINTER(i64), vp]
     L.gsr_backward.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, f32, f32, vp, vp, GSR_ALLOC, vp,
                                vp, vp, vp, vp, vp, vp, vp, vp]
+    # the _aux forms: out_invdepth, out_alpha after radii; dL_dinvdepth, dL_dalpha after dL_dout
+    L.gsr_forward_aux.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, C.POINTER(i64), vp]
+    L.gsr_forward_train_aux.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, GSR_ALLOC, vp,
+                                        C.POINTER(C.c_uint64), C.POINTER(i64), vp]
+    L.gsr_backward_aux.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, GSR_ALLOC, vp,
+                                   vp, vp, vp, vp, vp, vp, vp, vp]
     L.gsnn_generate.argtypes = [vp, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), vp]
     L.gsnn_forward_train.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, GSR_ALLOC, vp, C.POINTER(vp),
                                      C.POINTER(i64), vp]

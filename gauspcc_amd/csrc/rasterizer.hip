@@ -3,7 +3,8 @@
 // SURVEY.md App. E; call contract: HAC/gaussian_renderer/__init__.py:199-225, 268-303 and
 // TC-GS/SIBR_viewers/src/projects/gaussianviewer/renderer/GaussianView.cpp:535-553, 660-688).
 // The inference forward (RD evaluation: render -> PSNR) is gsr_forward; training runs gsr_forward_train + gsr_backward (k_render<true>,
-// k_render_backward, k_preprocess_backward: below the forward's kernels).
+// k_render_backward, k_preprocess_backward: below the forward's kernels).  The _aux forms of the three add the frame's inverse-depth and
+// accumulated-opacity maps and their gradients (the AUX instantiations); with no map asked for they are the three, kernel for kernel.
 //
 // gfx950 mapping:
 //   k_preprocess     one lane per Gaussian, coalesced SoA outputs (HBM-bound); counts the tiles the splat can reach (tile_touches: exact tile culling)
@@ -292,7 +293,9 @@ __global__ __launch_bounds__(TB) void k_tile_ranges(int L, const uint64_t *__res
 // Round 4 measured the one-pixel-per-lane form at 36 % of the VALU peak (three LDS waits, a libm exponential and three branches for ~15
 // useful VALU instructions per Gaussian and pixel: profiles/r04_render_counters.txt).
 constexpr int RT = 128;
-__device__ __forceinline__ void blend_one(float power, float op, float r, float g, float b, bool &done, float &T, float &C0, float &C1, float &C2)
+// AUX: one more blended channel, the Gaussian's inverse view depth d into D (the invdepth map; alpha comes from the final T)
+template <bool AUX>
+__device__ __forceinline__ void blend_one(float power, float op, float r, float g, float b, bool &done, float &T, float &C0, float &C1, float &C2, float d, float &D)
 {
     const float e = __builtin_amdgcn_exp2f(power * 1.44269504088896341f);
     const float alpha = fminf(0.99f, op * e);
@@ -303,11 +306,13 @@ __device__ __forceinline__ void blend_one(float power, float op, float r, float 
     const bool upd = ok && !sat;
     const float w = upd ? alpha * T : 0.0f;
     C0 += r * w; C1 += g * w; C2 += b * w;
+    if constexpr (AUX) D += d * w;
     T = upd ? tt : T;
 }
 // the same blend, plus the list position after the last Gaussian blended into the pixel (the training forward)
+template <bool AUX>
 __device__ __forceinline__ void blend_one_rec(float power, float op, float r, float g, float b, bool &done, float &T, float &C0, float &C1, float &C2,
-                                              uint32_t kend, uint32_t &e)
+                                              uint32_t kend, uint32_t &e, float d, float &D)
 {
     const float e2 = __builtin_amdgcn_exp2f(power * 1.44269504088896341f);
     const float alpha = fminf(0.99f, op * e2);
@@ -318,6 +323,7 @@ __device__ __forceinline__ void blend_one_rec(float power, float op, float r, fl
     const bool upd = ok && !sat;
     const float w = upd ? alpha * T : 0.0f;
     C0 += r * w; C1 += g * w; C2 += b * w;
+    if constexpr (AUX) D += d * w;
     T = upd ? tt : T;
     e = upd ? kend : e;
 }
@@ -336,15 +342,19 @@ __global__ __launch_bounds__(TB) void k_tile_order_keys(const uint2 *__restrict_
 // TRAIN (the training forward, gsr_forward_train): point_list holds the pair's SLOT (its position in the duplicate pass's output, see
 // k_render_backward) and the Gaussian is gathered through slot_ids; every in-image pixel leaves its final T and the list position after the last
 // Gaussian it blended (0: none).  The blend is the same code: the image is bit-identical to the inference path's.
-template <bool TRAIN>
+// AUX (gsr_forward_aux / gsr_forward_train_aux): one more float per list entry through LDS, 1 / depth, and one more accumulator per pixel:
+// out_invdepth = sum_i w_i / tz_i (no background term, not normalised) and out_alpha = 1 - T_final, each (H, W), either may be null.
+template <bool TRAIN, bool AUX>
 __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ point_list, int W, int H, int gx,
                                             const float2 *__restrict__ xy, const float *__restrict__ colors, const float4 *__restrict__ conic_op,
                                             const float *__restrict__ bg, float *__restrict__ out, const uint32_t *__restrict__ slot_ids, float *__restrict__ final_T,
-                                            uint32_t *__restrict__ n_end)
+                                            uint32_t *__restrict__ n_end, const float *__restrict__ depth, float *__restrict__ out_invdepth,
+                                            float *__restrict__ out_alpha)
 {
     __shared__ float4 s_a[RT];   // x, y, conic.x, conic.y
     __shared__ float4 s_b[RT];   // conic.z, opacity, r, g
     __shared__ float2 s_c[RT];   // b, skip threshold: a Gaussian contributes to a pixel only if thr <= power <= 0
+    __shared__ float s_d[AUX ? RT : 1];   // 1 / depth
     const int tile = (int)tile_order[blockIdx.x];
     const int tbx = tile % gx, tby = tile / gx;
     const int pxi = tbx * BX + (threadIdx.x & 15), py0 = tby * BY + (threadIdx.x >> 4), py1 = py0 + 8;
@@ -355,6 +365,7 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
     float T0 = 1.0f, A0 = 0.f, A1 = 0.f, A2 = 0.f;
     float T1 = 1.0f, B0 = 0.f, B1 = 0.f, B2 = 0.f;
     uint32_t e0 = 0, e1 = 0;
+    float D0 = 0.f, D1 = 0.f;
     for (uint32_t b0 = range.x; b0 < range.y; b0 += RT) {
         if (__syncthreads_count(done0 && done1) == RT) break;
         const uint32_t k = b0 + threadIdx.x;
@@ -369,9 +380,11 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
             // alpha = op * exp(power) >= 1 / 255  <=>  power >= -ln(255 op); a margin keeps the borderline pixels on the exact test below
             // (a NaN opacity blends as alpha 0.99 in the reference -- fminf(0.99, NaN) -- so it must pass the pre-test: threshold -inf)
             s_c[threadIdx.x] = make_float2(colors[3 * id + 2], co.w > 0.0f ? -__logf(255.0f * co.w) - 1e-3f : (co.w != co.w ? -__builtin_inff() : __builtin_inff()));
+            if constexpr (AUX) s_d[threadIdx.x] = 1.0f / depth[id];
         } else {
             // behind the list: a Gaussian of opacity 0 (alpha 0 < 1 / 255: never blended), so that the loop below runs in pairs
             s_a[threadIdx.x] = make_float4(0.f, 0.f, 1.f, 0.f); s_b[threadIdx.x] = make_float4(1.f, 0.f, 0.f, 0.f); s_c[threadIdx.x] = make_float2(0.f, __builtin_inff());
+            if constexpr (AUX) s_d[threadIdx.x] = 0.0f;
         }
         __syncthreads();
         const int cnt = (int)min((uint32_t)RT, range.y - b0);
@@ -380,6 +393,8 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
             // two Gaussians per trip: their six LDS reads are in flight together
             const float4 a = s_a[j], bq = s_b[j], a2 = s_a[j + 1], bq2 = s_b[j + 1];
             const float2 cb = s_c[j], cb2 = s_c[j + 1];
+            float da = 0.f, db = 0.f;
+            if constexpr (AUX) { da = s_d[j]; db = s_d[j + 1]; }
             const float dxa = a.x - pxf, dya0 = a.y - pyf0, dya1 = a.y - pyf1;
             const float pa0 = -0.5f * (a.z * dxa * dxa + bq.x * dya0 * dya0) - a.w * dxa * dya0;
             const float pa1 = -0.5f * (a.z * dxa * dxa + bq.x * dya1 * dya1) - a.w * dxa * dya1;
@@ -390,20 +405,20 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
             // every Gaussian that only touches the tile's other half) costs the twelve instructions above and no exponential
             if (__builtin_amdgcn_ballot_w64((!done0 && !(pa0 < cb.y) && !(pa0 > 0.0f)) || (!done1 && !(pa1 < cb.y) && !(pa1 > 0.0f))) != 0ull) {   // (a NaN power passes, as in the reference's `if (power > 0) continue`)
                 if constexpr (TRAIN) {
-                    blend_one_rec(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2, b0 + (uint32_t)j + 1u, e0);
-                    blend_one_rec(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2, b0 + (uint32_t)j + 1u, e1);
+                    blend_one_rec<AUX>(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2, b0 + (uint32_t)j + 1u, e0, da, D0);
+                    blend_one_rec<AUX>(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2, b0 + (uint32_t)j + 1u, e1, da, D1);
                 } else {
-                    blend_one(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2);
-                    blend_one(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2);
+                    blend_one<AUX>(pa0, bq.y, bq.z, bq.w, cb.x, done0, T0, A0, A1, A2, da, D0);
+                    blend_one<AUX>(pa1, bq.y, bq.z, bq.w, cb.x, done1, T1, B0, B1, B2, da, D1);
                 }
             }
             if (__builtin_amdgcn_ballot_w64((!done0 && !(pb0 < cb2.y) && !(pb0 > 0.0f)) || (!done1 && !(pb1 < cb2.y) && !(pb1 > 0.0f))) != 0ull) {
                 if constexpr (TRAIN) {
-                    blend_one_rec(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2, b0 + (uint32_t)j + 2u, e0);
-                    blend_one_rec(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2, b0 + (uint32_t)j + 2u, e1);
+                    blend_one_rec<AUX>(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2, b0 + (uint32_t)j + 2u, e0, db, D0);
+                    blend_one_rec<AUX>(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2, b0 + (uint32_t)j + 2u, e1, db, D1);
                 } else {
-                    blend_one(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2);
-                    blend_one(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2);
+                    blend_one<AUX>(pb0, bq2.y, bq2.z, bq2.w, cb2.x, done0, T0, A0, A1, A2, db, D0);
+                    blend_one<AUX>(pb1, bq2.y, bq2.z, bq2.w, cb2.x, done1, T1, B0, B1, B2, db, D1);
                 }
             }
         }
@@ -414,11 +429,19 @@ __global__ __launch_bounds__(RT) void k_render(const uint2 *__restrict__ ranges,
         const size_t pix = (size_t)py0 * W + pxi;
         out[pix] = A0 + T0 * bg0; out[plane + pix] = A1 + T0 * bg1; out[2 * plane + pix] = A2 + T0 * bg2;
         if constexpr (TRAIN) { final_T[pix] = T0; n_end[pix] = e0; }
+        if constexpr (AUX) {
+            if (out_invdepth) out_invdepth[pix] = D0;
+            if (out_alpha) out_alpha[pix] = 1.0f - T0;
+        }
     }
     if (in1) {
         const size_t pix = (size_t)py1 * W + pxi;
         out[pix] = B0 + T1 * bg0; out[plane + pix] = B1 + T1 * bg1; out[2 * plane + pix] = B2 + T1 * bg2;
         if constexpr (TRAIN) { final_T[pix] = T1; n_end[pix] = e1; }
+        if constexpr (AUX) {
+            if (out_invdepth) out_invdepth[pix] = D1;
+            if (out_alpha) out_alpha[pix] = 1.0f - T1;
+        }
     }
 }
 
@@ -465,8 +488,12 @@ __device__ __forceinline__ void wave_sum_to_63(float *v)
 // S is the colour blended behind it, normalised by the transmittance behind it.  tb = T_final * <dL/dpixel, bg>.  The decision is the forward's:
 // `cand` holds k < n_end and the power test, alpha the forward's expressions; the saturation test needs no repeat (a pair before the pixel's last
 // blended one was not saturated).  The gradient passes through min(0.99, .) as if it were not there.
+// AUX: inverse depth d is a fourth colour channel with background 0 (gradient gD, running SD, record v[NREC] = sum of gD w); the alpha map's
+// gradient gO is already inside tb = T_final * (<dL/dpixel, bg> - gO), since d(1 - T_final) / dalpha = T_final / (1 - alpha).
+template <bool AUX>
 __device__ __forceinline__ bool grad_one(bool cand, float power, float dx, float dy, float A, float B, float C, float op, float r, float g, float b,
-                                         float gr, float gg, float gb, float tb, float &T, float &S0, float &S1, float &S2, float *v)
+                                         float gr, float gg, float gb, float tb, float &T, float &S0, float &S1, float &S2, float *v, float d, float gD,
+                                         float &SD)
 {
     const float G = __builtin_amdgcn_exp2f(power * 1.44269504088896341f);
     const float alpha = fminf(0.99f, op * G);
@@ -474,7 +501,9 @@ __device__ __forceinline__ bool grad_one(bool cand, float power, float dx, float
     const float inv = __builtin_amdgcn_rcpf(1.0f - alpha);
     const float Ti = T * inv;
     const float w = alpha * Ti;
-    const float dLda = Ti * (gr * (r - S0) + gg * (g - S1) + gb * (b - S2)) - tb * inv;
+    float bracket = gr * (r - S0) + gg * (g - S1) + gb * (b - S2);
+    if constexpr (AUX) bracket += gD * (d - SD);   // after the colour terms: with gD = 0 the sum is the colour-only one
+    const float dLda = Ti * bracket - tb * inv;
     const float dLdp = op * G * dLda;            // dalpha / dpower = op G
     v[0] += bl ? gr * w : 0.0f;
     v[1] += bl ? gg * w : 0.0f;
@@ -488,6 +517,10 @@ __device__ __forceinline__ bool grad_one(bool cand, float power, float dx, float
     S0 = bl ? alpha * r + (1.0f - alpha) * S0 : S0;
     S1 = bl ? alpha * g + (1.0f - alpha) * S1 : S1;
     S2 = bl ? alpha * b + (1.0f - alpha) * S2 : S2;
+    if constexpr (AUX) {
+        v[NREC] += bl ? gD * w : 0.0f;
+        SD = bl ? alpha * d + (1.0f - alpha) * SD : SD;
+    }
     T = bl ? Ti : T;
     return bl;
 }
@@ -496,17 +529,23 @@ __device__ __forceinline__ bool grad_one(bool cand, float power, float dx, float
 // the tile's largest n_end.  Per Gaussian a wave sums its 128 pixels' NREC values (wave_sum_to_63) only when one of its lanes blended it -- the
 // forward's ballot skip --, the two waves' sums meet in LDS, and the batch's records go out with plain stores at their slots (wave 0's sum + wave
 // 1's, in that order).  Entries behind the largest n_end are never reached: their records are written as zeros.
+// AUX (gsr_backward_aux with a map gradient): records of NREC + 1 floats, 1 / depth staged as in k_render<., true>, and the gradients of the
+// invdepth and alpha maps (d_invdepth, d_alpha: (H, W), either may be null = zero) walked along with the colour's.
+template <bool AUX>
 __global__ __launch_bounds__(RT) void k_render_backward(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ slot_list,
                                                         const uint32_t *__restrict__ slot_ids, int W, int H, int gx, const float2 *__restrict__ xy,
                                                         const float *__restrict__ colors, const float4 *__restrict__ conic_op, const float *__restrict__ bg,
                                                         const float *__restrict__ final_T, const uint32_t *__restrict__ n_end, const float *__restrict__ dout,
-                                                        float *__restrict__ rec)
+                                                        float *__restrict__ rec, const float *__restrict__ depth, const float *__restrict__ d_invdepth,
+                                                        const float *__restrict__ d_alpha)
 {
+    constexpr int NR = NREC + (AUX ? 1 : 0);
     __shared__ float4 s_a[RT];   // x, y, conic.x, conic.y
     __shared__ float4 s_b[RT];   // conic.z, opacity, r, g
     __shared__ float2 s_c[RT];   // b, skip threshold (k_render's)
+    __shared__ float s_d[AUX ? RT : 1];   // 1 / depth
     __shared__ uint32_t s_slot[RT];
-    __shared__ float s_part[2][NREC][RT];
+    __shared__ float s_part[2][NR][RT];
     __shared__ uint32_t s_top;
     const int tile = (int)tile_order[blockIdx.x];
     const int tbx = tile % gx, tby = tile / gx;
@@ -518,26 +557,35 @@ __global__ __launch_bounds__(RT) void k_render_backward(const uint2 *__restrict_
     const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
     float T0 = 1.0f, g00 = 0.f, g01 = 0.f, g02 = 0.f, T1 = 1.0f, g10 = 0.f, g11 = 0.f, g12 = 0.f;
     uint32_t e0 = 0, e1 = 0;
+    float gD0 = 0.f, gD1 = 0.f, gO0 = 0.f, gO1 = 0.f;
     if (in0) {
         const size_t pix = (size_t)py0 * W + pxi;
         T0 = final_T[pix]; e0 = n_end[pix]; g00 = dout[pix]; g01 = dout[plane + pix]; g02 = dout[2 * plane + pix];
+        if constexpr (AUX) { if (d_invdepth) gD0 = d_invdepth[pix]; if (d_alpha) gO0 = d_alpha[pix]; }
     }
     if (in1) {
         const size_t pix = (size_t)py1 * W + pxi;
         T1 = final_T[pix]; e1 = n_end[pix]; g10 = dout[pix]; g11 = dout[plane + pix]; g12 = dout[2 * plane + pix];
+        if constexpr (AUX) { if (d_invdepth) gD1 = d_invdepth[pix]; if (d_alpha) gO1 = d_alpha[pix]; }
     }
-    const float tb0 = T0 * (g00 * bg0 + g01 * bg1 + g02 * bg2), tb1 = T1 * (g10 * bg0 + g11 * bg1 + g12 * bg2);
+    // the alpha map joins the background term: d(1 - T_final) / dalpha_i = T_final / (1 - alpha_i)
+    float bgs0 = g00 * bg0 + g01 * bg1 + g02 * bg2;
+    if constexpr (AUX) bgs0 -= gO0;
+    const float tb0 = T0 * bgs0;
+    float bgs1 = g10 * bg0 + g11 * bg1 + g12 * bg2;
+    if constexpr (AUX) bgs1 -= gO1;
+    const float tb1 = T1 * bgs1;
     if (threadIdx.x == 0) s_top = 0u;
     __syncthreads();
     if (max(e0, e1) > 0u) atomicMax(&s_top, max(e0, e1));
     __syncthreads();
     const uint32_t top = max(s_top, range.x);
     for (uint32_t k = top + threadIdx.x; k < range.y; k += RT) {
-        float *__restrict__ r = rec + (size_t)slot_list[k] * NREC;
-        for (int c = 0; c < NREC; ++c) r[c] = 0.0f;
+        float *__restrict__ r = rec + (size_t)slot_list[k] * NR;
+        for (int c = 0; c < NR; ++c) r[c] = 0.0f;
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float S00 = 0.f, S01 = 0.f, S02 = 0.f, S10 = 0.f, S11 = 0.f, S12 = 0.f;
+    float S00 = 0.f, S01 = 0.f, S02 = 0.f, S10 = 0.f, S11 = 0.f, S12 = 0.f, SD0 = 0.f, SD1 = 0.f;
     for (uint32_t hi = top; hi > range.x;) {
         const uint32_t lo = hi - range.x > (uint32_t)RT ? hi - RT : range.x;
         const int cnt = (int)(hi - lo);
@@ -552,13 +600,16 @@ __global__ __launch_bounds__(RT) void k_render_backward(const uint2 *__restrict_
             s_a[t] = make_float4(p.x, p.y, co.x, co.y);
             s_b[t] = make_float4(co.z, co.w, colors[3 * id], colors[3 * id + 1]);
             s_c[t] = make_float2(colors[3 * id + 2], co.w > 0.0f ? -__logf(255.0f * co.w) - 1e-3f : (co.w != co.w ? -__builtin_inff() : __builtin_inff()));
+            if constexpr (AUX) s_d[t] = 1.0f / depth[id];   // k_render's expression
         }
-        for (int c = 0; c < NREC; ++c) { s_part[0][c][t] = 0.0f; s_part[1][c][t] = 0.0f; }
+        for (int c = 0; c < NR; ++c) { s_part[0][c][t] = 0.0f; s_part[1][c][t] = 0.0f; }
         __syncthreads();
         for (int j = cnt - 1; j >= 0; --j) {
             const uint32_t k = lo + (uint32_t)j;
             const float4 a = s_a[j], bq = s_b[j];
             const float2 cb = s_c[j];
+            float dj = 0.f;
+            if constexpr (AUX) dj = s_d[j];
             // the forward's expressions, operation for operation (-ffp-contract=off): the same power, so the same decisions
             const float dxa = a.x - pxf, dya0 = a.y - pyf0, dya1 = a.y - pyf1;
             const float pa0 = -0.5f * (a.z * dxa * dxa + bq.x * dya0 * dya0) - a.w * dxa * dya0;
@@ -566,19 +617,19 @@ __global__ __launch_bounds__(RT) void k_render_backward(const uint2 *__restrict_
             const bool c0 = k < e0 && !(pa0 < cb.y) && !(pa0 > 0.0f);
             const bool c1 = k < e1 && !(pa1 < cb.y) && !(pa1 > 0.0f);
             if (__builtin_amdgcn_ballot_w64(c0 || c1) == 0ull) continue;
-            float v[NREC];
-            for (int c = 0; c < NREC; ++c) v[c] = 0.0f;
-            const bool b0 = grad_one(c0, pa0, dxa, dya0, a.z, a.w, bq.x, bq.y, bq.z, bq.w, cb.x, g00, g01, g02, tb0, T0, S00, S01, S02, v);
-            const bool b1 = grad_one(c1, pa1, dxa, dya1, a.z, a.w, bq.x, bq.y, bq.z, bq.w, cb.x, g10, g11, g12, tb1, T1, S10, S11, S12, v);
+            float v[NR];
+            for (int c = 0; c < NR; ++c) v[c] = 0.0f;
+            const bool b0 = grad_one<AUX>(c0, pa0, dxa, dya0, a.z, a.w, bq.x, bq.y, bq.z, bq.w, cb.x, g00, g01, g02, tb0, T0, S00, S01, S02, v, dj, gD0, SD0);
+            const bool b1 = grad_one<AUX>(c1, pa1, dxa, dya1, a.z, a.w, bq.x, bq.y, bq.z, bq.w, cb.x, g10, g11, g12, tb1, T1, S10, S11, S12, v, dj, gD1, SD1);
             if (__builtin_amdgcn_ballot_w64(b0 || b1) == 0ull) continue;
-            wave_sum_to_63<NREC>(v);
+            wave_sum_to_63<NR>(v);
             if (lane == 63)
-                for (int c = 0; c < NREC; ++c) s_part[wave][c][j] = v[c];
+                for (int c = 0; c < NR; ++c) s_part[wave][c][j] = v[c];
         }
         __syncthreads();
         if (t < cnt) {
-            float *__restrict__ r = rec + (size_t)s_slot[t] * NREC;
-            for (int c = 0; c < NREC; ++c) r[c] = s_part[0][c][t] + s_part[1][c][t];
+            float *__restrict__ r = rec + (size_t)s_slot[t] * NR;
+            for (int c = 0; c < NR; ++c) r[c] = s_part[0][c][t] + s_part[1][c][t];
         }
         hi = lo;
     }
@@ -588,6 +639,8 @@ __global__ __launch_bounds__(RT) void k_render_backward(const uint2 *__restrict_
 // in slot order; then the chain back through k_preprocess's math: pixel centre -> NDC -> means3D; conic -> 2-D covariance -> J and the view
 // rotation -> 3-D covariance -> scales (with scale_modifier) and the raw quaternion, or cov3D_precomp.  A coordinate clamped at +-1.3 tan(fov)
 // enters J as a constant; Gaussians with radius 0 get exactly zero.
+// AUX: records of NREC + 1 floats; the last, dL/d(1 / tz), joins the view-depth gradient as -(sum) / tz^2, after the Jacobian's terms.
+template <bool AUX>
 __global__ __launch_bounds__(TB) void k_preprocess_backward(int P, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ offs, const float *__restrict__ rec,
                                                             const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ rots,
                                                             const float *__restrict__ cov3d_pre, Cam cam, const int *__restrict__ radii,
@@ -597,14 +650,15 @@ __global__ __launch_bounds__(TB) void k_preprocess_backward(int P, const uint32_
 {
     const int s = blockIdx.x * TB + threadIdx.x;
     if (s >= P) return;
+    constexpr int NR = NREC + (AUX ? 1 : 0);
     const uint32_t i = perm[s];
-    float acc[NREC];
-    for (int c = 0; c < NREC; ++c) acc[c] = 0.0f;
+    float acc[NR];
+    for (int c = 0; c < NR; ++c) acc[c] = 0.0f;
     float gm0 = 0.f, gm1 = 0.f, gm2 = 0.f, gnx = 0.f, gny = 0.f;
     float gc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
     if (radii[i] > 0) {
         for (uint32_t q = offs[s], qe = offs[s + 1]; q < qe; ++q)
-            for (int c = 0; c < NREC; ++c) acc[c] += rec[(size_t)q * NREC + c];
+            for (int c = 0; c < NR; ++c) acc[c] += rec[(size_t)q * NR + c];
         // k_preprocess's forward values
         const float px = means[3 * i], py = means[3 * i + 1], pz = means[3 * i + 2];
         const float *__restrict__ V = cam.view, *__restrict__ M = cam.proj;
@@ -674,7 +728,8 @@ __global__ __launch_bounds__(TB) void k_preprocess_backward(int P, const uint32_
         const float gj00 = ga0x * V[0] + ga0y * V[4] + ga0z * V[8], gj02 = ga0x * V[2] + ga0y * V[6] + ga0z * V[10];
         const float gj11 = ga1x * V[1] + ga1y * V[5] + ga1z * V[9], gj12 = ga1x * V[2] + ga1y * V[6] + ga1z * V[10];
         const float tz2 = tz * tz, tz3 = tz2 * tz;
-        const float gtz = -fx / tz2 * gj00 + 2.0f * fx * tx / tz3 * gj02 - fy / tz2 * gj11 + 2.0f * fy * ty / tz3 * gj12;
+        float gtz = -fx / tz2 * gj00 + 2.0f * fx * tx / tz3 * gj02 - fy / tz2 * gj11 + 2.0f * fy * ty / tz3 * gj12;
+        if constexpr (AUX) gtz += -acc[NREC] / tz2;   // the invdepth map: d(1 / tz) / dtz
         const float gtx = clx ? 0.0f : -fx / tz2 * gj02, gty = cly ? 0.0f : -fy / tz2 * gj12;
         gm0 += gtx * V[0] + gty * V[1] + gtz * V[2];
         gm1 += gtx * V[4] + gty * V[5] + gtz * V[6];
@@ -719,7 +774,9 @@ int make_cam(Cam *cam, int W, int H, const float *view_dev, const float *proj_de
     return GPCC_OK;
 }
 
-// The frame state gsr_forward_train hands to gsr_backward: GSR_STATE_WORDS host words, the fields below in this order (word 0 = L ... word 13 = n_end).
+// The frame state gsr_forward_train hands to gsr_backward: GSR_STATE_WORDS host words, the fields below in this order (word 0 = L ... word 13 = n_end;
+// words 14 and 15 are zero unless the frame was rendered with a map: the per-Gaussian view depth, kept with the frame, and which maps).
+constexpr uint64_t AUX_INVDEPTH = 1, AUX_ALPHA = 2;
 struct FrameState {
     uint64_t L, P, W, H;
     const float2 *xy;
@@ -729,8 +786,10 @@ struct FrameState {
     const uint32_t *tile_order, *slots, *slot_ids;
     const float *final_T;
     const uint32_t *n_end;
+    const float *depth;
+    uint64_t aux;
 };
-static_assert(sizeof(FrameState) == 14 * 8 && sizeof(FrameState) <= GSR_STATE_WORDS * 8, "the frame state is fourteen 64-bit words of gsr_forward_train's state[]");
+static_assert(sizeof(FrameState) == GSR_STATE_WORDS * 8, "the frame state is the sixteen 64-bit words of gsr_forward_train's state[]");
 void store_state(const FrameState &s, uint64_t *state) { memcpy(state, &s, sizeof s); }
 FrameState load_state(const uint64_t *state) { FrameState s; memcpy(&s, state, sizeof s); return s; }
 
@@ -742,12 +801,14 @@ struct FrameBufs {
     uint32_t *perm_a, *perm_b, *offs, *ord_a, *ord_b, *n_end;
     uint2 *ranges;
     float *final_T;
+    float *depth;   // the training frame with a map (ndepth = P1), else nothing: the frame's depths live in the arena
 };
-template <class Taker> void take_frame_bufs(Taker &c, FrameBufs &b, size_t P1, size_t ntiles, size_t npix)
+template <class Taker> void take_frame_bufs(Taker &c, FrameBufs &b, size_t P1, size_t ntiles, size_t npix, size_t ndepth)
 {
     b.xy = c.template take<float2>(P1); b.conic_op = c.template take<float4>(P1); b.perm_a = c.template take<uint32_t>(P1); b.perm_b = c.template take<uint32_t>(P1);
     b.offs = c.template take<uint32_t>(P1 + 1); b.ranges = c.template take<uint2>(ntiles); b.ord_a = c.template take<uint32_t>(ntiles); b.ord_b = c.template take<uint32_t>(ntiles);
     b.final_T = c.template take<float>(npix); b.n_end = c.template take<uint32_t>(npix);
+    if (ndepth) b.depth = c.template take<float>(ndepth);
 }
 
 // What differs between the two frames.  Training: the frame state lives in memory the caller hands out through `alloc` (so that it outlives the
@@ -758,6 +819,7 @@ struct FrameMode {
     gsr_alloc_fn alloc;
     void *alloc_user;
     uint64_t *state;
+    float *out_invdepth, *out_alpha;   // the maps of the _aux entry points, (H, W) each; both null: the frame as it was before them
 };
 
 // One frame, from the camera to the image: gsr_forward and gsr_forward_train after their argument checks.
@@ -773,9 +835,11 @@ int render_frame(gpcc_ctx *ctx, const FrameMode &m, int P, const float *backgrou
     static const int cull = dev_env_int("GAUSPCC_RASTER_CULL", 1) != 0 ? 1 : 0;   // exact tile culling (tile_touches); 0: the reference's lists
     static const bool stats = dev_env_int("GAUSPCC_RASTER_STATS", 0) != 0;
     const bool two_level = m.train || sort2;   // the single sort on (tile << 32 | depth bits) exists for the inference frame only
+    const bool aux = m.out_invdepth || m.out_alpha;
     FrameBufs b = {};
     if (m.train)   // frame state sized by P, the tiles and the pixels: one block from the caller
-        GP_TRY(caller_block(m.alloc, m.alloc_user, "gsr_forward_train: frame state", [&](Carver &c) { take_frame_bufs(c, b, P1, ntiles, (size_t)W * H); }));
+        GP_TRY(caller_block(m.alloc, m.alloc_user, "gsr_forward_train: frame state",
+                            [&](Carver &c) { take_frame_bufs(c, b, P1, ntiles, (size_t)W * H, aux ? P1 : 0); }));
     uint32_t *slot_ids = nullptr, *sa = nullptr, *sb = nullptr;   // training, sized by the pair count: slot -> Gaussian, and the sorted slots (the sort ping-pongs)
     size_t want = P1 * 112 + (size_t)ntiles * (m.train ? 32 : 8) + ((size_t)8 << 20);
     uint32_t L = 0;
@@ -787,11 +851,12 @@ int render_frame(gpcc_ctx *ctx, const FrameMode &m, int P, const float *backgrou
         GP_TRY(ctx->arena.reserve(want + (size_t)L * 40));
         ctx->arena.reset();
         if (!m.train) {   // `want` covers what P sizes and the ranges; the tile order's pair comes out of the slack, or of a second attempt
-            take_frame_bufs(ctx->arena, b, P1, ntiles, 0);
+            take_frame_bufs(ctx->arena, b, P1, ntiles, 0, 0);
             if (!b.xy || !b.conic_op || !b.perm_a || !b.perm_b || !b.offs || !b.ranges) return fail(GPCC_ERR_NOMEM, "rasteriser workspace");
             if (!b.ord_a || !b.ord_b) { want += (size_t)ntiles * 32; continue; }
         }
         TAKE(depth, float, P1); TAKE(touched, uint32_t, P1 + 1);
+        if (b.depth) depth = b.depth;   // a training frame with a map keeps its depths for the backward
         TAKE(rect_total, unsigned long long, RECT_SLOTS + 1);      // the slots of k_preprocess, then their sum
         TAKE(dka, uint64_t, P1); TAKE(dkb, uint64_t, P1); TAKE(recs, uint4, P1);
         HIP_TRY(hipMemsetAsync(b.ranges, 0, sizeof(uint2) * (size_t)ntiles, st));
@@ -861,16 +926,23 @@ int render_frame(gpcc_ctx *ctx, const FrameMode &m, int P, const float *backgrou
             GP_TRY(radix_sort_u64(ctx, st, &k0, &k1, &v0, &v1, ntiles, 8));
             tile_order = v0;
         }
-        if (m.train)
-            k_render<true><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background, out_color,
-                                                            slot_ids, b.final_T, b.n_end);
+        if (m.train && aux)
+            k_render<true, true><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background,
+                                                                  out_color, slot_ids, b.final_T, b.n_end, depth, m.out_invdepth, m.out_alpha);
+        else if (m.train)
+            k_render<true, false><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background,
+                                                                   out_color, slot_ids, b.final_T, b.n_end, nullptr, nullptr, nullptr);
+        else if (aux)
+            k_render<false, true><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background,
+                                                                   out_color, nullptr, nullptr, nullptr, depth, m.out_invdepth, m.out_alpha);
         else
-            k_render<false><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background, out_color,
-                                                             nullptr, nullptr, nullptr);
+            k_render<false, false><<<(unsigned)ntiles, RT, 0, st>>>(b.ranges, tile_order, vals_sorted, W, H, cam.gx, b.xy, colors_precomp, b.conic_op, background,
+                                                                    out_color, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         LAUNCH_CHECK();
         HIP_TRY(hipStreamSynchronize(st));
         if (m.train)
-            store_state(FrameState{L, (uint64_t)P, (uint64_t)W, (uint64_t)H, b.xy, b.conic_op, perm, offs, b.ranges, tile_order, vals_sorted, slot_ids, b.final_T, b.n_end},
+            store_state(FrameState{L, (uint64_t)P, (uint64_t)W, (uint64_t)H, b.xy, b.conic_op, perm, offs, b.ranges, tile_order, vals_sorted, slot_ids, b.final_T, b.n_end,
+                                   b.depth, (m.out_invdepth ? AUX_INVDEPTH : 0) | (m.out_alpha ? AUX_ALPHA : 0)},
                         m.state);
         return device_error_check(ctx);
     }
@@ -908,43 +980,66 @@ extern "C" int gsr_visible_filter(gpcc_ctx *ctx, int P, int W, int H, const floa
     return GPCC_OK;
 }
 
+extern "C" int gsr_forward_aux(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                               const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                               const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
+                               int *radii, float *out_invdepth, float *out_alpha, int64_t *num_rendered_out, void *stream)
+{
+    (void)prefiltered;
+    GP_TRY(check_frame_args(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, out_color, radii));
+    HIP_TRY(hipSetDevice(ctx->device));
+    return render_frame(ctx, FrameMode{false, nullptr, nullptr, nullptr, out_invdepth, out_alpha}, P, background, W, H, means3D, colors_precomp, opacities, scales,
+                        scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, out_color, radii, num_rendered_out, (hipStream_t)stream);
+}
+
 extern "C" int gsr_forward(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
                            const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
                            const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
                            int *radii, int64_t *num_rendered_out, void *stream)
 {
-    (void)prefiltered;
-    GP_TRY(check_frame_args(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, out_color, radii));
-    HIP_TRY(hipSetDevice(ctx->device));
-    return render_frame(ctx, FrameMode{false, nullptr, nullptr, nullptr}, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, out_color, radii, num_rendered_out, (hipStream_t)stream);
+    return gsr_forward_aux(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                           tan_fovx, tan_fovy, prefiltered, out_color, radii, nullptr, nullptr, num_rendered_out, stream);
 }
 
 // The training forward: gsr_forward's two-level path with the frame state the backward needs kept (FrameMode).
-extern "C" int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
-                                 const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
-                                 const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
-                                 int *radii, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state, int64_t *num_rendered_out, void *stream)
+extern "C" int gsr_forward_train_aux(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                                     const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                                     const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
+                                     int *radii, float *out_invdepth, float *out_alpha, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state,
+                                     int64_t *num_rendered_out, void *stream)
 {
     (void)prefiltered;
     if (!alloc || !state) return fail(GPCC_ERR_ARG, "null argument");
     GP_TRY(check_frame_args(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, out_color, radii));
     for (int k = 0; k < GSR_STATE_WORDS; ++k) state[k] = 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    return render_frame(ctx, FrameMode{true, alloc, alloc_user, state}, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, out_color, radii, num_rendered_out, (hipStream_t)stream);
+    return render_frame(ctx, FrameMode{true, alloc, alloc_user, state, out_invdepth, out_alpha}, P, background, W, H, means3D, colors_precomp, opacities, scales,
+                        scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, out_color, radii, num_rendered_out, (hipStream_t)stream);
 }
 
-extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
-                            const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
-                            const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, const int *radii, const float *dL_dout,
-                            gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
-                            float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream)
+extern "C" int gsr_forward_train(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                                 const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                                 const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
+                                 int *radii, gsr_alloc_fn alloc, void *alloc_user, uint64_t *state, int64_t *num_rendered_out, void *stream)
+{
+    return gsr_forward_train_aux(ctx, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
+                                 projmatrix, tan_fovx, tan_fovy, prefiltered, out_color, radii, nullptr, nullptr, alloc, alloc_user, state, num_rendered_out, stream);
+}
+
+extern "C" int gsr_backward_aux(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D,
+                                const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                                const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, const int *radii,
+                                const float *dL_dout, const float *dL_dinvdepth, const float *dL_dalpha, gsr_alloc_fn alloc, void *alloc_user,
+                                float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations,
+                                float *dL_dcov3D, void *stream)
 {
     (void)opacities;
     if (!ctx || !state || !background || !viewmatrix || !projmatrix || !dL_dout || !alloc) return fail(GPCC_ERR_ARG, "null argument");
     const FrameState s = load_state(state);
     if (s.P != (uint64_t)P || s.W != (uint64_t)W || s.H != (uint64_t)H) return fail(GPCC_ERR_ARG, "frame state of another frame");
+    if ((dL_dinvdepth && !(s.aux & AUX_INVDEPTH)) || (dL_dalpha && !(s.aux & AUX_ALPHA)))
+        return fail(GPCC_ERR_ARG, "gradient of a map the frame was not rendered with");
+    const bool aux = dL_dinvdepth || dL_dalpha;
     if (W <= 0 || H <= 0) return fail(GPCC_ERR_ARG, "bad image size");
     if (P <= 0) return GPCC_OK;
     if (!means3D || !colors_precomp || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities) return fail(GPCC_ERR_ARG, "null argument");
@@ -956,13 +1051,32 @@ extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const f
     const int ntiles = cam.gx * cam.gy;
     float *rec = nullptr;
     if (s.L > 0) {
-        GP_TRY(caller_alloc(alloc, alloc_user, (size_t)s.L * NREC * sizeof(float), &rec, "gsr_backward: records"));
-        k_render_backward<<<(unsigned)ntiles, RT, 0, st>>>(s.ranges, s.tile_order, s.slots, s.slot_ids, W, H, cam.gx, s.xy, colors_precomp, s.conic_op, background,
-                                                           s.final_T, s.n_end, dL_dout, rec);
+        GP_TRY(caller_alloc(alloc, alloc_user, (size_t)s.L * (NREC + (aux ? 1 : 0)) * sizeof(float), &rec, "gsr_backward: records"));
+        if (aux)
+            k_render_backward<true><<<(unsigned)ntiles, RT, 0, st>>>(s.ranges, s.tile_order, s.slots, s.slot_ids, W, H, cam.gx, s.xy, colors_precomp, s.conic_op,
+                                                                     background, s.final_T, s.n_end, dL_dout, rec, s.depth, dL_dinvdepth, dL_dalpha);
+        else
+            k_render_backward<false><<<(unsigned)ntiles, RT, 0, st>>>(s.ranges, s.tile_order, s.slots, s.slot_ids, W, H, cam.gx, s.xy, colors_precomp, s.conic_op,
+                                                                      background, s.final_T, s.n_end, dL_dout, rec, nullptr, nullptr, nullptr);
         LAUNCH_CHECK();
     }
-    k_preprocess_backward<<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, s.perm, s.offs, rec, means3D, scales, rotations, cov3D_precomp, cam, radii, dL_dmeans3D,
-                                                                dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D);
+    if (aux)
+        k_preprocess_backward<true><<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, s.perm, s.offs, rec, means3D, scales, rotations, cov3D_precomp, cam, radii, dL_dmeans3D,
+                                                                          dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D);
+    else
+        k_preprocess_backward<false><<<(unsigned)cdiv(P, TB), TB, 0, st>>>(P, s.perm, s.offs, rec, means3D, scales, rotations, cov3D_precomp, cam, radii, dL_dmeans3D,
+                                                                           dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D);
     LAUNCH_CHECK();
     return GPCC_OK;
+}
+
+extern "C" int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                            const float *opacities, const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                            const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy, const int *radii, const float *dL_dout,
+                            gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
+                            float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream)
+{
+    return gsr_backward_aux(ctx, state, P, background, W, H, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
+                            projmatrix, tan_fovx, tan_fovy, radii, dL_dout, nullptr, nullptr, alloc, alloc_user, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities,
+                            dL_dscales, dL_drotations, dL_dcov3D, stream);
 }

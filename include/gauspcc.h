@@ -599,6 +599,33 @@ GPCC_API int gsr_backward(gpcc_ctx *ctx, const uint64_t *state, int P, const flo
                           const int *radii, const float *dL_dout, gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D,
                           float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream);
 
+/* ================= Rasteriser depth and opacity maps =================
+ * The three calls above with two more maps of the frame, (H, W) float32 each, either may be NULL: out_invdepth = sum_i w_i / tz_i over the
+ * Gaussians a pixel blends (w_i = alpha_i T_i, the colour's own weights and blend rules; tz_i the view-space depth the frame sorts by; no
+ * background term, not normalised -- the inverse-depth map of the public rasteriser's depth-regularisation release) and out_alpha = 1 - T_final,
+ * the accumulated opacity (out_color = sum_i w_i c_i + (1 - out_alpha) background).  Pixels no Gaussian reaches hold 0 in both.
+ * gsr_backward_aux takes dL_dinvdepth / dL_dalpha (NULL: zero; a non-NULL one needs a frame rendered with that map) and adds their part to
+ * the same outputs: inverse depth is a fourth colour channel with background 0 whose per-Gaussian value 1 / tz sends its gradient to means3D
+ * through the view matrix's third row; records are 40 L bytes then, and the result stays bitwise reproducible.  A training frame rendered
+ * with a map keeps its per-Gaussian depths in the first block it asks `alloc` for (4 P bytes more) and notes the maps in state's last two
+ * words.  With both NULL each call is its sibling above: the same kernels, the same bits. */
+GPCC_API int gsr_forward_aux(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                             const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                             const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
+                             int prefiltered, float *out_color, int *radii, float *out_invdepth, float *out_alpha, int64_t *num_rendered_out,
+                             void *stream);
+GPCC_API int gsr_forward_train_aux(gpcc_ctx *ctx, int P, const float *background, int W, int H, const float *means3D, const float *colors_precomp,
+                                   const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                                   const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
+                                   int prefiltered, float *out_color, int *radii, float *out_invdepth, float *out_alpha, gsr_alloc_fn alloc,
+                                   void *alloc_user, uint64_t *state, int64_t *num_rendered_out, void *stream);
+GPCC_API int gsr_backward_aux(gpcc_ctx *ctx, const uint64_t *state, int P, const float *background, int W, int H, const float *means3D,
+                              const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
+                              const float *rotations, const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, float tan_fovx,
+                              float tan_fovy, const int *radii, const float *dL_dout, const float *dL_dinvdepth, const float *dL_dalpha,
+                              gsr_alloc_fn alloc, void *alloc_user, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                              float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream);
+
 /* ================= GausPcgc context network, training path (network_ue_4stage_conv.py:100-182 with gradients) =================
  * The frame is the encoder's teacher-forced layout: one octree (the FOG loop), a "prior set" of rows (levels 0..L-2 concatenated, base
  * level first, each level in Morton order) and a "target set" (levels 1..L-1), and ONE tile pool for the convolutions of both.  Rows of
