@@ -6,15 +6,17 @@ import a HAC++ checkout swaps in at gaussian_renderer/__init__.py:25, beside hac
 `is_training=False` is neural_gaussians.generate_neural_gaussians, which serves HAC++ inference.  `is_training=True` is the reference's
 branch (:46-119 and the 11-tuple of :207) built from the library's pieces:
 
-  select_rows        the five `tensor[visible_mask]` and six `tensor[choose_idx]` gathers: one scan, one launch and one wait per set
-                     (gpcc_compact_rows), one launch without a wait in the backward (gpcc_expand_rows)
-  quant_noise        x + U(-0.5, 0.5) * Q0 * (1 + tanh(adj)) on feat, scaling and offsets in one launch per set (gsnn_noise_forward); the
-                     adjustments are read in place from mlp_grid's output, the per-row steps go to the rate modules as (n, 1) operands
+  visible_rows       the five `tensor[visible_mask]` gathers (none when visible_mask is None) and, through the same select_rows, the six
+                     `tensor[choose_idx]` gathers: one scan, one launch and one wait per set (gpcc_compact_rows), one launch without a
+                     wait in the backward (gpcc_expand_rows)
+  attribute_noise    x + U(-0.5, 0.5) * Q0 * (1 + tanh(adj)) on feat, scaling and offsets in one launch per set (quant_noise:
+                     gsnn_noise_forward); the adjustments are read in place from mlp_grid's output, the per-row steps go to the rate
+                     modules as (n, 1) operands
   the model's own    calc_interp_feat, get_grid_mlp, get_deform_mlp, EG_mix_prob_2, entropy_gaussian, called as modules (they train too)
   the core           neural_gaussians_train(..., mask_after_opacity=True)
 
-Where HAC++ differs from HAC's branch (neural_gaussians._generate_training): the ten-way mlp_grid split with `prob` third; the 5 % of
-anchors for the rate terms are drawn over ALL anchors, not intersected with mask_anchor, gathered from the full model, put through the
+Where HAC++ differs from HAC's branch (neural_gaussians.generate_neural_gaussians with is_training=True): the ten-way mlp_grid split with
+`prob` third; the 5 % of anchors for the rate terms are drawn over ALL anchors, not intersected with mask_anchor, gathered from the full model, put through the
 context a second time and given their own noise; the feat rate is the two-component mixture with the channel-context MLP's second
 component; mask_anchor (n, 1) multiplies the bits instead of a mask-rate factor on the means.
 
@@ -24,11 +26,11 @@ tensors are drawn together before the channel-context MLP runs; the reference dr
 """
 import torch
 
-from . import neural_gaussians as _ng
+from . import neural_gaussians
 from .densify import select_rows
-from .neural_gaussians import neural_gaussians_train, quant_noise
+from .neural_gaussians import attribute_noise, check_context_width, neural_gaussians_train, out_columns, rate_means, visible_rows
 
-Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2
+Q0 = (1, 0.001, 0.2)
 
 
 def _uniform_like(t):
@@ -47,27 +49,18 @@ def _context(pc, anchor, width):
 
 
 def _noise(feat, scaling, offsets, adj):
-    """the three attributes with their noise (fresh draws in the reference's order) and the (n, 3) steps"""
-    us = [_uniform_like(feat), _uniform_like(scaling), _uniform_like(offsets)]
-    return quant_noise([feat, scaling, offsets], us, [Q_FEAT, Q_SCALING, Q_OFFSETS], adj)
+    return attribute_noise(_uniform_like, feat, scaling, offsets, Q0, adj)
 
 
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0):
     if not is_training:
-        return _ng.generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=False, step=step)
+        return neural_gaussians.generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=False, step=step)
     F, K = pc.feat_dim, pc.n_offsets
-    width = 3 * F + 12 + 6 * K + 3
-    out_cols = [m for m in pc.get_grid_mlp if isinstance(m, torch.nn.Linear)][-1].out_features
-    if out_cols != width:
-        raise ValueError(f"hac_plus_renderer: pc.get_grid_mlp returns {out_cols} columns, HAC++'s ten-way split has {width} "
-                         f"(feat_dim {F}, {K} offsets); HAC's branch is gauspcc_amd.neural_gaussians.generate_neural_gaussians")
+    width = check_context_width("hac_plus_renderer", "get_grid_mlp", "HAC++'s ten-way", (pc.get_anchor.shape[0], out_columns(pc.get_grid_mlp)), pc, heads=3,
+                                hint="; HAC's branch is gauspcc_amd.neural_gaussians.generate_neural_gaussians")
     split = [F, F, F, 6, 6, 3 * K, 3 * K, 1, 1, 1]
-    all_masks = pc.get_mask
-    model = (pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, all_masks)
-    if visible_mask is None:     # every anchor: nothing to gather
-        anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = model
-    else:
-        anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = select_rows(visible_mask, *model)
+    model = (pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, pc.get_mask)
+    anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = visible_rows(visible_mask, *model)
     bit_per_param = bit_per_feat_param = bit_per_scaling_param = bit_per_offsets_param = None
     if 3000 < step <= 10000:
         feat, grid_scaling, grid_offsets, _ = _noise(feat, grid_scaling, grid_offsets, None)
@@ -91,11 +84,7 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
         bit_scaling = bit_scaling * mask_anchor_c
         bit_offsets = pc.entropy_gaussian.forward(offsets_c.view(-1, 3 * K), mean_offsets, scale_offsets, Q[:, 2:3], pc._offset.mean())
         bit_offsets = bit_offsets * mask_anchor_c * masks_c
-        bit_per_feat_param = torch.sum(bit_feat) / bit_feat.numel()
-        bit_per_scaling_param = torch.sum(bit_scaling) / bit_scaling.numel()
-        bit_per_offsets_param = torch.sum(bit_offsets) / bit_offsets.numel()
-        bit_per_param = ((torch.sum(bit_feat) + torch.sum(bit_scaling) + torch.sum(bit_offsets))
-                         / (bit_feat.numel() + bit_scaling.numel() + bit_offsets.numel()))
+        bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param = rate_means(bit_feat, bit_scaling, bit_offsets)
     xyz, color, opacity, scaling, rot, neural_opacity, keep = neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, binary_grid_masks,
                                                                                      viewpoint_camera.camera_center, pc, mask_after_opacity=True)
     return xyz, color, opacity, scaling, rot, neural_opacity, keep, bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param

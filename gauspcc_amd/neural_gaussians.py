@@ -12,7 +12,11 @@ test (:188-205) where HAC multiplies them into the opacity before it (:136-137) 
 context model's rate terms on the 5 % chosen anchors (the model's own torch modules: they train too) and then the differentiable core
 neural_gaussians_train (gsnn_forward_train / gsnn_backward), which HAC++, TC-GS and CAT-3DGS callers can use after their own rate code.
 HAC++'s training branch is gauspcc_amd.hac_plus_renderer, CAT-3DGS's renderer gauspcc_amd.cat_renderer, TC-GS's gauspcc_amd.tcgs_renderer, all built on that core, on quant_noise
-below (gsnn_noise_forward_b / _backward_b) and, for inference, on _generate_tail.
+below (gsnn_noise_forward_b / _backward_b) and on the frame the four renderers share (the section after quantise_steps): the row sets
+of inference (gathered_rows, rows_in_place) and its end (emit_gaussians), the visible rows of training (visible_rows), the attribute noise
+(attribute_noise), the four rate means (rate_means), the context-width check (check_context_width) and the walk over the MLPs' parameters
+(mlp_tensors).  What stays in each renderer is what its model does differently: its context, its quantisation with the time_sub bracket
+and its rule for an empty set, its rate terms.
 The model `pc` is used through the attributes the reference uses.  When `pc.decoded_version` is false the attributes are first quantised
 with the context model's step sizes exactly as the reference does (:103-114); everything after that -- view vectors,
 feature bank, the three MLPs, masking, assembly -- is ONE call into libgauspcc (gsnn_generate: two kernels and a scan
@@ -29,6 +33,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib, runtime
 from .runtime import ptr, ptrs
 from .anchor_codec import Q_FEAT, Q_OFFSETS, Q_SCALING, run_mlp2, ste_multistep
+from .densify import select_rows
 
 
 def quant_steps(pc, anchor):
@@ -47,96 +52,6 @@ def quant_steps(pc, anchor):
 
 def _f32(t):
     return t.detach().to(torch.float32).contiguous()
-
-
-def _mlp_tensors(pc, convert=lambda p: p):
-    """{w1, b1, w2, b2} of mlp_feature_bank (None x 4 without the bank), mlp_opacity, mlp_cov, mlp_color, each through `convert`."""
-    def walk(seq):
-        mods = [m for m in seq if isinstance(m, torch.nn.Linear)]
-        if len(mods) != 2:
-            raise TypeError("expected nn.Sequential(Linear, ReLU, Linear, ...) as built in HAC/scene/gaussian_model.py:229-256")
-        return [convert(p) for p in (mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias)]
-    bank = walk(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
-    return bank + walk(pc.get_opacity_mlp) + walk(pc.get_cov_mlp) + walk(pc.get_color_mlp)
-
-
-def _linears(pc):
-    """The 16 tensors as detached float32 contiguous copies: what the inference call reads."""
-    return _mlp_tensors(pc, _f32)
-
-
-def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0):
-    if is_training:
-        return _generate_training(viewpoint_camera, pc, visible_mask, step)
-    return _generate_inference(viewpoint_camera, pc, visible_mask)
-
-
-def _no_gaussians(dev):
-    """(xyz, color, opacity, scaling, rot) of zero Gaussians."""
-    return tuple(torch.empty(0, c, device=dev) for c in (3, 3, 1, 3, 4))
-
-
-@torch.no_grad()
-def _generate_inference(viewpoint_camera, pc, visible_mask):
-    time_sub = 0
-    dev = pc.get_anchor.device
-    K, F = pc.n_offsets, pc.feat_dim
-    rows = None
-    if not pc.decoded_version:      # quantise as the encoder would (:103-114): on the gathered rows, as the reference does
-        if visible_mask is None:
-            visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=dev)
-        anchor = pc.get_anchor[visible_mask]
-        feat = pc._anchor_feat[visible_mask]
-        grid_offsets = pc._offset[visible_mask]
-        grid_scaling = pc.get_scaling[visible_mask]
-        binary_grid_masks = pc.get_mask[visible_mask]
-        if anchor.shape[0] == 0:
-            return (*_no_gaussians(dev), time_sub)
-        torch.cuda.synchronize(); t1 = time.time()
-        q_feat, q_scaling, q_offsets = quant_steps(pc, anchor)
-        feat = ste_multistep(feat, q_feat, pc._anchor_feat.mean())
-        grid_scaling = ste_multistep(grid_scaling, q_scaling, pc.get_scaling.mean())
-        grid_offsets = ste_multistep(grid_offsets.reshape(anchor.shape[0], -1), q_offsets, pc._offset.mean()).view_as(grid_offsets)
-        torch.cuda.synchronize(); time_sub = time.time() - t1
-        n = anchor.shape[0]
-    else:
-        # decoded model: the kernels read the visible rows of the model's tensors in place (the reference's five `tensor[visible_mask]`
-        # gathers, :54-58, are 0.8 GB of copies per million anchors)
-        anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, pc.get_mask
-        n = anchor.shape[0]
-        if visible_mask is not None:
-            rows = torch.nonzero(visible_mask).view(-1).to(torch.int32)
-            n = rows.numel()
-    if n == 0:                      # no visible anchor: the reference's tensor program runs on empty tensors (:33-38, 115-167); no device buffer to hand over
-        return (*_no_gaussians(dev), time_sub)
-    return (*_generate_tail(viewpoint_camera, pc, n, rows, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks), time_sub)
-
-
-@torch.no_grad()
-def _generate_tail(viewpoint_camera, pc, n, rows, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks):
-    """gsnn_generate on n > 0 anchors -- the rows `rows` (int32 index list) of the tensors, or all of them (rows None) -- to (xyz, color,
-    opacity, scaling, rot).  The end of every inference path: HAC's and HAC++'s above, CAT-3DGS's in gauspcc_amd.cat_renderer."""
-    dev = anchor.device
-    K, F = pc.n_offsets, pc.feat_dim
-    tensors = _linears(pc)
-    anchor, feat, grid_offsets, grid_scaling = _f32(anchor), _f32(feat), _f32(grid_offsets), _f32(grid_scaling)
-    mask = _f32(binary_grid_masks).view(-1, K)
-    cam = _f32(viewpoint_camera.camera_center).view(3)
-    xyz = torch.empty(n * K, 3, device=dev); color = torch.empty(n * K, 3, device=dev); opacity = torch.empty(n * K, 1, device=dev)
-    scaling = torch.empty(n * K, 3, device=dev); rot = torch.empty(n * K, 4, device=dev)
-    m = C.c_int64()
-    _lib.check(_lib.lib().gsnn_generate(runtime.context(dev), n, ptr(rows), F, K, anchor.data_ptr(), feat.data_ptr(),
-                                        grid_offsets.data_ptr(), grid_scaling.data_ptr(), mask.data_ptr(), cam.data_ptr(), ptrs(tensors, 16), xyz.data_ptr(), color.data_ptr(),
-                                        opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), C.byref(m), runtime.stream_ptr(dev)))
-    m = m.value
-    return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m]
-
-
-# ---- training path ----------------------------------------------------------------------------------------------------------------------
-
-def _mlp_params(pc):
-    """The 16 parameters themselves, so that autograd delivers their gradients."""
-    return _mlp_tensors(pc)
 
 
 class _NeuralGaussians(torch.autograd.Function):
@@ -193,7 +108,7 @@ def neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, masks, cam_
     if F not in (32, 50) or not 1 <= K <= 64:
         raise _lib.GpccError(-1, f"neural_gaussians_train: feat_dim must be 32 or 50 and n_offsets 1..64 (got {F}, {K})")
     cam = cam_center.reshape(3)
-    return _NeuralGaussians.apply(bool(mask_after_opacity), anchor, feat, grid_offsets, grid_scaling, masks, cam, *_mlp_params(pc))
+    return _NeuralGaussians.apply(bool(mask_after_opacity), anchor, feat, grid_offsets, grid_scaling, masks, cam, *mlp_tensors(pc))
 
 
 def _noise_args(xs, us, q0s, adj, cols):
@@ -326,12 +241,134 @@ def quantise_steps(xs, q0s, adj, cols=None, base=1.0, means=None):
     return (*ys, q)
 
 
+# ---- the frame the four renderers share (this module's, hac_plus_renderer, tcgs_renderer, cat_renderer) ------------------------------------
+
+def mlp_tensors(pc, convert=None):
+    """{w1, b1, w2, b2} of mlp_feature_bank (None x 4 without the bank), mlp_opacity, mlp_cov, mlp_color: the 16 parameters themselves, so
+    that autograd delivers their gradients, or each through `convert` (inference reads detached float32 contiguous copies)."""
+    def walk(seq):
+        mods = [m for m in seq if isinstance(m, torch.nn.Linear)]
+        if len(mods) != 2:
+            raise TypeError("expected nn.Sequential(Linear, ReLU, Linear, ...) as built in HAC/scene/gaussian_model.py:229-256")
+        params = (mods[0].weight, mods[0].bias, mods[1].weight, mods[1].bias)
+        return list(params) if convert is None else [convert(p) for p in params]
+    bank = walk(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
+    return bank + walk(pc.get_opacity_mlp) + walk(pc.get_cov_mlp) + walk(pc.get_color_mlp)
+
+
+def gathered_rows(pc, visible_mask, masks):
+    """Inference on an un-decoded model: (anchor, feat, grid_offsets, grid_scaling, binary_grid_masks) as the reference's five
+    `tensor[visible_mask]` gathers (:54-58), on which it then quantises.  `masks` is the model's offset-mask tensor (a property in HAC, HAC++
+    and TC-GS, `pc.get_mask(mask)` in CAT-3DGS); visible_mask None is the all-ones mask."""
+    if visible_mask is None:
+        visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
+    return pc.get_anchor[visible_mask], pc._anchor_feat[visible_mask], pc._offset[visible_mask], pc.get_scaling[visible_mask], masks[visible_mask]
+
+
+def rows_in_place(pc, visible_mask, masks):
+    """Inference on a decoded model: ((the five tensors of the model as they are), rows, n) with `rows` the visible anchors as an int32 index
+    list (None: all of them) and n their number.  The kernels read those rows in place: the reference's five gathers are 0.8 GB of copies
+    per million anchors."""
+    rows, n = None, pc.get_anchor.shape[0]
+    if visible_mask is not None:
+        rows = torch.nonzero(visible_mask).view(-1).to(torch.int32)
+        n = rows.numel()
+    return (pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, masks), rows, n
+
+
+@torch.no_grad()
+def emit_gaussians(viewpoint_camera, pc, n, rows, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks):
+    """The end of every inference path: gsnn_generate on n anchors -- the rows `rows` (int32 index list) of the tensors, or all of them (rows
+    None) -- to (xyz, color, opacity, scaling, rot).  n == 0 gives five empty tensors: the reference's tensor program runs on empty tensors
+    (:33-38, 115-167), here there is no device buffer to hand over."""
+    dev = anchor.device
+    if n == 0:
+        return tuple(torch.empty(0, c, device=dev) for c in (3, 3, 1, 3, 4))
+    K, F = pc.n_offsets, pc.feat_dim
+    tensors = mlp_tensors(pc, _f32)
+    anchor, feat, grid_offsets, grid_scaling = _f32(anchor), _f32(feat), _f32(grid_offsets), _f32(grid_scaling)
+    mask = _f32(binary_grid_masks).view(-1, K)
+    cam = _f32(viewpoint_camera.camera_center).view(3)
+    xyz = torch.empty(n * K, 3, device=dev); color = torch.empty(n * K, 3, device=dev); opacity = torch.empty(n * K, 1, device=dev)
+    scaling = torch.empty(n * K, 3, device=dev); rot = torch.empty(n * K, 4, device=dev)
+    m = C.c_int64()
+    _lib.check(_lib.lib().gsnn_generate(runtime.context(dev), n, ptr(rows), F, K, anchor.data_ptr(), feat.data_ptr(),
+                                        grid_offsets.data_ptr(), grid_scaling.data_ptr(), mask.data_ptr(), cam.data_ptr(), ptrs(tensors, 16), xyz.data_ptr(), color.data_ptr(),
+                                        opacity.data_ptr(), scaling.data_ptr(), rot.data_ptr(), C.byref(m), runtime.stream_ptr(dev)))
+    m = m.value
+    return xyz[:m], color[:m], opacity[:m], scaling[:m], rot[:m]
+
+
+def visible_rows(visible_mask, *model):
+    """Training: the model's tensors at the visible anchors, differentiably (densify.select_rows: one scan, one launch and one wait for the
+    set).  visible_mask None is every anchor, as train.py calls it: the tensors as given, nothing to gather."""
+    return model if visible_mask is None else select_rows(visible_mask, *model)
+
+
+def attribute_noise(draw, feat, scaling, offsets, q0s, adj=None, base=1.0):
+    """The three attributes with their quantisation noise and the (n, 3) steps: fresh draws through `draw` -- the calling module's
+    U(-0.5, 0.5) hook, which the caller fetches from its module's globals at call time so that tests can replace it -- in the reference's
+    order feat, scaling, offsets, then quant_noise."""
+    us = [draw(feat), draw(scaling), draw(offsets)]
+    return quant_noise([feat, scaling, offsets], us, q0s, adj, base=base)
+
+
+def rate_means(bit_feat, bit_scaling, bit_offsets, factor=None):
+    """(bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param) of the three bit tables, each sum / numel in the
+    reference's expression order, times `factor` (the mask-anchor rate of HAC, TC-GS and CAT-3DGS; HAC++ has none and multiplies nothing)."""
+    scaled = (lambda m: m) if factor is None else (lambda m: m * factor)
+    per_attribute = [scaled(torch.sum(b) / b.numel()) for b in (bit_feat, bit_scaling, bit_offsets)]
+    total = scaled((torch.sum(bit_feat) + torch.sum(bit_scaling) + torch.sum(bit_offsets)) / (bit_feat.numel() + bit_scaling.numel() + bit_offsets.numel()))
+    return (total, *per_attribute)
+
+
+def out_columns(mlp):
+    """the width of what an nn.Sequential context MLP returns, before it runs: its last Linear's"""
+    return [m for m in mlp if isinstance(m, torch.nn.Linear)][-1].out_features
+
+
+def check_context_width(who, accessor, split, shape, pc, heads=2, hint=""):
+    """The context's width against the model's: `shape` is the shape of what pc.<accessor> returns (or will return) for the anchors,
+    `heads` the F-wide heads of a row (mean and scale; HAC++'s ten-way split has `prob` too) in front of the 12 + 6 K + 3 other columns."""
+    F, K = pc.feat_dim, pc.n_offsets
+    width = heads * F + 12 + 6 * K + 3
+    if len(shape) != 2 or shape[1] != width:
+        raise ValueError(f"{who}: pc.{accessor} returns a context of shape {tuple(shape)}, {split} split has {width} columns "
+                         f"(feat_dim {F}, {K} offsets){hint}")
+    return width
+
+
+# ---- HAC's renderer (and HAC++'s inference) ------------------------------------------------------------------------------------------------
+
+def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0):
+    if is_training:
+        return _generate_training(viewpoint_camera, pc, visible_mask, step)
+    return _generate_inference(viewpoint_camera, pc, visible_mask)
+
+
+@torch.no_grad()
+def _generate_inference(viewpoint_camera, pc, visible_mask):
+    if pc.decoded_version:
+        tensors, rows, n = rows_in_place(pc, visible_mask, pc.get_mask)
+        return (*emit_gaussians(viewpoint_camera, pc, n, rows, *tensors), 0)
+    anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = gathered_rows(pc, visible_mask, pc.get_mask)
+    n = anchor.shape[0]
+    time_sub = 0
+    if n:       # quantise as the encoder would (:103-114), on the gathered rows; nothing visible runs no context and is not timed
+        torch.cuda.synchronize(); t1 = time.time()
+        q_feat, q_scaling, q_offsets = quant_steps(pc, anchor)
+        feat = ste_multistep(feat, q_feat, pc._anchor_feat.mean())
+        grid_scaling = ste_multistep(grid_scaling, q_scaling, pc.get_scaling.mean())
+        grid_offsets = ste_multistep(grid_offsets.reshape(n, -1), q_offsets, pc._offset.mean()).view_as(grid_offsets)
+        torch.cuda.synchronize(); time_sub = time.time() - t1
+    return (*emit_gaussians(viewpoint_camera, pc, n, None, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks), time_sub)
+
+
 def _generate_training(viewpoint_camera, pc, visible_mask, step):
     """HAC's training branch (:25-98, 170): noise, rate terms, then the core.  The random draws are the reference's, in its order, with its
     shapes, dtypes and devices, so that under one torch.manual_seed the noise and the chosen anchors are the reference's."""
     F, K = pc.feat_dim, pc.n_offsets
-    out_cols = [m for m in pc.get_grid_mlp if isinstance(m, torch.nn.Linear)][-1].out_features
-    if out_cols != 2 * F + 12 + 6 * K + 3:
+    if out_columns(pc.get_grid_mlp) != 2 * F + 12 + 6 * K + 3:
         raise NotImplementedError("generate_neural_gaussians(is_training=True) serves HAC's rate branch (nine-way mlp_grid split); for HAC++ call "
                                   "gauspcc_amd.neural_gaussians.neural_gaussians_train(..., mask_after_opacity=True) after the model's own rate code")
     if visible_mask is None:
@@ -368,11 +405,7 @@ def _generate_training(viewpoint_camera, pc, visible_mask, step):
         bit_offsets = pc.entropy_gaussian.forward(grid_offsets[choose].view(-1, 3 * K), mean_offsets[choose], scale_offsets[choose], Q_offsets[choose],
                                                   pc._offset.mean())
         bit_offsets = bit_offsets * masks_chosen
-        bit_per_feat_param = torch.sum(bit_feat) / bit_feat.numel() * mask_anchor_rate
-        bit_per_scaling_param = torch.sum(bit_scaling) / bit_scaling.numel() * mask_anchor_rate
-        bit_per_offsets_param = torch.sum(bit_offsets) / bit_offsets.numel() * mask_anchor_rate
-        bit_per_param = ((torch.sum(bit_feat) + torch.sum(bit_scaling) + torch.sum(bit_offsets))
-                         / (bit_feat.numel() + bit_scaling.numel() + bit_offsets.numel()) * mask_anchor_rate)
+        bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param = rate_means(bit_feat, bit_scaling, bit_offsets, mask_anchor_rate)
     xyz, color, opacity, scaling, rot, neural_opacity, keep = neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, binary_grid_masks,
                                                                                      viewpoint_camera.camera_center, pc)
     return xyz, color, opacity, scaling, rot, neural_opacity, keep, bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param

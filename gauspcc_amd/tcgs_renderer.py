@@ -5,16 +5,16 @@ TC-GS checkout swaps in at gaussian_renderer/__init__.py:22, beside tcgs_codec a
 
 `is_training=True` returns the reference's 12-tuple (:204, `lae` last), built from the library's pieces:
 
-  select_rows        the six `tensor[visible_mask]` gathers (none when visible_mask is None, as train.py calls it) and ONE gather by
-                     `choose_idx` of the noisy attributes, the context, the steps and the masks
+  visible_rows       the six `tensor[visible_mask]` gathers (none when visible_mask is None, as train.py calls it) and, through the same
+                     select_rows, ONE gather by `choose_idx` of the noisy attributes, the context, the steps and the masks
   context_rows       the (N, K 3 C + 3) input of mlp_triplane -- the tri-plane features of pc.knnanchor (step > 15000) or of the anchor
                      written K times (the repeat form), with the anchor behind them -- in one kernel when pc.triplane is the library's
                      Triplane: no torch.cat, and the backward reads the MLP's input gradient in place.  Any other pc.triplane is called as
                      the reference calls it, followed by torch.cat
   the model's own    pc.get_tri_mlp, called as the model's module whatever it is (nn.Sequential or gauspcc_amd.mlp.ContextMLP), and
                      pc.entropy_gaussian.forward for the three rate terms with the reference's means
-  quant_noise        x + U(-0.5, 0.5) * Q0 * (1 + tanh(adj)) on feat, scaling and offsets in one launch, the adjustments read in place from the
-                     last three columns of the context; in (3000, 10000] the constant step Q0
+  attribute_noise    x + U(-0.5, 0.5) * Q0 * (1 + tanh(adj)) on feat, scaling and offsets in one launch (quant_noise), the adjustments read in
+                     place from the last three columns of the context; in (3000, 10000] the constant step Q0
   the core           neural_gaussians_train(..., mask_after_opacity=False): TC-GS multiplies the mask into the opacity before the test (:152-162)
 
 Where TC-GS differs from HAC's branch: Q_offsets is 0.3 here (:44; the codec's and estimate_final_bits' 0.2 is anchor_codec.Q_OFFSETS); 15 % of
@@ -26,7 +26,7 @@ ValueError says so.
 `is_training=False` returns the 6-tuple (:206).  An un-decoded model is quantised as the encoder would (:105-121, no step gate): the context of
 the gathered anchors in repeat form, then quantise_steps -- the three STE_multistep calls in one launch -- with the means of the full tensors,
 bracketed by the reference's two synchronisations for time_sub.  A decoded model runs no context and hands the visible anchors over as an index
-list.  Both end in gsnn_generate (neural_gaussians._generate_tail).
+list (neural_gaussians.rows_in_place).  Both end in gsnn_generate (neural_gaussians.emit_gaussians).
 
 The random draws are the reference's, in its order (feat, scaling, offsets, then the rand_like), with its shapes, dtypes and devices, through
 the two hooks below (tests replace them to replay recorded draws): under one torch.manual_seed the noise and the chosen anchors are the
@@ -36,9 +36,9 @@ import time
 
 import torch
 
-from . import neural_gaussians as _ng
 from .densify import select_rows
-from .neural_gaussians import neural_gaussians_train, quant_noise, quantise_steps
+from .neural_gaussians import (attribute_noise, check_context_width, emit_gaussians, gathered_rows, neural_gaussians_train, quantise_steps, rate_means,
+                               rows_in_place, visible_rows)
 from .triplane import Triplane
 
 Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.3      # :42-44; not anchor_codec.Q_OFFSETS, the codec's 0.2
@@ -61,9 +61,7 @@ def l1_loss(network_output, gt):
 
 
 def _noise(feat, scaling, offsets, adj):
-    """the three attributes with their noise (fresh draws in the reference's order) and the (n, 3) steps"""
-    us = [_uniform_like(feat), _uniform_like(scaling), _uniform_like(offsets)]
-    return quant_noise([feat, scaling, offsets], us, Q0, adj)
+    return attribute_noise(_uniform_like, feat, scaling, offsets, Q0, adj)
 
 
 def context_input(pc, anchor, knnanchor, is_training, step):
@@ -89,12 +87,8 @@ def context_input(pc, anchor, knnanchor, is_training, step):
 
 
 def _context(pc, rows):
-    F, n_off = pc.feat_dim, pc.n_offsets
     ctx = pc.get_tri_mlp(rows)
-    width = 2 * F + 12 + 6 * n_off + 3
-    if ctx.dim() != 2 or ctx.shape[1] != width:
-        raise ValueError(f"tcgs_renderer: pc.get_tri_mlp returns a context of shape {tuple(ctx.shape)}, TC-GS's nine-way split has {width} columns "
-                         f"(feat_dim {F}, {n_off} offsets)")
+    check_context_width("tcgs_renderer", "get_tri_mlp", "TC-GS's nine-way", ctx.shape, pc)
     return ctx
 
 
@@ -104,10 +98,8 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     F, n_off = pc.feat_dim, pc.n_offsets
     model = (pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, pc.get_mask)
     mask_anchor = pc.get_mask_anchor
-    if visible_mask is None:     # every anchor (train.py's call): nothing to gather
-        anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = model
-    else:
-        anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = select_rows(visible_mask, *model)
+    anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = visible_rows(visible_mask, *model)
+    if visible_mask is not None:
         mask_anchor = mask_anchor[visible_mask]
     mask_anchor_bool = mask_anchor.detach().to(torch.bool).view(-1)
     mask_anchor_rate = (mask_anchor.sum() / mask_anchor.numel()).detach()
@@ -134,11 +126,7 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
         bit_scaling = pc.entropy_gaussian.forward(scaling_c, mean_scaling, scale_scaling, Q_c[:, 1:2], pc.get_scaling.mean())
         bit_offsets = pc.entropy_gaussian.forward(offsets_c.view(-1, 3 * n_off), mean_offsets, scale_offsets, Q_c[:, 2:3], pc._offset.mean())
         bit_offsets = bit_offsets * masks_c
-        bit_per_feat_param = torch.sum(bit_feat) / bit_feat.numel() * mask_anchor_rate
-        bit_per_scaling_param = torch.sum(bit_scaling) / bit_scaling.numel() * mask_anchor_rate
-        bit_per_offsets_param = torch.sum(bit_offsets) / bit_offsets.numel() * mask_anchor_rate
-        bit_per_param = ((torch.sum(bit_feat) + torch.sum(bit_scaling) + torch.sum(bit_offsets))
-                         / (bit_feat.numel() + bit_scaling.numel() + bit_offsets.numel()) * mask_anchor_rate)
+        bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param = rate_means(bit_feat, bit_scaling, bit_offsets, mask_anchor_rate)
     xyz, color, opacity, scaling, rot, neural_opacity, keep = neural_gaussians_train(anchor, feat, grid_offsets, grid_scaling, binary_grid_masks,
                                                                                      viewpoint_camera.camera_center, pc, mask_after_opacity=False)
     return (xyz, color, opacity, scaling, rot, neural_opacity, keep, bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param,
@@ -147,31 +135,16 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
 
 @torch.no_grad()
 def _generate_inference(viewpoint_camera, pc, visible_mask):
+    if pc.decoded_version:      # no context
+        tensors, rows, n = rows_in_place(pc, visible_mask, pc.get_mask)
+        return (*emit_gaussians(viewpoint_camera, pc, n, rows, *tensors), 0)
+    anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = gathered_rows(pc, visible_mask, pc.get_mask)
+    n = anchor.shape[0]
     time_sub = 0
-    dev = pc.get_anchor.device
-    rows = None
-    if not pc.decoded_version:
-        if visible_mask is None:
-            visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=dev)
-        anchor = pc.get_anchor[visible_mask]
-        feat = pc._anchor_feat[visible_mask]
-        grid_offsets = pc._offset[visible_mask]
-        grid_scaling = pc.get_scaling[visible_mask]
-        binary_grid_masks = pc.get_mask[visible_mask]
-        n = anchor.shape[0]
-        if n:       # quantise as the encoder would (:105-121)
-            torch.cuda.synchronize(); t1 = time.time()
-            ctx = _context(pc, context_input(pc, anchor, None, False, 0)[0])
-            feat, grid_scaling, grid_offsets, _ = quantise_steps([feat, grid_scaling, grid_offsets], Q0, ctx[:, -3:],
-                                                                 means=(pc._anchor_feat.mean(), pc.get_scaling.mean(), pc._offset.mean()))
-            torch.cuda.synchronize(); time_sub = time.time() - t1
-    else:
-        # decoded model: no context; the kernels read the visible rows of the model's tensors in place
-        anchor, feat, grid_offsets, grid_scaling, binary_grid_masks = pc.get_anchor, pc._anchor_feat, pc._offset, pc.get_scaling, pc.get_mask
-        n = anchor.shape[0]
-        if visible_mask is not None:
-            rows = torch.nonzero(visible_mask).view(-1).to(torch.int32)
-            n = rows.numel()
-    if n == 0:      # no visible anchor: the reference's tensor program runs on empty tensors; no device buffer to hand over
-        return (*_ng._no_gaussians(dev), time_sub)
-    return (*_ng._generate_tail(viewpoint_camera, pc, n, rows, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks), time_sub)
+    if n:       # quantise as the encoder would (:105-121); nothing visible runs no context and is not timed
+        torch.cuda.synchronize(); t1 = time.time()
+        ctx = _context(pc, context_input(pc, anchor, None, False, 0)[0])
+        feat, grid_scaling, grid_offsets, _ = quantise_steps([feat, grid_scaling, grid_offsets], Q0, ctx[:, -3:],
+                                                             means=(pc._anchor_feat.mean(), pc.get_scaling.mean(), pc._offset.mean()))
+        torch.cuda.synchronize(); time_sub = time.time() - t1
+    return (*emit_gaussians(viewpoint_camera, pc, n, None, anchor, feat, grid_offsets, grid_scaling, binary_grid_masks), time_sub)

@@ -10,10 +10,10 @@ chain_rate_staged is the staged form of gauspcc_amd.entropy_models.chain_rate: p
 ShadowModel copies a model (gauspcc_amd.synth.SyntheticGaussianModelCAT or the namespace of tests/cat_train_cases.py) into another dtype
 with every trainable tensor a fresh leaf, so that the restatement's gradients can be read off it.
 """
-import copy
-
 import torch
 
+from tests import branch_common
+from tests.branch_common import core_params
 from tests.ng_train_ref import ng_train_ref
 from tests.rate_ref import rate_torch
 
@@ -26,19 +26,6 @@ ATTRS = ("feat", "scaling", "offsets")
 def _hooks():
     from gauspcc_amd import cat_renderer
     return cat_renderer._uniform_like, cat_renderer._rand_like
-
-
-def _linears(seq):
-    out = []
-    for m in seq:
-        if isinstance(m, torch.nn.Linear):
-            out += [m.weight, m.bias]
-    return out
-
-
-def core_params(pc):
-    bank = _linears(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
-    return bank + _linears(pc.get_opacity_mlp) + _linears(pc.get_cov_mlp) + _linears(pc.get_color_mlp)
 
 
 def stages_of(pc):
@@ -128,40 +115,24 @@ def cat_branch_ref(cam, pc, visible_mask, step, is_training=True, mask=None, mut
     return (*out[:5], time_sub, feat_rate)
 
 
-class ShadowModel:
-    """pc in `dtype` on `device` (default: pc's): _anchor_feat, _offset, _scaling, _mask as leaves that require grad, deep copies of the
-    modules (feature_net included: it must run in `dtype`, or pass `feature_net`)."""
+class ShadowModel(branch_common.ShadowModel):
+    """branch_common.ShadowModel with CAT-3DGS's modules (feature_net included: it must run in `dtype`, or pass `feature_net`)."""
 
     def __init__(self, pc, dtype, device=None, feature_net=None):
-        dev = device or pc.get_anchor.device
-        self.src, self.dtype = pc, dtype
-        self.feat_dim, self.n_offsets, self.use_feat_bank = pc.feat_dim, pc.n_offsets, bool(getattr(pc, "use_feat_bank", False))
+        super().__init__(pc, dtype, device)
         self.decoded_version = pc.decoded_version
         self.chcm_slices_list, self.chcm_for_scaling, self.chcm_for_offsets = list(pc.chcm_slices_list), pc.chcm_for_scaling, pc.chcm_for_offsets
-        leaf = lambda t: t.detach().to(device=dev, dtype=dtype).clone().requires_grad_(True)   # noqa: E731
-        self.get_anchor = pc.get_anchor.detach().to(device=dev, dtype=dtype)
-        self._anchor_feat, self._offset = leaf(pc._anchor_feat), leaf(pc._offset)
-        self._scaling = leaf(pc._scaling) if hasattr(pc, "_scaling") else None
-        self._scaling_value = None if self._scaling is not None else leaf(pc.get_scaling)
-        self._mask = leaf(pc._mask) if hasattr(pc, "_mask") else None
-        self._mask01 = None if self._mask is not None else pc._mask01.detach().to(device=dev, dtype=dtype)
-        mod = lambda m: None if m is None else copy.deepcopy(m).to(device=dev, dtype=dtype)   # noqa: E731
-        self.feature_net = feature_net if feature_net is not None else mod(pc.feature_net)
+        self.get_anchor = self.value(pc.get_anchor)
+        self._mask01 = None if self._mask is not None else self.value(pc._mask01)
+        self.feature_net = feature_net if feature_net is not None else self.mod(pc.feature_net)
         chcm = lambda name, alt: getattr(pc, name) if hasattr(pc, name) else getattr(pc, alt, None)   # noqa: E731
-        self.get_chcm_mlp_list = mod(chcm("get_chcm_mlp_list", "mlp_chcm_list"))
-        self.get_chcm_mlp_scaling = mod(chcm("get_chcm_mlp_scaling", "mlp_chcm_scaling")) if pc.chcm_for_scaling else None
-        self.get_chcm_mlp_offsets = mod(chcm("get_chcm_mlp_offsets", "mlp_chcm_offsets")) if pc.chcm_for_offsets else None
-        self.get_opacity_mlp, self.get_cov_mlp, self.get_color_mlp = mod(pc.get_opacity_mlp), mod(pc.get_cov_mlp), mod(pc.get_color_mlp)
-        if self.use_feat_bank:
-            self.get_featurebank_mlp = mod(pc.get_featurebank_mlp)
+        self.get_chcm_mlp_list = self.mod(chcm("get_chcm_mlp_list", "mlp_chcm_list"))
+        self.get_chcm_mlp_scaling = self.mod(chcm("get_chcm_mlp_scaling", "mlp_chcm_scaling")) if pc.chcm_for_scaling else None
+        self.get_chcm_mlp_offsets = self.mod(chcm("get_chcm_mlp_offsets", "mlp_chcm_offsets")) if pc.chcm_for_offsets else None
         self.bound_updates = 0
 
     def update_anchor_bound(self):
         self.bound_updates += 1
-
-    @property
-    def get_scaling(self):
-        return torch.exp(self._scaling) if self._scaling is not None else self._scaling_value
 
     def get_mask(self, weighted_mask=None):
         if self._mask is None:
@@ -169,7 +140,7 @@ class ShadowModel:
         s = torch.sigmoid(self._mask)
         if weighted_mask is not None:
             s = s * weighted_mask.to(s)
-        return ((s > 0.01).to(s.dtype) - s).detach() + s
+        return self.straight_through(s)
 
     def get_mask_anchor(self, weighted_mask=None):
         with torch.no_grad():
@@ -177,16 +148,9 @@ class ShadowModel:
 
     def trainable(self):
         """name -> tensor of everything the branch's gradients reach, in a fixed order"""
-        out = {"_anchor_feat": self._anchor_feat, "_offset": self._offset}
-        out["_scaling"] = self._scaling if self._scaling is not None else self._scaling_value
-        if self._mask is not None:
-            out["_mask"] = self._mask
+        leaves = {"_anchor_feat": self._anchor_feat, "_offset": self._offset, "_scaling": self.scaling_leaf}
         mods = [("feature_net", self.feature_net), ("chcm_list", self.get_chcm_mlp_list), ("chcm_scaling", self.get_chcm_mlp_scaling),
                 ("chcm_offsets", self.get_chcm_mlp_offsets), ("opacity", self.get_opacity_mlp), ("cov", self.get_cov_mlp), ("color", self.get_color_mlp)]
         if self.use_feat_bank:
             mods.append(("bank", self.get_featurebank_mlp))
-        for name, m in mods:
-            if m is not None:
-                for k, p in m.named_parameters():
-                    out[f"{name}.{k}"] = p
-        return out
+        return self.walk(leaves, mods)

@@ -23,6 +23,7 @@ import types
 
 import numpy as np
 
+from tests import branch_common
 from tests.attr_pin_cases import NG_TOL, _sequential, sha256_of   # noqa: F401  (re-exported for the generator and the tests)
 from tests.hacpp_train_cases import _Streams
 
@@ -173,24 +174,9 @@ def draws(a, tag):
     return out
 
 
-class Replay:
-    """Stand-ins for the renderer's two hooks that hand out the recorded draws in order, checking shape and kind of each request."""
-
-    def __init__(self, a, tag, torch):
-        self.torch, self.queue, self.served = torch, [(i, d) for i, d in enumerate(draws(a, tag))], 0
-
-    def _next(self, t, is_rand):
-        assert self.queue, "more draws than recorded"
-        i, d = self.queue.pop(0)
-        assert (i == 3) == is_rand and tuple(d.shape) == tuple(t.shape), (i, is_rand, d.shape, tuple(t.shape))
-        self.served += 1
-        return self.torch.tensor(d).to(device=t.device, dtype=t.dtype)
-
-    def uniform_like(self, t):
-        return self._next(t, False)
-
-    def rand_like(self, t):
-        return self._next(t, True)
+def Replay(a, tag, torch):
+    """branch_common.Replay on the recorded draws of a run"""
+    return branch_common.Replay(draws(a, tag), torch)
 
 
 def expected_draws(step, training=True):

@@ -8,10 +8,10 @@ channel-context MLP), scaling and offsets noise of the chosen.
 ShadowModel copies a model (gauspcc_amd.synth.SyntheticGaussianModelPlus or the namespace of tests/hacpp_train_cases.py) into another dtype
 with every trainable tensor a fresh leaf, so that the restatement's gradients can be read off it.
 """
-import copy
-
 import torch
 
+from tests import branch_common
+from tests.branch_common import core_params
 from tests.ng_train_ref import ng_train_ref
 from tests.rate_ref import rate_torch
 
@@ -21,18 +21,6 @@ Q0 = (1, 0.001, 0.2)
 def _hooks():
     from gauspcc_amd import hac_plus_renderer
     return hac_plus_renderer._uniform_like, hac_plus_renderer._rand_like
-
-
-def _linears(seq):
-    out = []
-    for m in seq:
-        if isinstance(m, torch.nn.Linear):
-            out += [m.weight, m.bias]
-    return out
-
-
-def core_params(pc):
-    return [None] * 4 + _linears(pc.get_opacity_mlp) + _linears(pc.get_cov_mlp) + _linears(pc.get_color_mlp)
 
 
 def hacpp_branch_ref(cam, pc, visible_mask, step, mutate=None):
@@ -80,25 +68,16 @@ def hacpp_branch_ref(cam, pc, visible_mask, step, mutate=None):
     return (*out, *bits)
 
 
-class ShadowModel:
-    """pc in `dtype` on `device` (default: pc's): _anchor_feat, _offset, _scaling, _mask as leaves that require grad, deep copies of the
-    modules.  calc_interp_feat: `interp` if given (a callable of the anchors), else pc's own (which must then work in `dtype`)."""
+class ShadowModel(branch_common.ShadowModel):
+    """branch_common.ShadowModel with HAC++'s modules: deep copies of get_grid_mlp and get_deform_mlp.  calc_interp_feat: `interp` if given (a
+    callable of the anchors), else pc's own (which must then work in `dtype`)."""
 
     def __init__(self, pc, dtype, device=None, interp=None):
-        dev = device or pc.get_anchor.device
-        self.src, self.dtype = pc, dtype
-        self.feat_dim, self.n_offsets, self.use_feat_bank = pc.feat_dim, pc.n_offsets, False
-        leaf = lambda t: t.detach().to(device=dev, dtype=dtype).clone().requires_grad_(True)   # noqa: E731
-        self.get_anchor = pc.get_anchor.detach().to(device=dev, dtype=dtype)
-        self._anchor_feat, self._offset = leaf(pc._anchor_feat), leaf(pc._offset)
-        self._scaling = leaf(pc._scaling) if hasattr(pc, "_scaling") else None
-        self._scaling_value = None if self._scaling is not None else leaf(pc.get_scaling)
-        self._mask = leaf(pc._mask) if hasattr(pc, "_mask") else None
-        self._mask_value = None if self._mask is not None else pc.get_mask.detach().to(device=dev, dtype=dtype)
-        self._mask_anchor_value = None if self._mask is not None else pc.get_mask_anchor.detach().to(device=dev, dtype=dtype)
-        mod = lambda m: copy.deepcopy(m).to(device=dev, dtype=dtype)   # noqa: E731
-        self.get_grid_mlp, self.get_deform_mlp = mod(pc.get_grid_mlp), mod(pc.get_deform_mlp)
-        self.get_opacity_mlp, self.get_cov_mlp, self.get_color_mlp = mod(pc.get_opacity_mlp), mod(pc.get_cov_mlp), mod(pc.get_color_mlp)
+        super().__init__(pc, dtype, device)
+        self.get_anchor = self.value(pc.get_anchor)
+        self._mask_value = None if self._mask is not None else self.value(pc.get_mask)
+        self._mask_anchor_value = None if self._mask is not None else self.value(pc.get_mask_anchor)
+        self.get_grid_mlp, self.get_deform_mlp = self.mod(pc.get_grid_mlp), self.mod(pc.get_deform_mlp)
         self.calc_interp_feat = interp if interp is not None else pc.calc_interp_feat
         self.bound_updates = 0
 
@@ -106,15 +85,10 @@ class ShadowModel:
         self.bound_updates += 1
 
     @property
-    def get_scaling(self):
-        return torch.exp(self._scaling) if self._scaling is not None else self._scaling_value
-
-    @property
     def get_mask(self):
         if self._mask is None:
             return self._mask_value
-        s = torch.sigmoid(self._mask[:, :self.n_offsets, :])
-        return ((s > 0.01).to(s.dtype) - s).detach() + s
+        return self.straight_through(torch.sigmoid(self._mask[:, :self.n_offsets, :]))
 
     @property
     def get_mask_anchor(self):
@@ -125,12 +99,7 @@ class ShadowModel:
 
     def trainable(self):
         """name -> tensor of everything the branch's gradients reach, in a fixed order"""
-        out = {"_anchor_feat": self._anchor_feat, "_offset": self._offset}
+        leaves = {"_anchor_feat": self._anchor_feat, "_offset": self._offset}
         if self._scaling is not None:
-            out["_scaling"] = self._scaling
-        if self._mask is not None:
-            out["_mask"] = self._mask
-        for name in ("grid", "deform", "opacity", "cov", "color"):
-            for k, p in getattr(self, f"get_{name}_mlp").named_parameters():
-                out[f"mlp_{name}.{k}"] = p
-        return out
+            leaves["_scaling"] = self._scaling
+        return self.walk(leaves, [(f"mlp_{name}", getattr(self, f"get_{name}_mlp")) for name in ("grid", "deform", "opacity", "cov", "color")])

@@ -18,6 +18,7 @@ import types
 import numpy as np
 
 from gauspcc_amd.synth import CounterRNG
+from tests import branch_common
 from tests.attr_pin_cases import NG_TOL, _sequential, sha256_of   # noqa: F401  (NG_TOL: re-exported for the generator and the tests)
 
 F, K, N, CTX_DIM, HIDDEN = 50, 10, 120, 16, 100
@@ -105,24 +106,9 @@ def draws(a, step):
     return out
 
 
-class Replay:
-    """Stand-ins for the renderer's two hooks that hand out the recorded draws in order, checking shape and kind of each request."""
-
-    def __init__(self, a, step, torch):
-        self.torch, self.queue, self.served = torch, [(i, d) for i, d in enumerate(draws(a, step))], 0
-
-    def _next(self, t, is_rand):
-        assert self.queue, "more draws than recorded"
-        i, d = self.queue.pop(0)
-        assert (i == 3) == is_rand and tuple(d.shape) == tuple(t.shape), (i, is_rand, d.shape, tuple(t.shape))
-        self.served += 1
-        return self.torch.tensor(d).to(device=t.device, dtype=t.dtype)
-
-    def uniform_like(self, t):
-        return self._next(t, False)
-
-    def rand_like(self, t):
-        return self._next(t, True)
+def Replay(a, step, torch):
+    """branch_common.Replay on the recorded draws of a run"""
+    return branch_common.Replay(draws(a, step), torch)
 
 
 def model(a, torch, device="cpu", dtype=None):

@@ -11,10 +11,10 @@ float64.
 ShadowModel copies a model (gauspcc_amd.synth.SyntheticGaussianModelTC or the object of tests/tcgs_train_cases.py) into another dtype with
 every trainable tensor a fresh leaf, so that the restatement's gradients can be read off it.
 """
-import copy
-
 import torch
 
+from tests import branch_common
+from tests.branch_common import core_params
 from tests.ng_train_ref import ng_train_ref
 from tests.rate_ref import rate_torch
 
@@ -27,19 +27,6 @@ CHOOSE = 0.15
 def _hooks():
     from gauspcc_amd import tcgs_renderer
     return tcgs_renderer._uniform_like, tcgs_renderer._rand_like
-
-
-def _linears(seq):
-    out = []
-    for m in seq:
-        if isinstance(m, torch.nn.Linear):
-            out += [m.weight, m.bias]
-    return out
-
-
-def core_params(pc):
-    bank = _linears(pc.get_featurebank_mlp) if getattr(pc, "use_feat_bank", False) else [None] * 4
-    return bank + _linears(pc.get_opacity_mlp) + _linears(pc.get_cov_mlp) + _linears(pc.get_color_mlp)
 
 
 def _ste(x, q, xm):
@@ -153,31 +140,20 @@ class PlaneRef(torch.nn.Module):
         return (out, None, None) if is_training else out
 
 
-class ShadowModel:
-    """pc in `dtype` on `device` (default: pc's): _anchor_feat, _offset, _scaling, _mask and the anchor as leaves that require grad, deep copies
-    of the modules; `triplane` the given module (it must run in `dtype`) or a deep copy of pc's."""
+class ShadowModel(branch_common.ShadowModel):
+    """branch_common.ShadowModel with TC-GS's modules and the anchor as a leaf too; `triplane` the given module (it must run in `dtype`) or a
+    deep copy of pc's, `tri_mlp` likewise."""
 
     def __init__(self, pc, dtype, device=None, triplane=None, tri_mlp=None):
-        dev = device or pc.get_anchor.device
-        self.src, self.dtype = pc, dtype
-        self.feat_dim, self.n_offsets, self.use_feat_bank = pc.feat_dim, pc.n_offsets, bool(getattr(pc, "use_feat_bank", False))
+        super().__init__(pc, dtype, device)
         self.decoded_version = pc.decoded_version
-        leaf = lambda t: t.detach().to(device=dev, dtype=dtype).clone().requires_grad_(True)   # noqa: E731
-        self.get_anchor = leaf(pc.get_anchor)
+        self.get_anchor = self.leaf(pc.get_anchor)
         self._anchor = self.get_anchor
-        self._anchor_feat, self._offset = leaf(pc._anchor_feat), leaf(pc._offset)
-        self._scaling = leaf(pc._scaling) if hasattr(pc, "_scaling") else None
-        self._scaling_value = None if self._scaling is not None else leaf(pc.get_scaling)
-        self._mask = leaf(pc._mask) if hasattr(pc, "_mask") else None
-        self._mask01 = None if self._mask is not None else pc._mask01.detach().to(device=dev, dtype=dtype)
-        mod = lambda m: None if m is None else copy.deepcopy(m).to(device=dev, dtype=dtype)   # noqa: E731
-        self.triplane = triplane if triplane is not None else mod(pc.triplane)
-        self.get_tri_mlp = tri_mlp if tri_mlp is not None else mod(pc.get_tri_mlp)
-        self.get_opacity_mlp, self.get_cov_mlp, self.get_color_mlp = mod(pc.get_opacity_mlp), mod(pc.get_cov_mlp), mod(pc.get_color_mlp)
-        if self.use_feat_bank:
-            self.get_featurebank_mlp = mod(pc.get_featurebank_mlp)
-        self.x_bound_max, self.x_bound_min = (b.detach().to(device=dev, dtype=dtype).reshape(3) for b in (pc.x_bound_max, pc.x_bound_min))
-        self.knnanchor = pc.knnanchor.detach().to(device=dev, dtype=dtype)
+        self._mask01 = None if self._mask is not None else self.value(pc._mask01)
+        self.triplane = triplane if triplane is not None else self.mod(pc.triplane)
+        self.get_tri_mlp = tri_mlp if tri_mlp is not None else self.mod(pc.get_tri_mlp)
+        self.x_bound_max, self.x_bound_min = (self.value(b).reshape(3) for b in (pc.x_bound_max, pc.x_bound_min))
+        self.knnanchor = self.value(pc.knnanchor)
         self.entropy_gaussian = getattr(pc, "entropy_gaussian", None)
         self.hooks = []
 
@@ -188,15 +164,8 @@ class ShadowModel:
         self.hooks.append(("init_knn_indice", k))
 
     @property
-    def get_scaling(self):
-        return torch.exp(self._scaling) if self._scaling is not None else self._scaling_value
-
-    @property
     def get_mask(self):
-        if self._mask is None:
-            return self._mask01
-        s = torch.sigmoid(self._mask)
-        return ((s > 0.01).to(s.dtype) - s).detach() + s
+        return self._mask01 if self._mask is None else self.straight_through(torch.sigmoid(self._mask))
 
     @property
     def get_mask_anchor(self):
@@ -205,16 +174,9 @@ class ShadowModel:
 
     def trainable(self):
         """name -> tensor of everything the branch's gradients reach, in a fixed order"""
-        out = {"anchor": self.get_anchor, "_anchor_feat": self._anchor_feat, "_offset": self._offset}
-        out["_scaling"] = self._scaling if self._scaling is not None else self._scaling_value
-        if self._mask is not None:
-            out["_mask"] = self._mask
+        leaves = {"anchor": self.get_anchor, "_anchor_feat": self._anchor_feat, "_offset": self._offset, "_scaling": self.scaling_leaf}
         mods = [("triplane", self.triplane), ("tri_mlp", self.get_tri_mlp), ("opacity", self.get_opacity_mlp), ("cov", self.get_cov_mlp),
                 ("color", self.get_color_mlp)]
         if self.use_feat_bank:
             mods.append(("bank", self.get_featurebank_mlp))
-        for name, m in mods:
-            for k, p in m.named_parameters():
-                if not k.startswith("autoencoder"):
-                    out[f"{name}.{k}"] = p
-        return out
+        return {k: p for k, p in self.walk(leaves, mods).items() if not k.startswith("triplane.autoencoder")}

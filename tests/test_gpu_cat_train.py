@@ -478,8 +478,20 @@ def test_edges(arrays, monkeypatch):
         out = cat_renderer.generate_neural_gaussians(cam, pc, none, is_training=True, step=step)
         assert len(out) == 12 and [tuple(o.shape) for o in out[:7]] == shapes
         assert all(o is None for o in out[7:11]) if step == 5000 else all(torch.isnan(o) for o in out[7:11])
+    # un-decoded, nothing visible, evaluation: from step 10000 on feature_net runs on the (0, 3) anchor, is timed, and its rate comes back
+    feature_net, calls = pc.feature_net, []
+
+    def recording(anchor, itr=-1):
+        calls.append((tuple(anchor.shape), feature_net(anchor, itr=itr)))
+        return calls[-1][1]
+    pc.feature_net = recording
     out = cat_renderer.generate_neural_gaussians(cam, pc, none, is_training=False, step=12000)
     assert len(out) == 7 and [tuple(o.shape) for o in out[:5]] == shapes[:5]
+    assert len(calls) == 1 and calls[0][0] == (0, 3) and out[6] is calls[0][1][1] and type(out[5]) is float
+    out = cat_renderer.generate_neural_gaussians(cam, pc, none, is_training=False, step=5000)
+    assert len(out) == 7 and [tuple(o.shape) for o in out[:5]] == shapes[:5]
+    assert len(calls) == 1 and type(out[5]) is int and out[5] == 0 and type(out[6]) is int and out[6] == 0
+    pc.feature_net = feature_net
     # nothing chosen: the chain launches nothing, the MLPs are not run, the rates are 0 / 0
     monkeypatch.setattr(cat_renderer, "_rand_like", lambda t: torch.ones_like(t))
     torch.manual_seed(0)

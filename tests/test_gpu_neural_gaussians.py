@@ -136,3 +136,49 @@ def test_without_a_visible_mask_and_with_few_survivors(torch_cuda, mask_kind):
     # the values are compared in EVERY run: rows paired as above, so a run that keeps another set by one Gaussian cannot pass unseen
     near_zero = int(((nopa.abs() < 1e-4) & (nopa != 0)).sum())          # `borderline` above counts the masked candidates (exactly 0) as well
     _compare_paired(torch, (xyz, color, opacity, scaling, rot), (rx, rc, ro, rs, rr), nopa, rx.shape[0] - near_zero - 1)
+
+
+def _with_context_model(torch, pc, seed):
+    """pc as an un-decoded HAC model: mlp_grid with the nine-way split behind a stand-in calc_interp_feat, sin(anchor @ A + b)"""
+    F, K, dev = pc.feat_dim, pc.n_offsets, pc.get_anchor.device
+    nn = torch.nn
+    torch.manual_seed(seed)
+    pc.get_grid_mlp = nn.Sequential(nn.Linear(16, 2 * F), nn.ReLU(True), nn.Linear(2 * F, 2 * F + 12 + 6 * K + 3)).to(dev)
+    A, b = torch.randn(3, 16, device=dev), torch.randn(16, device=dev)
+    pc.calc_interp_feat = lambda x: torch.sin(x @ A + b)
+    pc.decoded_version = False
+    return pc
+
+
+def test_nothing_visible_on_an_undecoded_model_runs_no_context(torch_cuda):
+    torch = torch_cuda
+    from gauspcc_amd.neural_gaussians import generate_neural_gaussians
+
+    n = 300
+    pc, cam = _model(torch, n, 50, 10, False, seed=5)
+    grid_mlp, calls = _with_context_model(torch, pc, 5).get_grid_mlp, []
+
+    def recording(x):
+        calls.append(tuple(x.shape))
+        return grid_mlp(x)
+    pc.get_grid_mlp = recording
+    out = generate_neural_gaussians(cam, pc, torch.zeros(n, dtype=torch.bool, device="cuda"))
+    assert len(out) == 6 and [tuple(o.shape) for o in out[:5]] == [(0, 3), (0, 3), (0, 1), (0, 3), (0, 4)]
+    assert type(out[5]) is int and out[5] == 0 and calls == []
+    out = generate_neural_gaussians(cam, pc, torch.rand(n, device="cuda") > 0.2)       # the wrapper does record: one call on the visible rows
+    assert len(calls) == 1 and calls[0][1] == 16 and out[0].shape[0] > 0 and type(out[5]) is float
+
+
+@pytest.mark.parametrize("decoded", [False, True])
+def test_no_visible_mask_is_the_all_ones_mask(torch_cuda, decoded):
+    torch = torch_cuda
+    from gauspcc_amd.neural_gaussians import generate_neural_gaussians
+
+    n = 300
+    pc, cam = _model(torch, n, 50, 10, False, seed=6)
+    if not decoded:
+        _with_context_model(torch, pc, 6)
+    a = generate_neural_gaussians(cam, pc, None)
+    b = generate_neural_gaussians(cam, pc, torch.ones(n, dtype=torch.bool, device="cuda"))
+    assert a[0].shape[0] > n and all(torch.equal(x, y) for x, y in zip(a[:5], b[:5]))
+    assert type(a[5]) is (int if decoded else float) and type(b[5]) is type(a[5])

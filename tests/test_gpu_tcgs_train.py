@@ -464,6 +464,10 @@ def test_edges(arrays):
         out = generate_neural_gaussians(cam, pc, none, is_training=False)
         assert len(out) == 6 and [tuple(o.shape) for o in out[:5]] == [(0, 3), (0, 3), (0, 1), (0, 3), (0, 4)] and out[5] == 0
     pc.decoded_version = False
+    # visible_mask=None is every anchor in evaluation too (un-decoded: the context and the quantisation run on all of them)
+    a = generate_neural_gaussians(cam, pc, None, is_training=False)
+    b = generate_neural_gaussians(cam, pc, torch.ones(n, dtype=torch.bool, device=DEV), is_training=False)
+    assert a[0].shape[0] > 0 and all(torch.equal(x, y) for x, y in zip(a[:5], b[:5]))
     # a context of another width is refused
     pc.get_tri_mlp = lambda rows: rows.new_zeros(rows.shape[0], 170)
     with pytest.raises(ValueError, match="get_tri_mlp"):

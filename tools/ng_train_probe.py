@@ -11,7 +11,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from gauspcc_amd.neural_gaussians import _mlp_params, neural_gaussians_train  # noqa: E402
+from gauspcc_amd.neural_gaussians import mlp_tensors, neural_gaussians_train  # noqa: E402
 from gauspcc_amd.synth import SyntheticGaussianModel  # noqa: E402
 from tests.ng_train_ref import ng_train_ref  # noqa: E402
 
@@ -24,7 +24,7 @@ with torch.no_grad():
 ctr = ins[0].mean(dim=0)
 ext = float((ins[0].max(dim=0).values - ins[0].min(dim=0).values).max())
 cam = ctr + torch.tensor([0.0, 0.0, -1.4 * ext], device=dev)
-params = _mlp_params(pc)
+params = mlp_tensors(pc)
 for t in ins:
     t.requires_grad_(True)
 
