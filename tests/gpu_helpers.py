@@ -16,6 +16,29 @@ def _st():
     return runtime.stream_ptr(dev())
 
 
+GUARD_WORDS = 256      # 1 KB of float32 on either side, and a multiple of 16 bytes: the view keeps the allocation's alignment
+
+
+def guarded(t, device=None):
+    """The values of float32 tensor `t` as a contiguous, 16-byte-aligned view inside a NaN-filled buffer on `device` (default: t's), with
+    GUARD_WORDS of NaN in front of it and at least as many behind.  A kernel handed the view reads and writes the view's own memory, so a
+    padding read that leaves the tensor brings NaN into the result and a write that leaves it shows in guards_intact."""
+    t = t.detach()
+    assert t.dtype == torch.float32 and t.numel() > 0
+    n = t.numel()
+    buf = torch.full((GUARD_WORDS + (n + 3) // 4 * 4 + GUARD_WORDS,), float("nan"), dtype=torch.float32, device=t.device if device is None else device)
+    view = buf[GUARD_WORDS:GUARD_WORDS + n].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 0 and view._base is buf
+    return view
+
+
+def guards_intact(view):
+    """every word of the buffer around a `guarded` view is still NaN"""
+    buf, at = view._base, view.storage_offset()
+    return at >= GUARD_WORDS and bool(buf[:at].isnan().all()) and bool(buf[at + view.numel():].isnan().all())
+
+
 def sort_zyx(xyz: np.ndarray) -> np.ndarray:
     x = torch.tensor(np.ascontiguousarray(xyz, dtype=np.int32), device=dev())
     perm = torch.empty(x.shape[0], dtype=torch.int32, device=dev())

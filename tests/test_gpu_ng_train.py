@@ -6,7 +6,7 @@ import types
 import pytest
 import torch
 
-from tests.ng_train_ref import ng_train_ref, random_params, ste_masks
+from tests.ng_train_ref import fixture, ng_train_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -20,28 +20,7 @@ def _gpu():
 
 
 def _fixture(n, F, K, bank, mask_after, seed):
-    """inputs (float64 on the GPU) without a candidate the keep test could decide either way: anchors with an unmasked (HAC) or any (HAC++)
-    candidate at |tanh z| < 1e-4 are left out, so that the fp32 and float64 keep sets must agree"""
-    g = torch.Generator().manual_seed(seed)
-    d = torch.float64
-    anchor = torch.rand(n, 3, generator=g, dtype=d) * 4 - 2
-    feat = torch.randn(n, F, generator=g, dtype=d) * 0.8
-    off = torch.randn(n, K, 3, generator=g, dtype=d) * 0.3
-    sc = torch.exp(torch.randn(n, 6, generator=g, dtype=d) * 0.4 - 2.5)
-    masks = ste_masks(n, K, g)
-    if n > 4:
-        masks[: n // 5] = 0.0       # fully masked anchors
-    cam = torch.tensor([0.3, -4.0, 1.1], dtype=d)
-    params = random_params(F, K, bank, g)
-    ts = [t.to(DEV) for t in (anchor, feat, off, sc, masks, cam)]
-    ps = [None if p is None else p.to(DEV) for p in params]
-    t = ng_train_ref(*ts, ps, True)[5].view(n, K)        # tanh(z)
-    live = masks.to(DEV).view(n, K) != 0 if not mask_after else torch.ones_like(t, dtype=torch.bool)
-    ok = ~((t.abs() < 1e-4) & live).any(dim=1)
-    ts = [x[ok] for x in ts[:5]] + [ts[5]]
-    t = t[ok]
-    assert not ((t.abs() < 1e-4) & (live[ok])).any()
-    return ts, ps
+    return fixture(n, F, K, bank, mask_after, seed, DEV)
 
 
 def _pc(ps, bank):

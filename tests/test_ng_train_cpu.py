@@ -2,6 +2,7 @@
 import pytest
 import torch
 
+from tests import ng_train_ref as ref
 from tests.ng_train_ref import ng_train_ref, normalize, random_params, ste_masks
 
 
@@ -55,6 +56,38 @@ def test_rotation_eps_branch():
     assert torch.allclose(q.grad[0], g[0] / 1e-12)            # below eps the denominator is a constant
     assert torch.allclose(q.grad[1], (g[1] - r[1] * (r[1] @ g[1])) / 5.0)
     assert torch.equal(normalize(q.detach()), torch.nn.functional.normalize(q.detach(), dim=-1))
+
+
+def edge_input_failures(F, K, bank, seed=None):
+    """the conditions on the inputs of tests/test_gpu_ng_classes.py that case (F, K, bank) misses with `seed` (default: its own)"""
+    bad = []
+    for n in ref.EDGE_ROWS + ([ref.LOOP_ROWS] if (F, K, bank) in ref.LOOP_EDGES else []):
+        for mask_after in (False, True):
+            ts, ps, dropped = ref.edge_case(n, F, K, bank, mask_after, "cpu", seed)
+            assert [t.shape[0] for t in ts[:5]] == [n] * 5
+            kept = ng_train_ref(*ts, ps, mask_after)[6]
+            share = float(kept.double().mean())
+            if dropped >= 0.05:
+                bad.append((n, mask_after, "dropped", dropped))
+            if n >= 333 and not 0.1 <= share <= 0.9:
+                bad.append((n, mask_after, "kept share", share))
+            if not kept.any():
+                bad.append((n, mask_after, "nothing kept"))
+    return bad
+
+
+@pytest.mark.parametrize("F,K,bank", ref.NG_EDGES + [c for c in ref.GUARDED_EDGES if c not in ref.NG_EDGES])
+def test_edge_inputs_meet_their_conditions(F, K, bank):
+    """under 5 % of the anchors left out, 10 % to 90 % of the candidates kept, at least one Gaussian at 1, 16 and 17 anchors"""
+    assert not edge_input_failures(F, K, bank)
+
+
+def test_edge_tables():
+    assert len(ref.NG_EDGES) == 25 and len(set(ref.NG_EDGES)) == 25 and set(ref.EDGE_SEED_J) <= set(ref.NG_EDGES)
+    assert set(ref.LOOP_EDGES + ref.BITWISE_EDGES) <= set(ref.NG_EDGES) and set(ref.GRAD_K) <= set(ref.EDGE_K)
+    assert sorted({(16 * K + 63) // 64 for K in ref.EDGE_K if K <= 16}) == [1, 2, 3, 4]         # every NIT of k_ng_emit
+    strips = lambda F, K, bank: 3 + sum(-(-m // 64) for m in (K, 7 * K, 3 * K)) + (2 if bank else 0)   # noqa: E731  (F <= 64: one strip per first layer)
+    assert strips(32, 64, True) == 16 and max(strips(*c) for c in ref.NG_EDGES) == 16           # NG_MAX_STRIPS, reached and not passed
 
 
 def _hand_case():
